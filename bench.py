@@ -8,8 +8,15 @@ Frames are independent, so N GPUs shard frames with no collective ("weak").
 
 Prints ONE JSON line on rank 0 with the roofline of the dominant kernel (HIP
 events around its launches inside the timed region; algorithmic bytes per
-launch) and the CPU baseline (the oracle restatement of the
-reference, single thread, on a bounded sample of the same workload).
+launch).
+
+A plain run sets up, warms up, times `--steps` steps, writes the last step's
+outputs if `--dump-outputs DIR` is given, and prints the line.  `--full` adds
+everything else to the line: the checks of the measured batch against its
+source and the oracle, encode-only / decode-only / single-frame rates, the
+measured copy peak, the RGB, 1080p, 8K, streamed and config-4 legs, and the CPU
+baseline (the oracle restatement of the reference on a bounded sample of the
+same workload).
 """
 from __future__ import annotations
 
@@ -116,6 +123,62 @@ def cpu_baseline_threads(W, H, seconds=8.0):
             "kind": "port",
             "sample": f"{n} x {W}x{H} RGBA NICE-SYN-v1 frames ({threads} distinct, seeds 1..{threads}), "
                       f"encode+decode, {threads} threads, {el:.1f} s"}
+
+
+DUMP_FRAMES = 8            # frames of the batch sampled byte by byte
+DUMP_BYTES = 1 << 19       # sampled bytes per sampled frame (streams and pixels)
+DUMP_SEED = 0x4E494345
+
+
+def dump_outputs(torch, out_dir, streams, lens, dec, status, suffix=""):
+    """--dump-outputs: what a caller of the timed step holds after its last
+    call (encode_batch's streams and lengths, decode_batch's pixels and
+    status), as <name>.npy under `out_dir`, about 32 MB at the default sizes:
+
+      lens, status          float64 [F]: every frame's stream length and decode status
+      stream_sums           float64 [F, 2]: byte sum and position-weighted byte sum
+                            (weights i % 65521 + 1) of every stream's lens[f] bytes
+      decoded_sums          float64 [F, 2]: the same of every decoded frame
+      stream_sample         float32 [k, n]: bytes of k seeded frames at n seeded
+                            positions floor(u * lens[f]), u in [0, 1)
+      decoded_sample        float32 [k, n]: decoded bytes of the same frames at n
+                            seeded positions
+
+    Every sum is an integer below 2^53, so float64 holds it exactly; the sample
+    is fixed by DUMP_SEED and the shapes alone."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    F, stride = streams.shape
+    npx = dec.shape[1]
+    L = lens.cpu().clamp(0, stride)
+    wts = torch.arange(max(stride, npx), device=streams.device, dtype=torch.int64) % 65521 + 1
+
+    def sums(rows, n_of):
+        out = torch.zeros((F, 2), dtype=torch.int64, device=rows.device)
+        for f in range(F):
+            v = rows[f, :n_of(f)].to(torch.int64)
+            out[f, 0] = v.sum()
+            out[f, 1] = (v * wts[:v.numel()]).sum()
+        return out.cpu().numpy().astype(np.float64)
+
+    rng = np.random.default_rng(DUMP_SEED)
+    frames = np.sort(rng.choice(F, min(F, DUMP_FRAMES), replace=False))
+    n = min(DUMP_BYTES, npx)
+    u = np.sort(rng.random(n))
+    dpos = torch.from_numpy(np.sort(rng.integers(0, npx, n))).to(dec.device)
+    s_smp = np.full((len(frames), n), -1.0, np.float32)   # -1: an empty stream has no byte to sample
+    d_smp = np.empty((len(frames), n), np.float32)
+    for j, f in enumerate(frames):
+        f = int(f)
+        if int(L[f]) > 0:
+            spos = torch.from_numpy((u * int(L[f])).astype(np.int64)).to(streams.device)
+            s_smp[j] = streams[f][spos].cpu().numpy()
+        d_smp[j] = dec[f][dpos].cpu().numpy()
+    arrays = {"lens": L.numpy().astype(np.float64), "status": status.cpu().numpy().astype(np.float64),
+              "stream_sums": sums(streams, lambda f: int(L[f])), "decoded_sums": sums(dec, lambda f: npx),
+              "stream_sample": s_smp, "decoded_sample": d_smp}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), a)
 
 
 def timed_region(step, steps, sync, barrier):
@@ -534,12 +597,19 @@ def standin(args):
     if world > 1:
         dist.init_process_group("gloo")
     buf = np.random.default_rng(rank).integers(0, 256, 1 << 20, dtype=np.uint8)
-    step = (lambda: int(np.bitwise_xor.reduce(buf)))
+    last = [0]
+
+    def step():
+        last[0] = int(np.bitwise_xor.reduce(buf))
     for _ in range(args.warmup):
         step()
     barrier = (lambda: dist.barrier()) if world > 1 else (lambda: None)
     el = timed_region(step, args.steps, lambda: None, barrier)
     el = max_over_ranks(el, dist if world > 1 else None, torch.device("cpu"))
+    if args.dump_outputs:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "standin" + (f"_rank{rank}" if world > 1 else "") + ".npy"),
+                np.array([last[0]], np.float64))
     if rank == 0:
         print(json.dumps({"metric": "standin", "value": round(world * args.steps * buf.size / el / 1e6, 3),
                           "unit": "MB/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -556,6 +626,14 @@ def main():
     ap.add_argument("--frames", type=int, default=512, help="frames per step per GPU")
     ap.add_argument("--width", type=int, default=3840)
     ap.add_argument("--height", type=int, default=2160)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs (stream lengths, decode status, "
+                         "per-frame checksums and a seeded byte sample of streams and decoded pixels) as "
+                         "DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: round-trip and oracle checks of the "
+                         "measured batch, encode-only / decode-only / single-frame rates, copy peak, the RGB, "
+                         "1080p, 8K, streamed and config-4 legs, the CPU baseline (the options below)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--streamed-frames", type=int, default=1024,
@@ -576,6 +654,8 @@ def main():
 
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
     if args.standin:
@@ -623,18 +703,18 @@ def main():
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize()
-    # correctness of the measured work (outside the timed region)
-    assert int(status.abs().sum()) == 0, "decode reported an error"
-    for c in range(0, F, 64):   # chunked: a whole-batch RGB slice copy does not fit beside 1024 frames
-        assert torch.equal(dec.view(F, N, 4)[c:c + 64, :, :3], px.view(F, N, 4)[c:c + 64, :, :3]), \
-            "round trip mismatch"
-    stream_bytes = int(lens.sum())
     check = None
-    if rank == 0 and args.check_frames > 0:
-        from oracle import oracle as O
-        k = min(args.check_frames, F)
-        idx = sorted({(F - 1) * j // max(k - 1, 1) for j in range(k)})
-        check = stream_check(O, px, streams, lens, W, H, idx)
+    if args.full:
+        # correctness of the measured work (outside the timed region)
+        assert int(status.abs().sum()) == 0, "decode reported an error"
+        for c in range(0, F, 64):   # chunked: a whole-batch RGB slice copy does not fit beside 1024 frames
+            assert torch.equal(dec.view(F, N, 4)[c:c + 64, :, :3], px.view(F, N, 4)[c:c + 64, :, :3]), \
+                "round trip mismatch"
+        if rank == 0 and args.check_frames > 0:
+            from oracle import oracle as O
+            k = min(args.check_frames, F)
+            idx = sorted({(F - 1) * j // max(k - 1, 1) for j in range(k)})
+            check = stream_check(O, px, streams, lens, W, H, idx)
 
     L.nice_ctx_set_timing(ctx.ptr, 1)
     barrier = (lambda: dist.barrier()) if dist is not None else (lambda: None)
@@ -645,83 +725,85 @@ def main():
     L.nice_ctx_set_timing(ctx.ptr, 0)
     elapsed = max_over_ranks(elapsed, dist, device)
 
-    # encode-only / decode-only rates (separate short runs, outside the main timing)
-    def timed(fn, reps=2):
+    stream_bytes = int(lens.sum())
+    if args.dump_outputs:
+        dump_outputs(torch, args.dump_outputs, streams, lens, dec, status, f"_rank{rank}" if world > 1 else "")
+
+    t_enc = t_dec = t_one = t_one_enc = t_one_dec = copy_gb_s = None
+    subblock = rgb = config3 = uhd8k = stream_leg = sharded = None
+    if args.full:
+        # encode-only / decode-only rates (separate short runs, outside the main timing)
+        def timed(fn, reps=2):
+            torch.cuda.synchronize()
+            a = time.perf_counter()
+            for _ in range(reps):
+                fn()
+            torch.cuda.synchronize()
+            return (time.perf_counter() - a) / reps
+        t_enc = timed(lambda: nice.encode_batch(px, W, H, 4, streams, lens))
+        t_dec = timed(lambda: nice.decode_batch(streams, lens, W, H, 4, dec, status))
+        # single-frame latency (one 4K frame): encode, decode, encode then decode
+        one_px, one_s, one_l = px[:1], streams[:1], lens[:1]
+        one_d, one_st = dec[:1], status[:1]
+        t_one_enc = timed(lambda: nice.encode_batch(one_px, W, H, 4, one_s, one_l), reps=5)
+        t_one_dec = timed(lambda: nice.decode_batch(one_s, one_l, W, H, 4, one_d, one_st), reps=3)
+        t_one = timed(lambda: (nice.encode_batch(one_px, W, H, 4, one_s, one_l),
+                               nice.decode_batch(one_s, one_l, W, H, 4, one_d, one_st)), reps=2)
+        # measured copy peak: device-to-device copy of the frames
+        t_copy = timed(lambda: dec.copy_(px), reps=3)
+        copy_gb_s = 2 * px.numel() / t_copy / 1e9
+        # §8 f4: the 5x5 sub-block position map of one frame (8 B written per index)
+        img = nice.Image.new(W, H, 4)
+        pos = img.subblock_positions()
+        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        ev0.record()
+        for _ in range(20):
+            img.subblock_positions(out=pos)
+        ev1.record()
         torch.cuda.synchronize()
-        a = time.perf_counter()
-        for _ in range(reps):
-            fn()
-        torch.cuda.synchronize()
-        return (time.perf_counter() - a) / reps
-    t_enc = timed(lambda: nice.encode_batch(px, W, H, 4, streams, lens))
-    t_dec = timed(lambda: nice.decode_batch(streams, lens, W, H, 4, dec, status))
-    # single-frame latency (one 4K frame): encode, decode, encode then decode
-    one_px, one_s, one_l = px[:1], streams[:1], lens[:1]
-    one_d, one_st = dec[:1], status[:1]
-    t_one_enc = timed(lambda: nice.encode_batch(one_px, W, H, 4, one_s, one_l), reps=5)
-    t_one_dec = timed(lambda: nice.decode_batch(one_s, one_l, W, H, 4, one_d, one_st), reps=3)
-    t_one = timed(lambda: (nice.encode_batch(one_px, W, H, 4, one_s, one_l),
-                           nice.decode_batch(one_s, one_l, W, H, 4, one_d, one_st)), reps=2)
-    # measured copy peak: device-to-device copy of the frames
-    t_copy = timed(lambda: dec.copy_(px), reps=3)
-    copy_gb_s = 2 * px.numel() / t_copy / 1e9
-    # §8 f4: the 5x5 sub-block position map of one frame (8 B written per index)
-    img = nice.Image.new(W, H, 4)
-    pos = img.subblock_positions()
-    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    ev0.record()
-    for _ in range(20):
-        img.subblock_positions(out=pos)
-    ev1.record()
-    torch.cuda.synchronize()
-    t_pos = ev0.elapsed_time(ev1) / 20 / 1e3
-    subblock = {"workload": f"calc_pos_from map of one {W}x{H} frame", "ms": round(t_pos * 1e3, 4),
-                "gb_s": round(8 * N / t_pos / 1e9, 1), "frac": round(8 * N / t_pos / HBM_PEAK, 4)}
-    del pos
+        t_pos = ev0.elapsed_time(ev1) / 20 / 1e3
+        subblock = {"workload": f"calc_pos_from map of one {W}x{H} frame", "ms": round(t_pos * 1e3, 4),
+                    "gb_s": round(8 * N / t_pos / 1e9, 1), "frac": round(8 * N / t_pos / HBM_PEAK, 4)}
+        del pos
 
-    rgb = None
-    if args.rgb_frames:
-        try:
-            rgb = rgb_leg(torch, nice, device, W, H, args.rgb_frames, rank == 0 and args.check_frames > 0)
-        except Exception as exc:   # report, never lose the main measurement
-            rgb = {"error": repr(exc)[:300]}
-        torch.cuda.empty_cache()
+        if args.rgb_frames:
+            try:
+                rgb = rgb_leg(torch, nice, device, W, H, args.rgb_frames, rank == 0 and args.check_frames > 0)
+            except Exception as exc:   # report, never lose the main measurement
+                rgb = {"error": repr(exc)[:300]}
+            torch.cuda.empty_cache()
 
-    config3 = None
-    if args.config3_frames:
-        try:
-            config3 = batch_leg(torch, nice, device, 1920, 1080, args.config3_frames, 1 + rank * args.config3_frames,
-                                rank == 0 and args.check_frames > 0)
-        except Exception as exc:   # report, never lose the main measurement
-            config3 = {"error": repr(exc)[:300]}
-        torch.cuda.empty_cache()
-    uhd8k = None
-    if args.uhd8k_frames:
-        try:
-            uhd8k = batch_leg(torch, nice, device, 7680, 4320, args.uhd8k_frames, 7001 + rank * args.uhd8k_frames,
-                              rank == 0 and args.check_frames > 0, what="8k")
-        except Exception as exc:   # report, never lose the main measurement
-            uhd8k = {"error": repr(exc)[:300]}
-        torch.cuda.empty_cache()
+        if args.config3_frames:
+            try:
+                config3 = batch_leg(torch, nice, device, 1920, 1080, args.config3_frames,
+                                    1 + rank * args.config3_frames, rank == 0 and args.check_frames > 0)
+            except Exception as exc:   # report, never lose the main measurement
+                config3 = {"error": repr(exc)[:300]}
+            torch.cuda.empty_cache()
+        if args.uhd8k_frames:
+            try:
+                uhd8k = batch_leg(torch, nice, device, 7680, 4320, args.uhd8k_frames, 7001 + rank * args.uhd8k_frames,
+                                  rank == 0 and args.check_frames > 0, what="8k")
+            except Exception as exc:   # report, never lose the main measurement
+                uhd8k = {"error": repr(exc)[:300]}
+            torch.cuda.empty_cache()
 
-    stream_leg = None
-    if args.streamed_frames:
-        try:
-            stream_leg = streamed(torch, nice, dist, device, px, W, H, rank, world, args.streamed_frames)
-        except Exception as exc:   # report, never lose the main measurement
-            stream_leg = {"error": repr(exc)[:300]}
+        if args.streamed_frames:
+            try:
+                stream_leg = streamed(torch, nice, dist, device, px, W, H, rank, world, args.streamed_frames)
+            except Exception as exc:   # report, never lose the main measurement
+                stream_leg = {"error": repr(exc)[:300]}
 
-    sharded = None
-    if args.sharded_side:
-        del px, streams, dec
-        torch.cuda.empty_cache()
-        try:
-            if world > 1:
-                sharded = sharded_image(torch, nice, dist, device, args.sharded_side, rank, world)
-            else:
-                sharded = config4_one_gpu(torch, nice, device, args.sharded_side)
-        except Exception as exc:   # report, never lose the main measurement
-            sharded = {"error": repr(exc)[:300]}
+        if args.sharded_side:
+            del px, streams, dec
+            torch.cuda.empty_cache()
+            try:
+                if world > 1:
+                    sharded = sharded_image(torch, nice, dist, device, args.sharded_side, rank, world)
+                else:
+                    sharded = config4_one_gpu(torch, nice, device, args.sharded_side)
+            except Exception as exc:   # report, never lose the main measurement
+                sharded = {"error": repr(exc)[:300]}
 
     names = [L.nice_phase_name(i).decode() for i in range(32)]
     phase = {names[i]: {"ms_total": round(ms[i], 3), "launches": int(cnt[i])}
@@ -759,7 +841,7 @@ def main():
                    "channels": 4, "frames_per_gpu_per_step": F,
                    "parallelism": f"frames sharded over {world} GPU(s), no collective"},
         "roofline": {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 2),
-                     "copy_peak_measured": round(copy_gb_s, 1),
+                     "copy_peak_measured": copy_gb_s and round(copy_gb_s, 1),   # --full
                      "peak": HBM_PEAK / 1e9, "unit": "GB/s",
                      "frac": round(achieved * 1e9 / HBM_PEAK, 5),
                      "traffic": traffic,
@@ -771,11 +853,12 @@ def main():
         # whole path against HBM: encode (px in + stream out) + decode (stream in + px out)
         "path_roofline_frac": round(2 * (in_bytes + stream_bytes) / (elapsed / args.steps)
                                     / HBM_PEAK * world, 5),
-        "encode_mpix_s": round(F * N / t_enc / 1e6, 2),
-        "decode_mpix_s": round(F * N / t_dec / 1e6, 2),
-        "single_frame_latency_ms": round(t_one * 1e3, 2),
-        "single_frame_encode_ms": round(t_one_enc * 1e3, 3),
-        "single_frame_decode_ms": round(t_one_dec * 1e3, 3),
+        # from here on, what is None in a plain run is measured under --full
+        "encode_mpix_s": t_enc and round(F * N / t_enc / 1e6, 2),
+        "decode_mpix_s": t_dec and round(F * N / t_dec / 1e6, 2),
+        "single_frame_latency_ms": t_one and round(t_one * 1e3, 2),
+        "single_frame_encode_ms": t_one_enc and round(t_one_enc * 1e3, 3),
+        "single_frame_decode_ms": t_one_dec and round(t_one_dec * 1e3, 3),
         "stream_check": check,
         "subblock_positions": subblock,
         "rgb_4k": rgb,
@@ -791,7 +874,7 @@ def main():
     }
     # rank 0 only, after every GPU leg (at N > 1 the other ranks wait at the
     # final barrier; their GPUs are idle by then)
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         from oracle import oracle as O
         try:   # the reference's release profile with target-cpu=native
             flags = O.use_native()

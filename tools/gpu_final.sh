@@ -7,5 +7,5 @@ timeout -k 10 900 python -u -m pytest tests -m gpu -q -x --timeout 120 --timeout
 tail -2 $O/pytest_gpu.log
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.log 2>&1
 cat $O/smoke.log | tail -2
-timeout -k 10 400 python bench.py > $O/bench.json 2> $O/bench.err
+timeout -k 10 400 python bench.py --full > $O/bench.json 2> $O/bench.err
 cut -c1-400 $O/bench.json

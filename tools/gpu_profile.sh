@@ -13,11 +13,11 @@ if [ -z "$SKIP_TESTS" ]; then   # (tools/gpu_r04.sh runs them first)
   timeout -k 10 900 python -u -m pytest tests -m gpu -q -x --timeout 120 --timeout-method thread > $O/pytest_gpu.log 2>&1
   tail -2 $O/pytest_gpu.log
 fi
-timeout -k 10 400 python bench.py --frames $FR > $O/bench.json 2> $O/bench.err
+timeout -k 10 400 python bench.py --full --frames $FR > $O/bench.json 2> $O/bench.err
 cat $O/bench.json
 cd /tmp
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $S/kt -o run -- \
-  python3 $R/bench.py --frames $FR --steps 3 --warmup 1 --no-cpu-baseline --streamed-frames 0 > $O/kt.log 2>&1
+  python3 $R/bench.py --full --frames $FR --steps 3 --warmup 1 --no-cpu-baseline --streamed-frames 0 > $O/kt.log 2>&1
 # counter passes: every dispatch encodes or decodes the same 32 frames (no
 # single-frame or config-4 dispatches in the per-kernel averages)
 timeout -k 10 400 rocprofv3 --pmc FETCH_SIZE --kernel-include-regex "nice::" --output-format csv -d $S/pmc_fetch -o run -- \
