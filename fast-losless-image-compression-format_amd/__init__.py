@@ -26,6 +26,7 @@ from dataclasses import dataclass
 __all__ = [
     "Image", "encode", "decode", "encode_bytes", "decode_bytes", "encode_bound",
     "encode_batch", "decode_batch", "Context", "Pipeline", "NiceError", "lib", "LIB_PATH",
+    "packed_bound", "pack_streams", "encode_batch_packed", "decode_batch_packed", "save_packed", "load_packed",
     "DEC_STRICT_REFERENCE", "DEC_ALPHA_FILL_FF", "DEC_TOLERANT_HEADER",
 ]
 
@@ -51,6 +52,7 @@ EXPORTS = [
     "nice_band_assemble", "nice_tile_pixels",
     "nice_pipe_create", "nice_pipe_destroy", "nice_pipe_stream_stride", "nice_pipe_encode",
     "nice_pipe_decode", "nice_pipe_set_checksums",
+    "nice_packed_bound", "nice_pack_streams_dev", "nice_encode_batch_packed_dev", "nice_decode_packed_dev",
 ]
 
 
@@ -99,6 +101,13 @@ def lib():
                                         u32, ctypes.c_uint8, u8p, u64, u32, u8p]
     L.nice_decode_batch_dev_hl.argtypes = [ctypes.c_void_p, ctypes.c_void_p, u8p, u64, u8p, ctypes.c_void_p, u32,
                                            u32, u32, ctypes.c_uint8, u8p, u64, u32, u8p]
+    L.nice_packed_bound.restype = u64
+    L.nice_packed_bound.argtypes = [u32, u32, u32]
+    L.nice_pack_streams_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, u8p, u64, u8p, u32, u8p, u64, u8p, u8p]
+    L.nice_encode_batch_packed_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, u8p, u64, u32, u32, u32,
+                                               ctypes.c_uint8, ctypes.c_uint8, u8p, u64, u8p, u8p, u8p]
+    L.nice_decode_packed_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, u8p, u64, u8p, u8p, ctypes.c_void_p,
+                                         u32, u32, u32, ctypes.c_uint8, u8p, u64, u32, u8p]
     L.nice_pipe_create.argtypes = [ctypes.c_int, u32, u32, ctypes.c_uint8, u32, u32,
                                    ctypes.POINTER(ctypes.c_void_p)]
     L.nice_pipe_destroy.argtypes = [ctypes.c_void_p]
@@ -290,6 +299,169 @@ def decode_batch(streams, stream_len, width: int, height: int, out_channels: int
         hl = (ctypes.c_uint64 * n)(*hl_list)
         rc = lib().nice_decode_batch_dev_hl(*args, ctypes.cast(hl, ctypes.c_void_p), *tail)
     _check(rc, "nice_decode_batch_dev")
+
+
+# ---- packed stream batches (include/nice.h, "packed stream batches") --------
+def packed_bound(n_frames: int, width: int, height: int) -> int:
+    """Worst-case size of a packed batch of ``n_frames`` width x height streams."""
+    return int(lib().nice_packed_bound(n_frames, width, height))
+
+
+def _stream_of(torch, stream, device):
+    return ctypes.c_void_p(stream.cuda_stream) if stream is not None else _stream_ptr(torch, device)
+
+
+def pack_streams(streams, stream_len, packed, off, status, stream=None, ctx: "_Ctx | None" = None) -> None:
+    """Compact ``streams`` (uint8 cuda [n, stride], stride a multiple of 4) with
+    byte lengths ``stream_len`` (int64 cuda [n]) into ``packed`` (uint8 cuda,
+    16-byte aligned): stream f at ``packed[off[f] : off[f] + stream_len[f]]``,
+    ``off`` (int64 cuda [n + 1]) written in full, ``off[n]`` the packed size.
+    ``status`` (int32 cuda [1]) receives OK, E_CAPACITY (``off[n]`` exceeds
+    ``packed.numel()``; nothing is written past it) or E_ARG (a length above
+    the stride).  Asynchronous, never waits for the device."""
+    import torch
+    dev = streams.device.index or 0
+    n = streams.shape[0]
+    if stream_len.numel() < n or off.numel() < n + 1:
+        raise NiceError(E_ARG, "pack_streams: stream_len needs n entries, off n + 1")
+    rc = lib().nice_pack_streams_dev(
+        (ctx or _ctx(dev)).ptr, _stream_of(torch, stream, streams.device), ctypes.c_void_p(streams.data_ptr()),
+        streams.stride(0), ctypes.c_void_p(stream_len.data_ptr()), n,
+        ctypes.c_void_p(packed.data_ptr()), packed.numel(), ctypes.c_void_p(off.data_ptr()),
+        ctypes.c_void_p(status.data_ptr()))
+    _check(rc, "nice_pack_streams_dev")
+
+
+def encode_batch_packed(px, width: int, height: int, channels: int, packed, off, out_len, status,
+                        channels_out: int | None = None, stream=None, ctx: "_Ctx | None" = None) -> None:
+    """``encode_batch`` whose streams land packed: ``px`` (uint8 cuda
+    [n, W*H*channels]) is encoded into a strided scratch the context owns and
+    reuses, then compacted into ``packed`` as by ``pack_streams`` (``off``
+    int64 cuda [n + 1], ``out_len`` int64 cuda [n], ``status`` int32 cuda [1]).
+    ``packed_bound(n, width, height)`` bytes always suffice; a smaller buffer
+    gives E_CAPACITY in ``status`` and the needed size in ``off[n]``."""
+    import torch
+    dev = px.device.index or 0
+    n = px.shape[0]
+    if out_len.numel() < n or off.numel() < n + 1:
+        raise NiceError(E_ARG, "encode_batch_packed: out_len needs n entries, off n + 1")
+    rc = lib().nice_encode_batch_packed_dev(
+        (ctx or _ctx(dev)).ptr, _stream_of(torch, stream, px.device), ctypes.c_void_p(px.data_ptr()), px.stride(0),
+        n, width, height, channels, channels if channels_out is None else channels_out,
+        ctypes.c_void_p(packed.data_ptr()), packed.numel(), ctypes.c_void_p(off.data_ptr()),
+        ctypes.c_void_p(out_len.data_ptr()), ctypes.c_void_p(status.data_ptr()))
+    _check(rc, "nice_encode_batch_packed_dev")
+
+
+def decode_batch_packed(packed, off, stream_len, width: int, height: int, out_channels: int, px, status,
+                        flags: int = DEC_ALPHA_FILL_FF, stream=None, ctx: "_Ctx | None" = None,
+                        host_len=None, packed_bytes: int | None = None) -> None:
+    """``decode_batch`` reading the streams in place from ``packed`` (uint8 cuda,
+    16-byte aligned): frame i is the stream at ``off[i]`` with ``stream_len[i]``
+    bytes (int64 cuda tensors of n entries each; ``off`` may be a whole n + 1
+    table, and a gathered subset in any order with repeats decodes those
+    frames).  n = ``stream_len.numel()``.  ``packed_bytes`` (default
+    ``packed.numel()``) bounds every ``off[i] + stream_len[i]``; a frame past it
+    or with an offset that is not a multiple of 16 gets E_ARG in ``status``
+    (int32 cuda [n]), the others decode.  ``host_len`` as for ``decode_batch``."""
+    import torch
+    dev = packed.device.index or 0
+    n = stream_len.numel()
+    if off.numel() < n or status.numel() < n:
+        raise NiceError(E_ARG, "decode_batch_packed: off and status need one entry per frame")
+    if not off.is_contiguous() or not stream_len.is_contiguous():
+        raise NiceError(E_ARG, "decode_batch_packed: off and stream_len must be contiguous")
+    pb = packed.numel() if packed_bytes is None else int(packed_bytes)
+    if pb > packed.numel():
+        raise NiceError(E_ARG, "decode_batch_packed: packed_bytes exceeds the buffer")
+    hl = None
+    if host_len is not None:
+        hl_list = [int(x) for x in host_len]
+        if len(hl_list) != n:
+            raise NiceError(E_ARG, f"host_len has {len(hl_list)} entries for {n} frames")
+        hl = ctypes.cast((ctypes.c_uint64 * max(n, 1))(*hl_list), ctypes.c_void_p)
+    rc = lib().nice_decode_packed_dev(
+        (ctx or _ctx(dev)).ptr, _stream_of(torch, stream, packed.device), ctypes.c_void_p(packed.data_ptr()), pb,
+        ctypes.c_void_p(off.data_ptr()), ctypes.c_void_p(stream_len.data_ptr()), hl, n, width, height,
+        out_channels, ctypes.c_void_p(px.data_ptr()), px.stride(0), flags, ctypes.c_void_p(status.data_ptr()))
+    _check(rc, "nice_decode_packed_dev")
+
+
+# Host-side container of a packed batch: one file, little-endian throughout.
+#   header (40 bytes): magic "NICEPACK", u32 version (1), u32 n, u32 width,
+#                      u32 height, u32 channels, u32 reserved (0), u64 packed size
+#   n x u64 stream lengths, (n + 1) x u64 offsets, then the packed bytes
+_PACK_MAGIC = b"NICEPACK"
+_PACK_VERSION = 1
+_PACK_HEADER = "<8sIIIIIIQ"
+
+
+def save_packed(path, packed, off, stream_len, width: int, height: int, channels: int) -> None:
+    """Write a packed batch (tensors on the GPU or the CPU) to ``path``: one
+    device-to-host copy of ``packed[:off[n]]``."""
+    import struct
+    import numpy as np
+    lens = np.asarray(stream_len.detach().cpu().numpy(), dtype=np.int64).reshape(-1)
+    n = lens.size
+    offs = np.asarray(off.detach().cpu().numpy(), dtype=np.int64).reshape(-1)
+    if offs.size != n + 1:
+        raise NiceError(E_ARG, f"save_packed: off has {offs.size} entries for {n} streams")
+    size = int(offs[n])
+    if size < 0 or size > packed.numel():
+        raise NiceError(E_ARG, "save_packed: off[n] exceeds the packed buffer")
+    blob = packed.detach().reshape(-1)[:size].cpu().numpy()
+    with open(path, "wb") as fh:
+        fh.write(struct.pack(_PACK_HEADER, _PACK_MAGIC, _PACK_VERSION, n, width, height, channels, 0, size))
+        fh.write(lens.astype("<u8").tobytes())
+        fh.write(offs.astype("<u8").tobytes())
+        fh.write(blob.tobytes())
+
+
+def load_packed(path, device=None):
+    """Read a ``save_packed`` file: returns ``(packed, off, stream_len, width,
+    height, channels)`` with uint8 / int64 / int64 tensors on ``device`` (one
+    host-to-device copy of the blob), or on the CPU with ``device=None`` (no
+    GPU needed).  A file that is not a consistent packed batch raises
+    NiceError(E_FORMAT)."""
+    import struct
+    import numpy as np
+    import torch
+
+    def bad(why):
+        return NiceError(E_FORMAT, f"load_packed({path}): {why}")
+
+    hsz = struct.calcsize(_PACK_HEADER)
+    fsize = os.path.getsize(path)
+    with open(path, "rb") as fh:
+        head = fh.read(hsz)
+        if len(head) < hsz:
+            raise bad("truncated header")
+        magic, version, n, width, height, channels, _, size = struct.unpack(_PACK_HEADER, head)
+        if magic != _PACK_MAGIC:
+            raise bad("wrong magic")
+        if version != _PACK_VERSION:
+            raise bad(f"version {version}")
+        if size % 16 or size >= 1 << 62:
+            raise bad("packed size")
+        if fsize != hsz + 8 * n + 8 * (n + 1) + size:
+            raise bad("file size does not match the header")
+        lens = np.frombuffer(fh.read(8 * n), "<u8")
+        offs = np.frombuffer(fh.read(8 * (n + 1)), "<u8")
+        if offs[0] != 0 or offs[n] != size or (offs % 16).any():
+            raise bad("offsets not 16-byte aligned from 0 to the packed size")
+        if (offs[1:] < offs[:-1]).any():
+            raise bad("offsets not monotone")
+        if (lens > offs[1:] - offs[:-1]).any():
+            raise bad("a stream overlaps the next")
+        blob = np.frombuffer(fh.read(size), np.uint8)
+        if blob.size != size:
+            raise bad("truncated")
+    packed = torch.from_numpy(blob.copy())
+    off = torch.from_numpy(offs.astype(np.int64))
+    stream_len = torch.from_numpy(lens.astype(np.int64))
+    if device is not None:
+        packed, off, stream_len = packed.to(device), off.to(device), stream_len.to(device)
+    return packed, off, stream_len, width, height, channels
 
 
 def checksum64(buf) -> int:

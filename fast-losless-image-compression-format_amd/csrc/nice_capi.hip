@@ -167,6 +167,7 @@ struct nice_ctx {
   int device = 0;
   std::mutex mu;
   Arena enc, dec, host_px, host_out, dev_len, band, band_hdr;
+  Arena pack;   // nice_encode_batch_packed_dev: the strided streams before they are packed
   PhaseTimer timer;
   BandState bs;
   // decoder record tags (DecArgs::rec_tag): the region the last call used and its tag
@@ -232,6 +233,7 @@ void nice_ctx_destroy(nice_ctx* ctx) {
   ctx->dev_len.release();
   ctx->band.release();
   ctx->band_hdr.release();
+  ctx->pack.release();
   ctx->timer.release();
   (void)hipSetDevice(prev);
   delete ctx;
@@ -243,13 +245,22 @@ static uint32_t tiles_for(uint32_t w, uint32_t h) {
 }
 
 int nice_ctx_reserve(nice_ctx* ctx, uint32_t n_frames, uint32_t w, uint32_t h) {
-  if (!ctx) return NICE_E_ARG;
-  NICE_HIP(hipSetDevice(ctx->device));
-  EncLayout L = enc_layout(n_frames, tiles_for(w, h), (uint64_t)w * h);
-  return ctx->enc.grow(L.total);
+  return nice::ctx_reserve_impl(ctx, n_frames, w, h, true);
 }
 
 }  // extern "C"
+
+// nice_encode_batch_packed_dev's strided scratch: one slot per frame
+static uint64_t packed_slot_bytes(uint32_t w, uint32_t h) { return align_up(nice_encode_bound(w, h), 256); }
+
+int nice::ctx_reserve_impl(nice_ctx* ctx, uint32_t n_frames, uint32_t w, uint32_t h, bool with_packed) {
+  if (!ctx) return NICE_E_ARG;
+  NICE_HIP(hipSetDevice(ctx->device));
+  EncLayout L = enc_layout(n_frames, tiles_for(w, h), (uint64_t)w * h);
+  int rc = ctx->enc.grow(L.total);
+  if (rc == NICE_OK && with_packed) rc = ctx->pack.grow((size_t)n_frames * packed_slot_bytes(w, h));
+  return rc;
+}
 
 namespace {
 EncArgs enc_args(const EncLayout& L, uint8_t* base, uint32_t n_frames, uint32_t w, uint32_t h,
@@ -637,6 +648,55 @@ int nice_decode_batch_dev_hl(nice_ctx* ctx, void* stream, const uint8_t* d_strea
                                  out_channels, d_px, px_stride, flags, d_status);
 }
 
+// ---- packed stream batches -------------------------------------------------
+uint64_t nice_packed_bound(uint32_t n_frames, uint32_t w, uint32_t h) {
+  return (uint64_t)n_frames * align_up(nice_encode_bound(w, h), 16);
+}
+
+int nice_pack_streams_dev(nice_ctx* ctx, void* stream, const uint8_t* d_streams, uint64_t stream_stride,
+                          const uint64_t* d_stream_len, uint32_t n_frames, uint8_t* d_packed, uint64_t packed_cap,
+                          uint64_t* d_off, int32_t* d_status) {
+  if (!ctx || !d_off || !d_status) return NICE_E_ARG;
+  if (n_frames && (!d_streams || !d_stream_len)) return NICE_E_ARG;
+  if (!d_packed && packed_cap) return NICE_E_ARG;
+  if ((stream_stride & 3) || ((uintptr_t)d_streams & 3) || ((uintptr_t)d_packed & 15)) return NICE_E_ARG;
+  NICE_HIP(hipSetDevice(ctx->device));
+  return nice::pack_streams_launch(stream, ctx->cus, d_streams, stream_stride, d_stream_len, n_frames, d_packed,
+                                   packed_cap, d_off, d_status);
+}
+
+int nice_encode_batch_packed_dev(nice_ctx* ctx, void* stream, const uint8_t* d_px, uint64_t frame_stride,
+                                 uint32_t n_frames, uint32_t w, uint32_t h, uint8_t channels, uint8_t channels_out,
+                                 uint8_t* d_packed, uint64_t packed_cap, uint64_t* d_off, uint64_t* d_out_len,
+                                 int32_t* d_status) {
+  if (!ctx || !d_off || !d_out_len || !d_status) return NICE_E_ARG;
+  if ((!d_packed && packed_cap) || ((uintptr_t)d_packed & 15)) return NICE_E_ARG;
+  if ((uint64_t)w * h > (1ull << 30)) return NICE_E_ARG;
+  NICE_HIP(hipSetDevice(ctx->device));
+  const uint64_t slot = packed_slot_bytes(w, h);
+  int rc = ctx->pack.grow((size_t)n_frames * slot);
+  if (rc) return rc;
+  uint8_t* scratch = (uint8_t*)ctx->pack.ptr;
+  if (n_frames) {
+    rc = nice_encode_batch_dev(ctx, stream, d_px, frame_stride, n_frames, w, h, channels, channels_out, scratch, slot,
+                               d_out_len);
+    if (rc) return rc;
+  } else if (channels != 3 && channels != 4) {
+    return NICE_E_ARG;
+  }
+  return nice::pack_streams_launch(stream, ctx->cus, scratch, slot, d_out_len, n_frames, d_packed, packed_cap, d_off,
+                                   d_status);
+}
+
+int nice_decode_packed_dev(nice_ctx* ctx, void* stream, const uint8_t* d_packed, uint64_t packed_bytes,
+                           const uint64_t* d_off, const uint64_t* d_stream_len, const uint64_t* h_stream_len,
+                           uint32_t n_frames, uint32_t w, uint32_t h, uint8_t out_channels, uint8_t* d_px,
+                           uint64_t px_stride, uint32_t flags, int32_t* d_status) {
+  if (!d_off) return NICE_E_ARG;
+  return nice::decode_batch_impl(ctx, stream, d_packed, 0, d_stream_len, h_stream_len, n_frames, w, h, out_channels,
+                                 d_px, px_stride, flags, d_status, d_off, packed_bytes);
+}
+
 }  // extern "C"
 
 // h_stream_len: the lengths on the host when the caller has them (saves a
@@ -644,10 +704,13 @@ int nice_decode_batch_dev_hl(nice_ctx* ctx, void* stream, const uint8_t* d_strea
 int nice::decode_batch_impl(nice_ctx* ctx, void* stream, const uint8_t* d_streams, uint64_t stream_stride,
                             const uint64_t* d_stream_len, const uint64_t* h_stream_len, uint32_t n_frames,
                             uint32_t w, uint32_t h, uint8_t out_channels, uint8_t* d_px, uint64_t px_stride,
-                            uint32_t flags, int32_t* d_status) {
+                            uint32_t flags, int32_t* d_status, const uint64_t* d_stream_off,
+                            uint64_t packed_bytes) {
   if (!ctx || !d_streams || !d_stream_len || !d_status) return NICE_E_ARG;
   if (out_channels != 3 && out_channels != 4) return NICE_E_ARG;
-  if ((stream_stride & 3) || ((uintptr_t)d_streams & 3)) return NICE_E_ARG;
+  const bool packed = d_stream_off != nullptr;
+  if (packed ? ((uintptr_t)d_streams & 15) != 0 : ((stream_stride & 3) || ((uintptr_t)d_streams & 3)))
+    return NICE_E_ARG;
   const uint64_t N = (uint64_t)w * h;
   if (N > (1ull << 30)) return NICE_E_ARG;
   if (n_frames == 0) return NICE_OK;
@@ -665,8 +728,11 @@ int nice::decode_batch_impl(nice_ctx* ctx, void* stream, const uint8_t* d_stream
     NICE_HIP(hipStreamSynchronize(st));
   }
   uint64_t max_len = 0;
-  for (uint64_t l : lens) {
-    if (l > stream_stride) return NICE_E_ARG;
+  for (uint64_t& l : lens) {
+    // packed: a length the buffer cannot hold fails its frame on the device
+    // (dec_tables), not the batch; it sizes no scratch
+    if (!packed && l > stream_stride) return NICE_E_ARG;
+    if (packed && l > packed_bytes) l = 0;
     max_len = l > max_len ? l : max_len;
   }
   const uint64_t D = FILE_HEADER_BYTES * 8 + TABLE_HEADER_BITS;
@@ -796,6 +862,8 @@ int nice::decode_batch_impl(nice_ctx* ctx, void* stream, const uint8_t* d_stream
   a.streams = d_streams;
   a.stream_stride = stream_stride;
   a.stream_len = (const unsigned long long*)d_stream_len;
+  a.stream_off = (const unsigned long long*)d_stream_off;
+  a.packed_bytes = packed_bytes;
   a.n_frames = n_frames;
   a.W = w;
   a.H = h;

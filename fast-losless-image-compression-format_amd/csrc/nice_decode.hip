@@ -56,11 +56,20 @@ __global__ __launch_bounds__(256) void dec_tables(DecArgs a) {
   __shared__ uint16_t order[N_BINS];
   __shared__ int bad;
   const uint32_t f = blockIdx.x;
-  const uint8_t* s = a.streams + (uint64_t)f * a.stream_stride;
   const uint64_t len = a.stream_len[f];
   DecTables* T = reinterpret_cast<DecTables*>(a.tables) + f;
   if (threadIdx.x == 0) bad = 0;
   __syncthreads();
+  if (a.stream_off) {
+    // packed batch: the stream must start on a granule and lie inside the
+    // buffer -- checked before any byte of it is read
+    const uint64_t o = a.stream_off[f];
+    if ((o & 15u) || o > a.packed_bytes || len > a.packed_bytes - o) {
+      if (threadIdx.x == 0) set_status(&a.status[f], NICE_E_ARG);
+      return;
+    }
+  }
+  const uint8_t* s = dec_stream_ptr(a, f);
   if (len < (uint64_t)FILE_HEADER_BYTES + (TABLE_HEADER_BITS + 7) / 8) {
     if (threadIdx.x == 0) set_status(&a.status[f], NICE_E_FORMAT);
     return;
@@ -76,8 +85,9 @@ __global__ __launch_bounds__(256) void dec_tables(DecArgs a) {
   }
   // the host sized the slice scratch from its copy of the lengths
   // (nice_decode_batch_dev_hl): a device length past that bound or the stream
-  // stride fails the frame before any kernel indexes slices by it
-  if (len > a.stream_stride ||
+  // stride fails the frame before any kernel indexes slices by it (packed
+  // batches: the offset checks above take the stride's place)
+  if ((!a.stream_off && len > a.stream_stride) ||
       n_chunks(len, FILE_HEADER_BYTES * 8 + TABLE_HEADER_BITS, a.chunk_bits) > a.max_chunks) {
     if (threadIdx.x == 0) set_status(&a.status[f], NICE_E_ARG);
     return;
@@ -716,7 +726,7 @@ __global__ __launch_bounds__(DEC_PARSE_THREADS) PARSE_ATTR void dec_sync(DecArgs
   SP.load(S);
   uint32_t* wring = ring + wave * 64u * RING_STRIDE;
   const uint32_t* my = wring + (threadIdx.x & 63u) * RING_STRIDE;
-  const uint8_t* p = a.streams + (uint64_t)f * a.stream_stride;
+  const uint8_t* p = dec_stream_ptr(a, f);
   const bool al16 = (reinterpret_cast<uintptr_t>(p) & 15u) == 0;
   const bool check = last != ~0ull;
   const uint32_t nvalid_old = (uint32_t)(last >> 56);
@@ -1000,7 +1010,7 @@ __global__ __launch_bounds__(SETTLE_THREADS) void dec_sync_settle(DecArgs a, con
   const uint32_t t = threadIdx.x;
   uint32_t* wring = ring + (t & ~63u) * RING_STRIDE;
   const uint32_t* my = ring + t * RING_STRIDE;
-  const uint8_t* p = a.streams + (uint64_t)f * a.stream_stride;
+  const uint8_t* p = dec_stream_ptr(a, f);
   const bool al16 = (reinterpret_cast<uintptr_t>(p) & 15u) == 0;
   const uint64_t base = (uint64_t)f * a.max_chunks;
   const uint32_t N = a.W * a.H;
@@ -1186,7 +1196,7 @@ __global__ __launch_bounds__(DEC_PARSE_THREADS) void dec_strict_refill(DecArgs a
   const uint32_t j0 = j > 0 ? j - 1u : 0u;
   uint32_t* wring = ring + wave * 64u * RING_STRIDE;
   const uint32_t* my = wring + (threadIdx.x & 63u) * RING_STRIDE;
-  const uint8_t* p = a.streams + (uint64_t)f * a.stream_stride;
+  const uint8_t* p = dec_stream_ptr(a, f);
   const bool al16 = (reinterpret_cast<uintptr_t>(p) & 15u) == 0;
   const uint64_t base = (uint64_t)f * a.max_chunks;
   const unsigned long long N = (unsigned long long)a.W * a.H;
@@ -1425,7 +1435,7 @@ __global__ __launch_bounds__(DEC_PARSE_THREADS) PARSE_ATTR void dec_emit(DecArgs
   const uint32_t j = item / subs, sub = item - j * subs;
   uint32_t* wring = ring + wave * 64u * RING_STRIDE;
   const uint32_t* my = wring + (threadIdx.x & 63u) * RING_STRIDE;
-  const uint8_t* p = a.streams + (uint64_t)f * a.stream_stride;
+  const uint8_t* p = dec_stream_ptr(a, f);
   const bool al16 = (reinterpret_cast<uintptr_t>(p) & 15u) == 0;
   const uint64_t base = (uint64_t)f * a.max_chunks;
   const uint32_t N = a.W * a.H;

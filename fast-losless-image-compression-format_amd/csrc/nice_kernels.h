@@ -231,7 +231,16 @@ struct DecArgs {
   // dec_scan: per-frame flags of the last sync iteration (an entry still moved:
   // the frame fails with NICE_E_HIP), or null
   const uint32_t* unsettled;
+  // packed batch (include/nice.h, "Packed stream batches"): stream f starts at
+  // streams + stream_off[f] (stream_stride unused), and the buffer holds
+  // packed_bytes bytes; null: the strided layout
+  const unsigned long long* stream_off;
+  uint64_t packed_bytes;
 };
+// Frame f's stream.  With stream_off null: streams + f * stream_stride.
+__device__ __forceinline__ const uint8_t* dec_stream_ptr(const DecArgs& a, uint32_t f) {
+  return a.streams + (a.stream_off ? (uint64_t)a.stream_off[f] : (uint64_t)f * a.stream_stride);
+}
 constexpr uint32_t SPLIT_ABORT_ERR = 1u, SPLIT_REDO = 2u;
 // first-pass event of a run digit: EV_RUN | pixels (saturated); a coded
 // pixel's record before its tag: EV_L2 (LUMA2: needs the row above) and EV_BAD

@@ -157,7 +157,7 @@ extern "C" int nice_pipe_create(int device, uint32_t w, uint32_t h, uint8_t chan
   p->slots.resize(depth);
   for (Slot& s : p->slots) {
     int rc = nice_ctx_create(device, &s.ctx);
-    if (rc == NICE_OK) rc = nice_ctx_reserve(s.ctx, batch, w, h);
+    if (rc == NICE_OK) rc = nice::ctx_reserve_impl(s.ctx, batch, w, h, false);   // (the slot has its own stream buffer)
     bool ok = rc == NICE_OK;
     ok = ok && hipStreamCreateWithFlags(&s.st, hipStreamNonBlocking) == hipSuccess;
     ok = ok && hipEventCreateWithFlags(&s.done, hipEventDisableTiming) == hipSuccess;

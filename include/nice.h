@@ -81,7 +81,8 @@ int nice_decode(const uint8_t* s, size_t len, uint8_t* px_out, size_t cap, uint3
 /* ---- context API: device buffers, HIP streams (passed as void*), batches ---- */
 int nice_ctx_create(int device, nice_ctx** out);
 void nice_ctx_destroy(nice_ctx* ctx);
-/* Pre-size scratch so later batch calls allocate nothing (graph-capturable). */
+/* Pre-size scratch so later batch calls allocate nothing (graph-capturable);
+ * this includes nice_encode_batch_packed_dev's n_frames stream slots. */
 int nice_ctx_reserve(nice_ctx* ctx, uint32_t n_frames, uint32_t w, uint32_t h);
 
 /* Encode n_frames same-shape frames resident in device memory.
@@ -112,6 +113,67 @@ int nice_decode_batch_dev_hl(nice_ctx* ctx, void* stream, const uint8_t* d_strea
                              const uint64_t* h_stream_len, uint32_t n_frames, uint32_t w, uint32_t h,
                              uint8_t out_channels, uint8_t* d_px, uint64_t px_stride, uint32_t flags,
                              int32_t* d_status);
+
+/* ---- packed stream batches ----
+ * A strided batch spends nice_encode_bound(w, h) bytes per frame, the size of
+ * the raw frame.  The packed form keeps the same streams, bit for bit, back to
+ * back in one device buffer with an offset table.  Layout, for n streams of
+ * len[f] bytes (align16(x) = x rounded up to a multiple of 16):
+ *   off[0] = 0
+ *   off[f + 1] = off[f] + align16(len[f])
+ *   off[n] = the packed size
+ *   stream f occupies packed[off[f] .. off[f] + len[f])
+ *   the pad bytes up to off[f + 1] are zero (a packed buffer is a pure function
+ *   of its streams); a zero-length stream occupies nothing
+ * d_packed is 16-byte aligned, so every stream is.  The offset table is n + 1
+ * u64 in device memory.
+ *
+ * What the decoder reads: of a stream at offset o with length len, only bytes
+ * [o, o + len) -- its 16-byte refills are issued only for quads that end at or
+ * before len rounded down to 4, and the last partial quad is read byte by byte
+ * below len (positions past len repeat the last byte, as in the strided form).
+ * No pad byte and no byte of a neighbouring stream is ever loaded, so no tail
+ * padding is needed: packed_bytes = off[n] exactly, and nice_packed_bound()
+ * has no slack beyond the per-stream alignment.
+ *
+ * All three calls are asynchronous on `stream`. */
+/* Worst-case packed size of n_frames w x h streams. */
+uint64_t nice_packed_bound(uint32_t n_frames, uint32_t w, uint32_t h);
+/* Compacts a strided batch (stream f at d_streams + f*stream_stride, both
+ * multiples of 4; d_stream_len[f] <= stream_stride bytes) into d_packed
+ * (16-byte aligned, packed_cap bytes).  Never synchronises: the lengths are
+ * only read on the device.  d_off (n_frames + 1) is always written in full, so
+ * d_off[n_frames] is the size the call needed.  *d_status:
+ *   NICE_OK          every stream copied, pads zeroed
+ *   NICE_E_CAPACITY  d_off[n_frames] > packed_cap: no byte at or past packed_cap
+ *                    is written; streams that end at or before packed_cap
+ *                    rounded down to 16 are complete
+ *   NICE_E_ARG       some d_stream_len[f] > stream_stride: that stream counts
+ *                    as empty in d_off and is not copied
+ * Source bytes at or beyond d_stream_len[f] rounded up to 4 are not read. */
+int nice_pack_streams_dev(nice_ctx* ctx, void* stream, const uint8_t* d_streams, uint64_t stream_stride,
+                          const uint64_t* d_stream_len, uint32_t n_frames, uint8_t* d_packed,
+                          uint64_t packed_cap, uint64_t* d_off /* n_frames + 1 */, int32_t* d_status /* 1 */);
+/* nice_encode_batch_dev into a strided scratch owned and reused by the context
+ * (n_frames slots of nice_encode_bound(w, h); nice_ctx_reserve pre-sizes it),
+ * then nice_pack_streams_dev into d_packed.  d_out_len[f] = stream f's length;
+ * d_off, *d_status as above. */
+int nice_encode_batch_packed_dev(nice_ctx* ctx, void* stream, const uint8_t* d_px, uint64_t frame_stride,
+                                 uint32_t n_frames, uint32_t w, uint32_t h, uint8_t channels,
+                                 uint8_t channels_out, uint8_t* d_packed, uint64_t packed_cap, uint64_t* d_off,
+                                 uint64_t* d_out_len, int32_t* d_status);
+/* nice_decode_batch_dev reading stream f in place at d_packed + d_off[f]
+ * (d_packed 16-byte aligned).  d_off has n_frames entries in any order, repeats
+ * allowed: gather d_off / d_stream_len to decode a subset of a batch.  A frame
+ * whose d_off[f] is not a multiple of 16, or with d_off[f] + d_stream_len[f] >
+ * packed_bytes, gets NICE_E_ARG in d_status[f] before any byte of it is read;
+ * the other frames decode.  h_stream_len: the lengths on the host (the call
+ * then only enqueues work), or NULL (they are read back first, as by
+ * nice_decode_batch_dev). */
+int nice_decode_packed_dev(nice_ctx* ctx, void* stream, const uint8_t* d_packed, uint64_t packed_bytes,
+                           const uint64_t* d_off, const uint64_t* d_stream_len, const uint64_t* h_stream_len,
+                           uint32_t n_frames, uint32_t w, uint32_t h, uint8_t out_channels, uint8_t* d_px,
+                           uint64_t px_stride, uint32_t flags, int32_t* d_status);
 
 /* ---- one image sharded over ranks (config 4) ----
  * The image's raster is cut into bands of whole encoder tiles (1024 pixels in

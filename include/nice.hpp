@@ -78,5 +78,50 @@ class Context {
   nice_ctx* ctx_ = nullptr;
 };
 
+// ---- packed stream batches (nice.h, "packed stream batches") ----
+// A packed batch in device memory: the streams back to back at data + off[f]
+// (16-byte aligned), off[n] = its size.  The pointers are caller-owned device
+// memory; `stream` is a hipStream_t.  All calls are asynchronous.
+struct PackedBatch {
+  uint8_t* data = nullptr;      // 16-byte aligned, `cap` bytes
+  uint64_t cap = 0;
+  uint64_t* off = nullptr;      // n + 1
+  uint64_t* len = nullptr;      // n
+  int32_t* status = nullptr;    // 1: NICE_OK / NICE_E_CAPACITY / NICE_E_ARG, written on the device
+  uint32_t n = 0;
+};
+
+inline uint64_t packed_bound(uint32_t n_frames, const Image& img) {
+  return nice_packed_bound(n_frames, img.width, img.height);
+}
+
+// Compacts strided streams (lengths in b.len) into b.
+inline void pack_streams(const Context& ctx, void* stream, const uint8_t* d_streams, uint64_t stream_stride,
+                         const PackedBatch& b) {
+  check(nice_pack_streams_dev(ctx.get(), stream, d_streams, stream_stride, b.len, b.n, b.data, b.cap, b.off,
+                              b.status),
+        "nice_pack_streams_dev");
+}
+
+// Encodes b.n frames of `img` at d_px + f * frame_stride straight into b.
+inline void encode_batch_packed(const Context& ctx, void* stream, const uint8_t* d_px, uint64_t frame_stride,
+                                const Image& img, uint8_t channels_out, const PackedBatch& b) {
+  check(nice_encode_batch_packed_dev(ctx.get(), stream, d_px, frame_stride, b.n, img.width, img.height,
+                                     img.channels, channels_out, b.data, b.cap, b.off, b.len, b.status),
+        "nice_encode_batch_packed_dev");
+}
+
+// Decodes n frames in place from a packed buffer of packed_bytes bytes: frame i
+// is the stream at d_off[i] with d_len[i] bytes (any order, repeats allowed).
+// h_len: the same lengths on the host, or null.  d_status: n per-frame codes.
+inline void decode_packed(const Context& ctx, void* stream, const uint8_t* d_packed, uint64_t packed_bytes,
+                          const uint64_t* d_off, const uint64_t* d_len, const uint64_t* h_len, uint32_t n,
+                          const Image& img, uint8_t out_channels, uint8_t* d_px, uint64_t px_stride,
+                          int32_t* d_status, uint32_t flags = NICE_DEC_ALPHA_FILL_FF) {
+  check(nice_decode_packed_dev(ctx.get(), stream, d_packed, packed_bytes, d_off, d_len, h_len, n, img.width,
+                               img.height, out_channels, d_px, px_stride, flags, d_status),
+        "nice_decode_packed_dev");
+}
+
 }  // namespace nice
 #endif  // NICE_HPP
