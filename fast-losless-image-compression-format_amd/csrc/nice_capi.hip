@@ -16,6 +16,7 @@
 #include "nice_format.h"
 #include "nice_bits.hpp"
 #include "nice_kernels.h"
+#include "nice_dec_plan.hpp"
 #include "nice_rec.hpp"
 #include "nice_internal.h"
 
@@ -178,7 +179,9 @@ struct nice_ctx {
   // the last split decode's per-frame abort flags (test hook nice_test_split_redos)
   const uint32_t* split_abort = nullptr;
   uint32_t split_frames = 0;
-  int last_classify = -1;   // ClsKind of the last encode / band classify (test hook nice_test_last_classify)
+  // DecRoute of the last decode's row kernel and of its redo launch (test hook nice_test_last_dec_route)
+  uint32_t last_dec_route = 0, last_dec_fallback = 0;
+  int last_classify = -1;  // ClsKind of the last encode / band classify (test hook nice_test_last_classify)
   // test hooks (nice_test_set_hooks; 0 = off): the last strip of every split
   // decode returns at entry; enc_pack's LDS group buffer in bits per pixel
   uint32_t test_split_absent = 0, test_pack_cap_bpp = 0;
@@ -318,7 +321,7 @@ EncArgs enc_args(const EncLayout& L, uint8_t* base, uint32_t n_frames, uint32_t 
 // enc_classify_strip: rows per block (about three blocks per CU over all
 // frames and strips, >= 16 rows so the 3-row prefill stays small) and the grid
 static uint32_t strip_rows(const nice_ctx* ctx, uint32_t n_frames, uint32_t w, uint32_t rows_total, uint32_t* blocks) {
-  const uint64_t strips = (w + STRIP_W_HOST - 1) / STRIP_W_HOST;
+  const uint64_t strips = (w + STRIP_W - 1) / STRIP_W;
   const uint64_t want = 3ull * (uint64_t)ctx->cus;
   uint64_t r = (rows_total * strips * n_frames + want - 1) / want;
   if (r < 16) r = 16;
@@ -368,23 +371,23 @@ static void launch_classify(nice_ctx* ctx, ClsKind k, EncArgs& a, uint64_t work,
     case CLS_K_STRIP: {
       uint32_t sblocks;
       a.tiles_per_block = strip_rows(ctx, a.n_frames, a.W, rows_total, &sblocks);
-      hipLaunchKernelGGL(a.cmask ? enc_classify_strip_m : enc_classify_strip, dim3(sblocks), dim3(CLS_THREADS_HOST), 0, st, a);
+      hipLaunchKernelGGL(a.cmask ? enc_classify_strip_m : enc_classify_strip, dim3(sblocks), dim3(CLS_THREADS), 0, st, a);
       break;
     }
     case CLS_K_RING:   // (frames: the _m forms, as for the pair kernel below)
       if (rgb) hipLaunchKernelGGL(a.cmask ? enc_classify_ring3_m : enc_classify_ring3, dim3((uint32_t)blocks),
-                                  dim3(CLS_THREADS_HOST), 0, st, a);
+                                  dim3(CLS_THREADS), 0, st, a);
       else hipLaunchKernelGGL(a.cmask ? enc_classify_ring_m : enc_classify_ring, dim3((uint32_t)blocks),
-                              dim3(CLS_THREADS_HOST), 0, st, a);
+                              dim3(CLS_THREADS), 0, st, a);
       break;
     case CLS_K_PAIR:
       // frames: coded flags out, run digits by enc_rundigits (below); bands:
       // run digits in the kernel
-      if (a.cmask) hipLaunchKernelGGL(enc_classify_pair_m, dim3((uint32_t)blocks), dim3(CLS_THREADS_HOST), 0, st, a);
-      else hipLaunchKernelGGL(enc_classify_pair, dim3((uint32_t)blocks), dim3(CLS_THREADS_HOST), 0, st, a);
+      if (a.cmask) hipLaunchKernelGGL(enc_classify_pair_m, dim3((uint32_t)blocks), dim3(CLS_THREADS), 0, st, a);
+      else hipLaunchKernelGGL(enc_classify_pair, dim3((uint32_t)blocks), dim3(CLS_THREADS), 0, st, a);
       break;
     case CLS_K_SLIDE: {   // frames only (coded flags out in ballot order)
-      const dim3 g((uint32_t)blocks), b(CLS_THREADS_HOST);
+      const dim3 g((uint32_t)blocks), b(CLS_THREADS);
       switch (a.W & 3u) {
         case 0: hipLaunchKernelGGL(enc_classify_slide0, g, b, 0, st, a); break;
         case 1: hipLaunchKernelGGL(enc_classify_slide1, g, b, 0, st, a); break;
@@ -395,9 +398,9 @@ static void launch_classify(nice_ctx* ctx, ClsKind k, EncArgs& a, uint64_t work,
     }
     case CLS_K_RING2:
       if (rgb) hipLaunchKernelGGL(a.cmask ? enc_classify_ring2_3_m : enc_classify_ring2_3, dim3((uint32_t)blocks),
-                                  dim3(CLS_THREADS_HOST), 0, st, a);
+                                  dim3(CLS_THREADS), 0, st, a);
       else hipLaunchKernelGGL(a.cmask ? enc_classify_ring2_m : enc_classify_ring2, dim3((uint32_t)blocks),
-                              dim3(CLS_THREADS_HOST), 0, st, a);
+                              dim3(CLS_THREADS), 0, st, a);
       break;
     case CLS_K_TINY:
       hipLaunchKernelGGL(enc_classify_tiny, dim3((uint32_t)blocks), dim3(256), 0, st, a);
@@ -406,8 +409,8 @@ static void launch_classify(nice_ctx* ctx, ClsKind k, EncArgs& a, uint64_t work,
       const uint64_t tb = 2ull * ctx->cus, tper = (work + tb - 1) / tb;
       a.tiles_per_block = (uint32_t)tper;
       const dim3 g((uint32_t)((work + tper - 1) / tper));
-      if (rgb) hipLaunchKernelGGL(a.cmask ? enc_classify_twin3_m : enc_classify_twin3, g, dim3(CLS_THREADS_HOST), 0, st, a);
-      else hipLaunchKernelGGL(a.cmask ? enc_classify_twin_m : enc_classify_twin, g, dim3(CLS_THREADS_HOST), 0, st, a);
+      if (rgb) hipLaunchKernelGGL(a.cmask ? enc_classify_twin3_m : enc_classify_twin3, g, dim3(CLS_THREADS), 0, st, a);
+      else hipLaunchKernelGGL(a.cmask ? enc_classify_twin_m : enc_classify_twin, g, dim3(CLS_THREADS), 0, st, a);
       break;
     }
     default:
@@ -530,8 +533,8 @@ constexpr uint32_t kSettledFlag = kSyncQueuedMax, kFinalFlag = kSyncQueuedMax + 
 #endif
 constexpr uint32_t kSyncQueued = NICE_SYNC_QUEUED;
 static_assert(kSyncQueued >= 1 && kSyncQueued <= kSyncQueuedMax, "queued sync iterations");
-DecLayout dec_layout(uint32_t n_frames, uint32_t max_chunks, uint32_t n_ck, uint64_t npx, size_t rowbuf,
-                     uint32_t ev_cap, uint32_t subs, size_t hand = 0, bool abort_flags = false) {
+DecLayout dec_layout(uint32_t n_frames, uint64_t npx, const DecPlan& p) {
+  const uint32_t max_chunks = p.max_chunks, n_ck = p.n_ck, ev_cap = p.ev_cap, subs = p.subs;
   DecLayout L{};
   size_t o = 0;
   auto take = [&](size_t bytes) { size_t r = o; o = align_up(o + bytes, 256); return r; };
@@ -545,7 +548,7 @@ DecLayout dec_layout(uint32_t n_frames, uint32_t max_chunks, uint32_t n_ck, uint
   L.o_recs = take((size_t)n_frames * ((npx + 3) & ~3ull) * 4);
   L.o_changed = take(4 * kSyncFlags);
   L.o_fchanged = take((size_t)n_frames * 4);
-  L.o_rowbuf = take(rowbuf);
+  L.o_rowbuf = take(p.rowbuf);
   // first-pass pixel events (ev_cap per slice, 0: not kept)
   L.o_ev = take((size_t)n_frames * ((max_chunks + 63) & ~63u) * ev_cap * 4);
   L.o_evck = take(ev_cap ? (size_t)n_frames * n_ck * max_chunks * 4 : 0);
@@ -553,32 +556,114 @@ DecLayout dec_layout(uint32_t n_frames, uint32_t max_chunks, uint32_t n_ck, uint
   L.o_agree = take(ev_cap ? (size_t)n_frames * max_chunks * 4 : 0);
   L.o_items = take(ev_cap ? (size_t)n_frames * max_chunks * subs * 4 : 0);
   L.o_icount = take(ev_cap ? (size_t)n_frames * 4 : 0);
-  L.o_hand = take(hand);
-  L.o_abort = take(hand || abort_flags ? (size_t)n_frames * 4 : 0);
+  L.o_hand = take(p.hand);
+  L.o_abort = take(p.abort_flags ? (size_t)n_frames * 4 : 0);
   L.total = o;
   return L;
 }
-struct RecGeom {
-  uint32_t seg, nseg, R;
-  size_t lds;
-  bool in_lds;
-};
-RecGeom rec_geom(uint32_t w) {
-  RecGeom g;
-  uint32_t s = (w + DEC_MAX_SEGS - 1) / DEC_MAX_SEGS;
-  if (s < 6) s = 6;
-  g.seg = s;
-  g.nseg = w ? (w + s - 1) / s : 1;
-  // the last segment (which runs to W) must be >= 6 pixels: its last three
-  // columns read pixels 0..2 of the same row, written by lane 0 at steps 0..2
-  if (g.nseg > 1 && w - (g.nseg - 1) * s < 6) g.nseg -= 1;
-  g.R = w >= 3 ? 4 : 8;
-  const size_t kw = (w + 31) / 32;
-  const size_t head = 512 + align_up(kw, 4) * 4 + align_up(w, 4) * 4;   // RecLds <= 512 B, records
-  const size_t ring = (size_t)g.R * w * 4;
-  g.in_lds = head + ring <= 150 * 1024;
-  g.lds = g.in_lds ? head + ring : head;
-  return g;
+
+// The plan's and the scratch layout's half of the kernel arguments.
+void dec_args_scratch(DecArgs& a, const DecLayout& L, uint8_t* base, const DecPlan& P, uint64_t N) {
+  a.tables = base + L.o_tables;
+  a.data_start = (unsigned long long*)(base + L.o_dstart);
+  const uint32_t max_chunks = P.max_chunks, cb = P.slice_bits;
+  a.max_chunks = max_chunks;
+  a.chunk_bits = cb;
+  a.n_ck = P.n_ck;
+  a.ck_bits = P.ck_bits;
+  a.emit_blocks = (uint32_t)(((uint64_t)max_chunks * (cb / DEC_EMIT_BITS) + DEC_PARSE_THREADS - 1) / DEC_PARSE_THREADS);
+  a.chunk_blocks = (max_chunks + DEC_PARSE_THREADS - 1) / DEC_PARSE_THREADS;
+  a.chunk_px = (unsigned long long*)(base + L.o_cpx);
+  a.chunk_start = (unsigned long long*)(base + L.o_cstart);
+  a.entry = (unsigned long long*)(base + L.o_entry);
+  a.last = (unsigned long long*)(base + L.o_last);
+  a.ck = (unsigned long long*)(base + L.o_ck);
+  a.recs = (uint32_t*)(base + L.o_recs);
+  a.rec_stride = (N + 3) & ~3ull;
+  a.seg = P.g.seg;
+  a.nseg = P.g.nseg;
+  a.rows_in_lds = P.g.in_lds ? 1u : 0u;
+  a.parse_slow = opt_on(NICE_OPT_DEC_SLOW_PARSE) ? 1u : 0u;   // tests / A/B: the general parse only
+  a.rowbuf = (uint32_t*)(base + L.o_rowbuf);
+  if (P.ev_cap) {
+    a.ev = (uint32_t*)(base + L.o_ev);
+    a.ev_cap = P.ev_cap;
+    a.ev_ck = (uint32_t*)(base + L.o_evck);
+    a.ev_n = (uint32_t*)(base + L.o_evn);
+    a.agree = (uint32_t*)(base + L.o_agree);
+    a.head_items = (uint32_t*)(base + L.o_items);
+    a.head_count = (uint32_t*)(base + L.o_icount);
+  }
+}
+
+// One row-kernel launch of a plan (DecPlan::rows, or ::fallback with a.redo
+// set): one block per frame; the split kernel one per strip, frames in chunks.
+int launch_rows(const DecPlan& p, const DecLaunch& l, DecArgs& a, hipStream_t st) {
+  void (*k)(DecArgs) = nullptr;
+  switch (l.route) {
+    case DEC_R_RECONSTRUCT: k = dec_reconstruct; break;
+    case DEC_R_ROWS: k = dec_rows; break;
+    case DEC_R_ROWS8: k = dec_rows8; break;
+    case DEC_R_ROWS_WIDE: k = dec_rows_wide; break;
+    case DEC_R_FLOW: k = dec_rows_flow; break;
+    case DEC_R_SPLIT: k = dec_rows_split; break;
+    default: return NICE_E_ARG;
+  }
+  if (l.lds > LDS_OPT_IN)
+    NICE_HIP(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l.lds));
+  if (l.route != DEC_R_SPLIT) {
+    hipLaunchKernelGGL(k, dim3(a.n_frames), dim3(l.threads), l.lds, st, a);
+    return NICE_OK;
+  }
+  for (uint32_t f0 = 0; f0 < a.n_frames; f0 += p.split_frames) {
+    a.split_f0 = f0;
+    hipLaunchKernelGGL(k, dim3(std::min(p.split_frames, a.n_frames - f0) * p.strips), dim3(l.threads), l.lds, st, a);
+  }
+  a.split_f0 = 0;
+  return NICE_OK;
+}
+
+// NICE_OPT_DEC_STATS: the kernels' counters (DecArgs::stats) and the sync
+// flags to stderr, once the call's work on `st` is done
+void dec_print_stats(hipStream_t st, const unsigned long long* dstats, const uint32_t* changed, uint32_t it_count,
+                     uint32_t queued, const DecArgs& a) {
+  unsigned long long h[128] = {0};
+  (void)hipMemcpyAsync(h, dstats, 1024, hipMemcpyDeviceToHost, st);
+  uint32_t chg[kSyncFlags] = {0};
+  (void)hipMemcpyAsync(chg, changed, 4 * kSyncFlags, hipMemcpyDeviceToHost, st);
+  (void)hipStreamSynchronize(st);
+  fprintf(stderr,
+          "[nice dec stats] rows=%llu unconverged_segs=%llu tail_unknown_segs=%llu "
+          "recomputed_px=%llu fixup_rounds=%llu sync_iters=%u seg=%u nseg=%u "
+          "clk[load=%llu spec=%llu fix=%llu emit=%llu]\n",
+          h[0], h[1], h[2], h[3], h[4], it_count, a.seg, a.nseg, h[5], h[6], h[7], h[8]);
+  fprintf(stderr, "[nice dec stats] sync iterations that changed an entry:");
+  for (uint32_t i = 0; i < kSyncFlags; ++i) fprintf(stderr, " %u", chg[i]);
+  fprintf(stderr, " (queued %u, then settled, final)\n", queued);
+  for (int w = 0; w < 4; ++w) {   // dec_rows_flow (-DNICE_FLOW_STATS builds): cycles per row by phase
+    const unsigned long long* q = h + 64 + 8 * w;
+    if (q[7])
+      fprintf(stderr, "[nice flow stats] wave %d rows=%llu cyc/row: emit+decode=%.0f wait=%.0f ring=%.0f spec=%.0f "
+              "fix=%.0f publish=%.0f rounds/row=%.2f\n", w, q[7], (double)q[0] / q[7], (double)q[1] / q[7],
+              (double)q[2] / q[7], (double)q[3] / q[7], (double)q[4] / q[7], (double)q[5] / q[7],
+              (double)q[6] / q[7]);
+  }
+  fprintf(stderr, "[nice dec stats] unknown segment tails: copies of an unknown %llu, narrowed %llu\n", h[24], h[25]);
+  fprintf(stderr, "[nice dec stats] re-parse met previous parse at checkpoint:");
+  for (int k = 0; k < 17; ++k) fprintf(stderr, " %d:%llu", k, h[32 + k]);
+  fprintf(stderr, "\n");
+  fprintf(stderr, "[nice dec stats] slice=%u emit waves=%llu wave_iters=%llu active_lane_iters=%llu fills=%llu\n",
+          a.chunk_bits, h[20], h[16], h[17], h[18]);
+  fprintf(stderr, "[nice dec stats] slices by first-pass meeting checkpoint: 0:%llu 1:%llu 2-4:%llu 5-16:%llu "
+          "17-64:%llu 65+:%llu none:%llu overflow:%llu (ev_cap %u)\n",
+          h[50], h[51], h[52], h[53], h[54], h[55], h[56], h[57], a.ev_cap);
+  fprintf(stderr, "[nice dec stats] fix-up rounds per row: 0:%llu 1:%llu 2:%llu 3:%llu 4:%llu 5:%llu 6+:%llu\n",
+          h[9], h[10], h[11], h[12], h[13], h[14], h[15]);
+  if (h[61]) fprintf(stderr, "[nice dec stats] sync first pass: waves=%llu cycles/wave=%.0f refill cycles/wave=%.0f "
+          "refills/wave=%.1f iterations/wave=%.1f active lane share=%.3f\n",
+          h[61], h[61] ? (double)h[56] / h[61] : 0.0, h[61] ? (double)h[57] / h[61] : 0.0,
+          h[61] ? (double)h[58] / h[61] : 0.0, h[61] ? (double)h[59] / h[61] : 0.0,
+          h[59] ? (double)h[60] / (64.0 * h[59]) : 0.0);
 }
 }  // namespace
 
@@ -736,127 +821,26 @@ int nice::decode_batch_impl(nice_ctx* ctx, void* stream, const uint8_t* d_stream
     max_len = l > max_len ? l : max_len;
   }
   const uint64_t D = FILE_HEADER_BYTES * 8 + TABLE_HEADER_BITS;
-  // slice size: long slices make the Jacobi re-parses (which run until the
-  // slowest lane of a wave re-synchronises, ~1000 bits) cheap relative to the
-  // first pass, short ones keep a small batch filling the GPU: aim for about
-  // 256 CUs x 8 waves x 64 lanes x 2 slices, as a power of two in [1K, 16K]
-  // (at least 2048 bits from ~48 Mbit of streams up: a 1024-bit slice holds
-  // no checkpoint, so every Jacobi re-parse and dec_emit walk whole slices --
-  // one 4K frame 9.75 -> 9.61 ms, 4 x 4K 10.03 -> 9.85, 8 x 1080p 5.17 ->
-  // 5.11; one 1080p frame, whose 2048-bit slices leave the GPU emptier, 4.92
-  // -> 4.96: kept at 1024, profiles/r06v_ab_slice_min.log)
   uint64_t total_bits = 0;
   for (uint64_t l : lens) total_bits += l * 8 > D ? l * 8 - D : 0;
-  uint32_t cb = total_bits >= (48ull << 20) ? 2 * DEC_MIN_CHUNK_BITS : DEC_MIN_CHUNK_BITS;
-  while (cb < DEC_MAX_CHUNK_BITS && total_bits / (2ull * cb) > 256ull * 8 * 64 * 2) cb *= 2;
-  if (opt_set(NICE_OPT_DEC_SLICE_BITS)) {   // tests: force a slice size
-    const uint32_t v = (uint32_t)opt_val(NICE_OPT_DEC_SLICE_BITS);
-    if (v >= DEC_MIN_CHUNK_BITS && v <= DEC_MAX_CHUNK_BITS && (v & (v - 1)) == 0) cb = v;
-  }
-  const uint32_t max_chunks = max_len * 8 > D ? (uint32_t)((max_len * 8 - D + cb - 1) / cb) : 1;
-  // checkpoints every 512 bits in slices up to 4K bits (small batches: the
-  // re-parses and dec_emit's heads stop at the first meeting point, half as far
-  // in: one 4K frame 9.59 -> 9.52 ms, 64 x 1080p 6.13 -> 6.07), every 1024 from
-  // 8K bits up (512 x 4K: sync 12.0 -> 12.6 ms at 512, more checkpoint stores
-  // than the shorter heads save; profiles/r06x_ab_ck_bits.log)
-  const uint32_t ck_bits = cb <= 4096u ? DEC_CK_BITS_SMALL : DEC_CK_BITS;
-  const uint32_t n_ck = cb / ck_bits - 1;
-  const RecGeom g = rec_geom(w);
-  // multi-wave row kernel for 64 <= W <= 16384 (one lane per 16-pixel segment),
-  // single-wave kernel otherwise
-  const uint32_t rows_thr = ((w + 15) / 16 + 63) / 64 * 64;
-  const bool single_wave = opt_on(NICE_OPT_DEC_SINGLE_WAVE);
-  const bool use_rows = w >= 64 && rows_thr <= 1024 && !single_wave;
-  const size_t rows_lds = ((size_t)rows_thr * 7 + 8 + (size_t)4 * (w + (w >> 4) + 24)) * 4;   // rows_ring_stride
-  const bool rows_in_lds = rows_thr <= 512 && rows_lds + 1024 <= 160 * 1024;   // + static LDS
-  // 8-pixel segments (twice the lanes per frame) only on request
-  // (NICE_DEC_SEG=8): they were the default where 16-pixel segments leave SIMDs
-  // of a frame's CU idle (W <= 2048, frames not sharing CUs: 64 x 1080p 7.83 ->
-  // 6.32 ms in round 2), but the round-3/4 row kernel with 16-pixel segments is
-  // as fast or faster at every width measured (round 4, profiles/r04v, r04y:
-  // 64 x 1080p reconstruct 6.58 vs 6.88 ms, W = 1280 / 1024 / 640: 6.68 / 5.77
-  // / 6.22 vs 6.91 / 6.00 / 6.30 ms)
-  const uint32_t rows8_thr = ((w + 7) / 8 + 63) / 64 * 64;
-  const size_t rows8_lds = ((size_t)rows8_thr * 7 + 8 + (size_t)4 * (w + (w >> 4) + 24)) * 4;
-  bool rows8 = false;
-  if (opt_set(NICE_OPT_DEC_SEG)) rows8 = opt_val(NICE_OPT_DEC_SEG) == 8 && use_rows && rows_in_lds &&
-                                                       rows8_thr <= 512 && rows8_lds <= 160 * 1024;
-  // wide frames, few of them: strips of <= 256 segments on separate CUs
-  // (dec_rows_split; its blocks wait on each other, so they should all be
-  // resident: at most one per CU for half the CUs, frames in chunks of that
-  // many strips).  When they are not (other kernels hold the CUs), a strip's
-  // wait times out and the frame goes to the fallback launch (dec_rows_wide,
-  // or dec_reconstruct above 16384 columns) -- slower, never wrong.
-  // NICE_DEC_SPLIT=k forces k strips (tests), =0 disables
-  const uint32_t nseg16 = (w + 15) / 16;
-  const uint32_t split_cap = (uint32_t)std::max(ctx->cus / 2, 1);
-  uint32_t strips = (nseg16 + SPLIT_THREADS_HOST - 1) / SPLIT_THREADS_HOST;
-  if (opt_set(NICE_OPT_DEC_SPLIT)) strips = (uint32_t)opt_val(NICE_OPT_DEC_SPLIT);
-  // <= 16384 columns: only when the whole batch fits at once (else one block
-  // per frame is the better use of the CUs); wider: always, in frame chunks
-  bool split = !single_wave && w >= 64 && strips >= 2 && strips <= split_cap &&
-               (!use_rows || (uint64_t)n_frames * strips <= split_cap);
-  // rows of up to 8192 pixels (8 waves) take the dataflow kernel on one CU
-  // rather than strips on several (round 6: the strips' cross-CU hand-offs
-  // cost more than the second CU gains); NICE_DEC_SPLIT forces the strips
-  const uint32_t flow_wpr = ((w + 15) / 16 + 63) / 64;
-  if (split && !opt_set(NICE_OPT_DEC_SPLIT) && use_rows && w <= FLOW_MAX_W_HOST && !opt_on(NICE_OPT_DEC_SEG) &&
-      !(opt_set(NICE_OPT_DEC_FLOW) && opt_val(NICE_OPT_DEC_FLOW) <= 0))
-    split = false;
-  if (split) {
-    const uint32_t sps = (nseg16 + strips - 1) / strips;
-    // every strip >= 2 segments (>= 3 pixels: its first and last three) and <= 256 lanes
-    if (sps > SPLIT_THREADS_HOST || nseg16 <= (strips - 1) * sps + 1) split = false;
-  }
-  const uint32_t split_frames = split ? std::min(n_frames, split_cap / strips) : 0;   // frames per launch
-  // W <= 4096: the dataflow row kernel (no block barriers; dec_rows_flow).
-  // At most one frame per CU: two row groups in flight and an 8-row ring (one
-  // block per CU); larger batches: one group and a 4-row ring, so two frames
-  // share each CU.  NICE_DEC_FLOW=0 takes dec_rows, =k forces k groups (A/B).
-  uint32_t flow_k = 2, flow_ring = 8;
-  bool flow = !split && use_rows && !rows8 && w <= FLOW_MAX_W_HOST;
-  if (n_frames > (uint32_t)std::max(ctx->cus, 1)) { flow_k = 1; flow_ring = 4; }
-  if (opt_set(NICE_OPT_DEC_FLOW)) {
-    const int v = (int)opt_val(NICE_OPT_DEC_FLOW);
-    if (v <= 0) flow = false;
-    else flow_k = (uint32_t)v;
-  }
-  if (flow_k * flow_wpr > FLOW_THREADS_HOST / 64) flow_k = FLOW_THREADS_HOST / 64 / flow_wpr;
-  if (flow_k > 4 || flow_k < 1) flow = false;   // (stamps of 8 rows)
-  if (flow_k > 1) flow_ring = 8;
-  size_t flow_lds = FLOW_CTL_BYTES_HOST + ((size_t)flow_ring * (w + (w >> 4) + 24) + 4) * 4;   // rows_ring_stride
-  if (flow_lds > 160 * 1024 && flow_k == 1 && flow_ring == 8) {   // wide rows: a 4-row ring (one row group)
-    flow_ring = 4;
-    flow_lds = FLOW_CTL_BYTES_HOST + ((size_t)flow_ring * (w + (w >> 4) + 24) + 4) * 4;
-  }
-  if (flow_lds > 160 * 1024) flow = false;
-  const size_t hand = split ? (size_t)n_frames * h * strips * SPLIT_GRAN_HOST * 8 : 0;
-  // per-frame redo flags: the split kernel's, and the dataflow kernel's (a
-  // wait that timed out sends the frame to the barrier kernel)
-  const bool want_abort = split || flow;
-  // the row ring in global memory: dec_rows_wide (also the split path's
-  // fallback) or dec_reconstruct without room in LDS
-  const size_t ring_rows = use_rows ? (size_t)n_frames * 4 * (w + (w >> 4) + 24) * 4
-                                    : (g.in_lds ? 0 : (size_t)n_frames * g.R * w * 4);
-  const size_t rowbuf = split ? ring_rows : (use_rows && rows_in_lds) ? 0 : ring_rows;
-  // keep the first sync pass's pixel events (one per >= 4 bits of a slice;
-  // a slice with more parses its events again in dec_emit) unless the scratch
-  // does not fit, then every slice is parsed again in dec_emit
-  uint32_t ev_cap = opt_on(NICE_OPT_DEC_NO_EVENTS) ? 0u : cb / 4;
-  if (opt_set(NICE_OPT_DEC_EV_CAP)) {   // tests: force event overflow
-    const uint32_t v = (uint32_t)opt_val(NICE_OPT_DEC_EV_CAP);
-    if (ev_cap && v >= 4 && v % 4 == 0 && v < ev_cap) ev_cap = v;
-  }
-  const uint32_t subs = cb / DEC_EMIT_BITS;
-  DecLayout L = dec_layout(n_frames, max_chunks, n_ck, N, rowbuf, ev_cap, subs, hand, want_abort);
+  auto opt = [](int id) { return DecOpt{opt_set(id), opt_val(id)}; };
+  const DecOpts opts{opt(NICE_OPT_DEC_SLICE_BITS), opt(NICE_OPT_DEC_SINGLE_WAVE), opt(NICE_OPT_DEC_SEG),
+                     opt(NICE_OPT_DEC_SPLIT),      opt(NICE_OPT_DEC_FLOW),        opt(NICE_OPT_DEC_NO_EVENTS),
+                     opt(NICE_OPT_DEC_EV_CAP)};
+  DecPlan P = plan_decode(DecShape{n_frames, w, h, ctx->cus, max_len, total_bits}, opts);
+  ctx->last_dec_route = P.rows.route;
+  ctx->last_dec_fallback = P.fallback.route;
+  if (N > 0 && P.rows.route == DEC_R_NONE) return NICE_E_ARG;   // rows too wide for any row kernel
+  DecLayout L = dec_layout(n_frames, N, P);
   int rc = ctx->dec.grow(L.total);
-  if (rc && ev_cap) {
+  if (rc && P.ev_cap) {   // the scratch does not fit: without the first pass's events
     (void)hipGetLastError();   // the failed allocation
-    ev_cap = 0;
-    L = dec_layout(n_frames, max_chunks, n_ck, N, rowbuf, 0, subs, hand, want_abort);
+    P.ev_cap = 0;
+    L = dec_layout(n_frames, N, P);
     rc = ctx->dec.grow(L.total);
   }
   if (rc) return rc;
+  const uint32_t max_chunks = P.max_chunks;
   uint8_t* base = (uint8_t*)ctx->dec.ptr;
   DecArgs a{};
   a.streams = d_streams;
@@ -872,36 +856,8 @@ int nice::decode_batch_impl(nice_ctx* ctx, void* stream, const uint8_t* d_stream
   a.px_out = d_px;
   a.px_stride = px_stride;
   a.status = d_status;
-  a.tables = base + L.o_tables;
-  a.data_start = (unsigned long long*)(base + L.o_dstart);
-  a.max_chunks = max_chunks;
-  a.chunk_bits = cb;
-  a.n_ck = n_ck;
-  a.ck_bits = ck_bits;
-  a.emit_blocks = (uint32_t)(((uint64_t)max_chunks * (cb / DEC_EMIT_BITS) + DEC_PARSE_THREADS - 1) / DEC_PARSE_THREADS);
-  a.chunk_blocks = (max_chunks + DEC_PARSE_THREADS - 1) / DEC_PARSE_THREADS;
-  a.chunk_px = (unsigned long long*)(base + L.o_cpx);
-  a.chunk_start = (unsigned long long*)(base + L.o_cstart);
-  a.entry = (unsigned long long*)(base + L.o_entry);
-  a.last = (unsigned long long*)(base + L.o_last);
-  a.ck = (unsigned long long*)(base + L.o_ck);
-  a.recs = (uint32_t*)(base + L.o_recs);
-  a.rec_stride = (N + 3) & ~3ull;
-  a.seg = g.seg;
-  a.nseg = g.nseg;
-  a.rows_in_lds = g.in_lds ? 1u : 0u;
-  a.parse_slow = opt_on(NICE_OPT_DEC_SLOW_PARSE) ? 1u : 0u;   // tests / A/B: the general parse only
-  a.rowbuf = (uint32_t*)(base + L.o_rowbuf);
+  dec_args_scratch(a, L, base, P, N);
   uint32_t* changed = (uint32_t*)(base + L.o_changed);
-  if (ev_cap) {
-    a.ev = (uint32_t*)(base + L.o_ev);
-    a.ev_cap = ev_cap;
-    a.ev_ck = (uint32_t*)(base + L.o_evck);
-    a.ev_n = (uint32_t*)(base + L.o_evn);
-    a.agree = (uint32_t*)(base + L.o_agree);
-    a.head_items = (uint32_t*)(base + L.o_items);
-    a.head_count = (uint32_t*)(base + L.o_icount);
-  }
 
   PhaseTimer& tm = ctx->timer;
   tm.begin(NICE_PH_DEC_TABLES, st);
@@ -940,7 +896,7 @@ int nice::decode_batch_impl(nice_ctx* ctx, void* stream, const uint8_t* d_stream
     tm.end(st);
   }
   tm.begin(NICE_PH_DEC_RESYNC, st);
-  hipLaunchKernelGGL(dec_sync_settle, dim3(n_frames), dim3(512), 0, st, a, changed + queued - 1, fchanged,
+  hipLaunchKernelGGL(dec_sync_settle, dim3(n_frames), dim3(SETTLE_THREADS), 0, st, a, changed + queued - 1, fchanged,
                      changed + kSettledFlag);
   // the last iteration, for the slices the settle moved: it must change no
   // entry; a frame where it does (a settle that disagreed with dec_sync) is
@@ -981,119 +937,32 @@ int nice::decode_batch_impl(nice_ctx* ctx, void* stream, const uint8_t* d_stream
     hipLaunchKernelGGL(dec_place, dim3((max_chunks + DEC_PLACE_WAVES - 1) / DEC_PLACE_WAVES, n_frames), dim3(64 * DEC_PLACE_WAVES), 0, st, a);
     tm.end(st);
   }
-  if (g.lds > 64 * 1024)
-    NICE_HIP(hipFuncSetAttribute((const void*)dec_reconstruct,
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)g.lds));
   tm.begin(NICE_PH_DEC_RECON, st);
-  if (split) {
-    a.strips = strips;
+  if (P.abort_flags) {
+    a.hand_abort = (uint32_t*)(base + L.o_abort);
+    NICE_HIP(hipMemsetAsync(a.hand_abort, 0, (size_t)n_frames * 4, st));
+    ctx->split_abort = a.hand_abort;
+    ctx->split_frames = n_frames;
+  }
+  if (P.rows.route == DEC_R_SPLIT) {
+    a.strips = P.strips;
     a.hand = (unsigned long long*)(base + L.o_hand);
-    a.hand_abort = (uint32_t*)(base + L.o_abort);
-    NICE_HIP(hipMemsetAsync(a.hand, 0, hand, st));
-    NICE_HIP(hipMemsetAsync(a.hand_abort, 0, (size_t)n_frames * 4, st));
-    const uint32_t sps = (nseg16 + strips - 1) / strips;
-    // tails + flags + 4, then the ring; above 80 KB so a CU holds one strip
-    size_t lds = ((size_t)SPLIT_THREADS_HOST * 7 + 4 + 4 * ((size_t)sps * 16 + 6 + ((sps * 16 + 6) >> 4) + 17)) * 4;
-    lds = std::max<size_t>(lds, 82 * 1024);
-    NICE_HIP(hipFuncSetAttribute((const void*)dec_rows_split, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    NICE_HIP(hipMemsetAsync(a.hand, 0, P.hand, st));
     a.test_absent_strip = ctx->test_split_absent;
-    for (uint32_t f0 = 0; f0 < n_frames; f0 += split_frames) {
-      a.split_f0 = f0;
-      hipLaunchKernelGGL(dec_rows_split, dim3(std::min(split_frames, n_frames - f0) * strips),
-                         dim3(SPLIT_THREADS_HOST), lds, st, a);
-    }
-    a.split_f0 = 0;
-    a.test_absent_strip = 0;
-    // fallback: frames whose strips timed out waiting for a non-resident
-    // neighbour (every other block returns at once)
-    DecArgs r = a;
-    r.redo = 1;
-    if (use_rows)
-      hipLaunchKernelGGL(dec_rows_wide, dim3(n_frames), dim3(rows_thr), ((size_t)rows_thr * 7 + 8) * 4, st, r);
-    else
-      hipLaunchKernelGGL(dec_reconstruct, dim3(n_frames), dim3(64), g.lds, st, r);
-    ctx->split_abort = a.hand_abort;
-    ctx->split_frames = n_frames;
-  } else if (flow) {
-    if (flow_lds > 64 * 1024)
-      NICE_HIP(hipFuncSetAttribute((const void*)dec_rows_flow, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)flow_lds));
-    a.flow_k = flow_k;
-    a.flow_ring = flow_ring;
-    a.hand_abort = (uint32_t*)(base + L.o_abort);
-    NICE_HIP(hipMemsetAsync(a.hand_abort, 0, (size_t)n_frames * 4, st));
+  } else if (P.rows.route == DEC_R_FLOW) {
+    a.flow_k = P.flow_k;
+    a.flow_ring = P.flow_ring;
     a.test_absent_strip = opt_on(NICE_OPT_TEST_FLOW_ABSENT) ? 1u : 0u;
-    hipLaunchKernelGGL(dec_rows_flow, dim3(n_frames), dim3(64 * flow_k * flow_wpr), flow_lds, st, a);
+  }
+  if ((rc = launch_rows(P, P.rows, a, st))) return rc;
+  if (P.fallback.route != DEC_R_NONE) {   // its blocks return at once for every frame not marked SPLIT_REDO
     a.test_absent_strip = 0;
-    // fallback: frames whose waits timed out (the workgroup was
-    // preempted or time-sliced past the bound) go to the barrier kernel; its
-    // blocks return at once for every other frame
-    DecArgs r = a;
-    r.redo = 1;
-    if (rows_in_lds) {
-      if (rows_lds > 64 * 1024)
-        NICE_HIP(hipFuncSetAttribute((const void*)dec_rows, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)rows_lds));
-      hipLaunchKernelGGL(dec_rows, dim3(n_frames), dim3(rows_thr), rows_lds, st, r);
-    } else {
-      hipLaunchKernelGGL(dec_rows_wide, dim3(n_frames), dim3(rows_thr), ((size_t)rows_thr * 7 + 8) * 4, st, r);
-    }
-    ctx->split_abort = a.hand_abort;
-    ctx->split_frames = n_frames;
-  } else if (use_rows && rows_in_lds && rows8) {
-    if (rows8_lds > 64 * 1024)
-      NICE_HIP(hipFuncSetAttribute((const void*)dec_rows8, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)rows8_lds));
-    hipLaunchKernelGGL(dec_rows8, dim3(n_frames), dim3(rows8_thr), rows8_lds, st, a);
-  } else if (use_rows && rows_in_lds) {
-    if (rows_lds > 64 * 1024)
-      NICE_HIP(hipFuncSetAttribute((const void*)dec_rows, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)rows_lds));
-    hipLaunchKernelGGL(dec_rows, dim3(n_frames), dim3(rows_thr), rows_lds, st, a);
-  } else if (use_rows) {
-    hipLaunchKernelGGL(dec_rows_wide, dim3(n_frames), dim3(rows_thr), ((size_t)rows_thr * 7 + 8) * 4, st, a);
-  } else {
-    hipLaunchKernelGGL(dec_reconstruct, dim3(n_frames), dim3(64), g.lds, st, a);
+    a.redo = 1;
+    if ((rc = launch_rows(P, P.fallback, a, st))) return rc;
   }
   tm.end(st);
   if (dstats) {
-    unsigned long long h[128] = {0};
-    (void)hipMemcpyAsync(h, dstats, 1024, hipMemcpyDeviceToHost, st);
-    uint32_t chg[kSyncFlags] = {0};
-    (void)hipMemcpyAsync(chg, changed, 4 * kSyncFlags, hipMemcpyDeviceToHost, st);
-    (void)hipStreamSynchronize(st);
-    fprintf(stderr,
-            "[nice dec stats] rows=%llu unconverged_segs=%llu tail_unknown_segs=%llu "
-            "recomputed_px=%llu fixup_rounds=%llu sync_iters=%u seg=%u nseg=%u "
-            "clk[load=%llu spec=%llu fix=%llu emit=%llu]\n",
-            h[0], h[1], h[2], h[3], h[4], it_count, g.seg, g.nseg, h[5], h[6], h[7], h[8]);
-    fprintf(stderr, "[nice dec stats] sync iterations that changed an entry:");
-    for (uint32_t i = 0; i < kSyncFlags; ++i) fprintf(stderr, " %u", chg[i]);
-    fprintf(stderr, " (queued %u, then settled, final)\n", queued);
-    for (int w = 0; w < 4; ++w) {   // dec_rows_flow (-DNICE_FLOW_STATS builds): cycles per row by phase
-      const unsigned long long* q = h + 64 + 8 * w;
-      if (q[7])
-        fprintf(stderr, "[nice flow stats] wave %d rows=%llu cyc/row: emit+decode=%.0f wait=%.0f ring=%.0f spec=%.0f "
-                "fix=%.0f publish=%.0f rounds/row=%.2f\n", w, q[7], (double)q[0] / q[7], (double)q[1] / q[7],
-                (double)q[2] / q[7], (double)q[3] / q[7], (double)q[4] / q[7], (double)q[5] / q[7],
-                (double)q[6] / q[7]);
-    }
-    fprintf(stderr, "[nice dec stats] unknown segment tails: copies of an unknown %llu, narrowed %llu\n", h[24], h[25]);
-    fprintf(stderr, "[nice dec stats] re-parse met previous parse at checkpoint:");
-    for (int k = 0; k < 17; ++k) fprintf(stderr, " %d:%llu", k, h[32 + k]);
-    fprintf(stderr, "\n");
-    fprintf(stderr, "[nice dec stats] slice=%u emit waves=%llu wave_iters=%llu active_lane_iters=%llu fills=%llu\n",
-            a.chunk_bits, h[20], h[16], h[17], h[18]);
-    fprintf(stderr, "[nice dec stats] slices by first-pass meeting checkpoint: 0:%llu 1:%llu 2-4:%llu 5-16:%llu "
-            "17-64:%llu 65+:%llu none:%llu overflow:%llu (ev_cap %u)\n",
-            h[50], h[51], h[52], h[53], h[54], h[55], h[56], h[57], a.ev_cap);
-    fprintf(stderr, "[nice dec stats] fix-up rounds per row: 0:%llu 1:%llu 2:%llu 3:%llu 4:%llu 5:%llu 6+:%llu\n",
-            h[9], h[10], h[11], h[12], h[13], h[14], h[15]);
-    if (h[61]) fprintf(stderr, "[nice dec stats] sync first pass: waves=%llu cycles/wave=%.0f refill cycles/wave=%.0f "
-            "refills/wave=%.1f iterations/wave=%.1f active lane share=%.3f\n",
-            h[61], h[61] ? (double)h[56] / h[61] : 0.0, h[61] ? (double)h[57] / h[61] : 0.0,
-            h[61] ? (double)h[58] / h[61] : 0.0, h[61] ? (double)h[59] / h[61] : 0.0,
-            h[59] ? (double)h[60] / (64.0 * h[59]) : 0.0);
+    dec_print_stats(st, dstats, changed, it_count, queued, a);
     (void)hipFree(dstats);
   }
   NICE_HIP(hipGetLastError());
@@ -1425,7 +1294,7 @@ __global__ void nice_occupy_kernel(uint32_t short_blocks, unsigned long long sho
 }
 int nice_test_occupy(void* stream, uint32_t blocks, uint32_t short_blocks, uint32_t short_us, uint32_t long_us,
                      uint32_t lds_bytes) {
-  if (blocks == 0 || lds_bytes > 160 * 1024 || long_us > 5000000 || short_us > 5000000) return NICE_E_ARG;
+  if (blocks == 0 || lds_bytes > LDS_BUDGET || long_us > 5000000 || short_us > 5000000) return NICE_E_ARG;
   NICE_HIP(hipFuncSetAttribute((const void*)nice_occupy_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                (int)lds_bytes));
   hipLaunchKernelGGL(nice_occupy_kernel, dim3(blocks), dim3(64), lds_bytes, (hipStream_t)stream, short_blocks,
@@ -1461,6 +1330,17 @@ int nice_test_split_redos(nice_ctx* ctx, uint32_t* split_frames, uint32_t* redos
   std::vector<uint32_t> h(ctx->split_frames);
   NICE_HIP(hipMemcpy(h.data(), ctx->split_abort, h.size() * 4, hipMemcpyDeviceToHost));
   for (uint32_t v : h) *redos += v == SPLIT_REDO ? 1u : 0u;
+  return NICE_OK;
+}
+
+// The row kernel the context's last decode launched and its redo launch, as
+// DecRoute values (nice_dec_plan.hpp; 0: none).  ctx null: the context of the
+// host-buffer entry points (nice_decode).
+int nice_test_last_dec_route(nice_ctx* ctx, uint32_t* route, uint32_t* fallback) {
+  if (!ctx) ctx = g_default;
+  if (!ctx || !route || !fallback) return NICE_E_ARG;
+  *route = ctx->last_dec_route;
+  *fallback = ctx->last_dec_fallback;
   return NICE_OK;
 }
 

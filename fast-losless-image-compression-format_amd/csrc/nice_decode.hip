@@ -991,7 +991,6 @@ __global__ __launch_bounds__(DEC_PARSE_THREADS) PARSE_ATTR void dec_sync(DecArgs
 // re-parses the slices whose entries moved, bringing their pixel counts,
 // checkpoints and meeting points up to date.
 // ---------------------------------------------------------------------------
-constexpr uint32_t SETTLE_THREADS = 512;
 __global__ __launch_bounds__(SETTLE_THREADS) void dec_sync_settle(DecArgs a, const uint32_t* last_changed,
                                                                   const uint32_t* fchanged, uint32_t* settled) {
   __shared__ LutLds S;
@@ -1334,9 +1333,12 @@ constexpr unsigned long long CLS_PX_PACK = [] {
 
 
 // Record of a completed coded pixel (branch-free), as an event word: the
-// record (bits 0..27) plus EV_L2 (LUMA2: needs the row above) and EV_BAD (an
-// index the reference rejects wherever the pixel is, or an offset that wraps
-// for W < 3).  The position-dependent checks are rec_bad_at's.
+// record in its spread layout (REC_K: the constant in bits 0-7, 10-17 and
+// 20-27; the class in bits 28-31) with, in two of the gap bits that later
+// take the call's tag (REC_TAG_MASK: bits 8-9 and 18-19), EV_L2 (bit 8, LUMA2:
+// needs the row above) and EV_BAD (bit 9: an index the reference rejects
+// wherever the pixel is, or an offset that wraps for W < 3).  The
+// position-dependent checks are rec_bad_at's.
 __device__ __forceinline__ uint32_t make_event_rec(uint64_t W, uint32_t mode, uint32_t s0, uint32_t s1,
                                                    uint32_t s2, uint32_t s3) {
   const bool isbr = mode == P_BACK_REF, islu = mode == P_LUMA;
@@ -2111,8 +2113,7 @@ __device__ __forceinline__ void dec_reconstruct_body(const DecArgs& a) {
 //             (sound, so anything that collapses is final)
 //   emit      pixels to the ring and the caller's raster
 // ---------------------------------------------------------------------------
-constexpr int ROWS_SEG = 16;
-constexpr uint32_t ROWS_RING = 4;   // rows y-4 .. y-1 while row y is built
+// (ROWS_SEG, ROWS_RING and the kernels' LDS layouts: nice_geom.h)
 
 // Per-pixel word: spread constant c in the field bits, the kind as one-hot
 // flags in the guard bits -- W_L1/W_L2/W_L3: c plus the pixel 1..3 back;
@@ -2251,15 +2252,6 @@ __device__ __forceinline__ void rows_barrier() {
   }
 }
 
-// Ring row: W pixels padded one word per 16 (pixel x at x + (x >> 4)), plus 16
-// spare words that take a partial last segment's padding pixels (stored
-// unmasked), and halos so that no reference needs wrap logic: words -4..-2 hold
-// the previous row's last three pixels (x = -3..-1), words g(W..W+2) the next
-// row's first three (written when that row is emitted; the spare words of the
-// previous use are overwritten by then).
-constexpr uint32_t ROWS_RB = 4;   // left halo words before pixel 0
-__host__ __device__ constexpr uint32_t rows_ring_stride(uint32_t W) { return W + (W >> 4) + 24; }
-
 template <int MAXT, bool LDS_RING, int S = ROWS_SEG>
 __device__ __forceinline__ void dec_rows_body(const DecArgs& a) {
   // diagnostics counters (NICE_DEC_STATS=1) only in -DNICE_ROWS_STATS builds:
@@ -2282,16 +2274,17 @@ __device__ __forceinline__ void dec_rows_body(const DecArgs& a) {
   }
   const uint32_t nthr = blockDim.x;
   const uint32_t W = a.W, H = a.H;
-  uint32_t* tails = sm;                 // nthr x {lo, len} x 3 (pixels S-1, S-2, S-3)
-  uint32_t* flags = tails + nthr * 6;   // nthr: last three pixels exact
-  uint32_t* head3 = flags + nthr;       // pixels 0..2 of the current row
-  uint32_t* pend = head3 + 4;           // 2 round flags
-  int* err = reinterpret_cast<int*>(pend + 2);
+  const RowsLds lds = rows_lds(nthr);
+  uint32_t* tails = sm + lds.tails;   // nthr x {lo, len} x 3 (pixels S-1, S-2, S-3)
+  uint32_t* flags = sm + lds.flags;   // nthr: last three pixels exact
+  uint32_t* head3 = sm + lds.head3;   // pixels 0..2 of the current row
+  uint32_t* pend = sm + lds.pend;     // 2 round flags
+  int* err = reinterpret_cast<int*>(sm + lds.err);
   const uint32_t f = blockIdx.x;
   // ring rows padded one word per 16 pixels: lane i's segment starts at bank
   // 17i mod 32, so the lanes' accesses to their segments are conflict free
   const uint32_t RS = rows_ring_stride(W);
-  uint32_t* ring = (LDS_RING ? (sm + nthr * 7 + 8) : (a.rowbuf + (uint64_t)f * ROWS_RING * RS)) + ROWS_RB;
+  uint32_t* ring = (LDS_RING ? (sm + lds.ring) : (a.rowbuf + (uint64_t)f * ROWS_RING * RS)) + ROWS_RB;
   // per-row class table (S == 16), double-buffered by row parity: x = kind bits
   // | pixels back + 3, y = ring offset of the referenced row's pixel 0 plus 3
   // minus pixels back, so a reference's word is 17 * lane + p + y (+ a +-1
@@ -2605,11 +2598,11 @@ __device__ __forceinline__ void dec_rows_body(const DecArgs& a) {
 }
 
 // Ring in LDS (4 rows fit next to the block's tails) or in global memory.
-__global__ __launch_bounds__(512) void dec_rows(DecArgs a) { dec_rows_body<512, true>(a); }
-__global__ __launch_bounds__(1024) void dec_rows_wide(DecArgs a) { dec_rows_body<1024, false>(a); }
+__global__ __launch_bounds__(ROWS_THREADS) void dec_rows(DecArgs a) { dec_rows_body<ROWS_THREADS, true>(a); }
+__global__ __launch_bounds__(ROWS_WIDE_THREADS) void dec_rows_wide(DecArgs a) { dec_rows_body<ROWS_WIDE_THREADS, false>(a); }
 // 8-pixel segments (W <= 4096: up to 512 lanes): twice the lanes per frame,
 // for batches too small to fill the CUs (single-frame latency)
-__global__ __launch_bounds__(512) void dec_rows8(DecArgs a) { dec_rows_body<512, true, 8>(a); }
+__global__ __launch_bounds__(ROWS_THREADS) void dec_rows8(DecArgs a) { dec_rows_body<ROWS_THREADS, true, 8>(a); }
 
 // ---------------------------------------------------------------------------
 // D5d: dataflow row reconstruction for small batches (round 5; 64 <= W <=
@@ -2641,30 +2634,14 @@ __global__ __launch_bounds__(512) void dec_rows8(DecArgs a) { dec_rows_body<512,
 // is bounded (0.2 s, then the frame fails with NICE_E_HIP and the other waves
 // stop).
 // ---------------------------------------------------------------------------
-constexpr uint32_t FLOW_THREADS = 512;
-constexpr uint32_t FLOW_SLOTS = 8;   // stamp slots
-
-constexpr uint32_t FLOW_MAXW = 8;   // waves per row: W <= 8192 (round 6; 4 before)
+// (FLOW_THREADS, FLOW_SLOTS, FLOW_MAXW and struct FlowCtl: nice_geom.h)
 constexpr unsigned long long FLOW_TIMEOUT = 20000000ull;   // s_memrealtime ticks (100 MHz): 0.2 s
 // a timed-out wait (the workgroup preempted or time-sliced for longer than
 // that) does not fail the frame: it is marked for the barrier kernel
 // (dec_rows, launched after this one in redo mode) -- slower,
 // never wrong
 constexpr int FLOW_REDO = 1;
-struct FlowCtl {
-  uint32_t fin[FLOW_SLOTS][FLOW_MAXW];
-  uint32_t tst[FLOW_SLOTS][FLOW_MAXW];
-  uint32_t tail[FLOW_SLOTS][FLOW_MAXW][4];
-  uint32_t hst[FLOW_SLOTS];
-  uint32_t head[FLOW_SLOTS][4];
-  uint2 rtab[FLOW_THREADS / 64][16];   // per wave: the class table of its current row
-  uint32_t zero[4];                    // the "reference" word of records that have none
-  int err;
-  uint32_t abort;
-  uint32_t pad[2];
-};
-static_assert(sizeof(FlowCtl) % 16 == 0, "ring after the control block, 16-byte aligned");
-static_assert(sizeof(FlowCtl) == FLOW_CTL_BYTES_HOST && FLOW_THREADS == FLOW_THREADS_HOST, "host LDS sizing");
+static_assert(sizeof(FlowPair) == sizeof(uint2) && alignof(FlowPair) == alignof(uint2), "FlowCtl::rtab");
 __device__ __forceinline__ uint32_t flow_peek(const uint32_t* p) {
   return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
@@ -2793,7 +2770,7 @@ __global__ __launch_bounds__(FLOW_THREADS) void dec_rows_flow(DecArgs a) {
   const uint32_t depmask = w == 0 ? full : ((((7u << w) >> 1) & full) | (w == lastw ? 1u : 0u));
   const bool curlane = active && x0 + S + 2u >= W;   // words that can reference row y itself (W_CUR)
   const bool wave_cur = __any(curlane);
-  uint2* const rtab = C.rtab[wid];
+  uint2* const rtab = reinterpret_cast<uint2*>(C.rtab[wid]);
   const uint32_t lb = 17u * seg;
   uint32_t rn[S];
   auto load_recs = [&](uint32_t y) {
@@ -3086,14 +3063,12 @@ __global__ __launch_bounds__(FLOW_THREADS) void dec_rows_flow(DecArgs a) {
 // after SPLIT_TIMEOUT (a frame-wide abort flag stops the other strips early
 // on an error).
 // ---------------------------------------------------------------------------
-constexpr uint32_t SPLIT_THREADS = 256;                      // lanes (16-pixel segments) per strip
+// (SPLIT_THREADS, SPLIT_GRAN, split_ring_stride and the LDS layout: nice_geom.h)
 // s_memrealtime ticks (100 MHz): 0.2 s.  A wait this long means a strip's
 // neighbour is not resident (other kernels hold the CUs): the frame is handed
 // to the fallback launch (SPLIT_REDO), not failed
 constexpr unsigned long long SPLIT_TIMEOUT = 20000000ull;
 constexpr int SPLIT_QUIET = -1000, SPLIT_TIMED_OUT = -1001;   // block-local err codes
-constexpr uint32_t SPLIT_GRAN = 8;                           // granules per unit: first3 at 0..2, last3 at 4..6
-__host__ __device__ constexpr uint32_t split_ring_stride(uint32_t sw) { return (sw + 6) + ((sw + 6) >> 4) + 17; }
 __device__ __forceinline__ uint32_t sr_idx(uint32_t lc3) { return lc3 + (lc3 >> 4); }
 
 __device__ __forceinline__ void hand_put(unsigned long long* p, uint32_t row, uint32_t v) {
@@ -3205,8 +3180,8 @@ __global__ __launch_bounds__(SPLIT_THREADS) void dec_rows_split(DecArgs a) {
   const SplitGeo G{f, j, k, W, H, sw, split_ring_stride(sw), a.hand + (uint64_t)f * H * k * SPLIT_GRAN};
   const uint32_t RS = G.RS;
   uint32_t* tails = sm;                              // SPLIT_THREADS x {lo, len} x 3
-  uint32_t* flags = tails + SPLIT_THREADS * 6;       // SPLIT_THREADS
-  uint32_t* ring = flags + SPLIT_THREADS + 4;        // 4 x RS
+  uint32_t* flags = sm + SPLIT_FLAGS;                // SPLIT_THREADS
+  uint32_t* ring = sm + SPLIT_RING;                  // 4 x RS
   if (threadIdx.x < 32) {
     const uint32_t c = threadIdx.x & 15u;
     const unsigned long long kinds = threadIdx.x >= 16 ? ROWS_KIND_Y0 : ROWS_KIND;

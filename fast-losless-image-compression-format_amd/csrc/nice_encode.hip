@@ -471,7 +471,7 @@ __global__ __launch_bounds__(ENC_THREADS) void enc_classify_tiny(EncArgs a) { en
 //  * the five mode-prefix counts are accumulated per thread in packed
 //    registers and added to the histogram once per frame.
 // ---------------------------------------------------------------------------
-constexpr int CLS_THREADS = 512;
+// (CLS_THREADS: nice_geom.h)
 constexpr int CLS_PPT = ENC_TILE / CLS_THREADS;   // 2 pixels per thread
 constexpr int CLS_RING = 16384;                   // ring words (64 KB)
 // words 0..CLS_GUARD-1 of the ring mirrored past its end: a neighbour group
@@ -1595,7 +1595,7 @@ __global__ __launch_bounds__(256) void enc_rundigits(EncArgs a, int il) {
 // like the reference's linear offsets (code.rs:141-145) -- is inside the
 // window of its row.  Same outputs as enc_classify_ring.
 // ---------------------------------------------------------------------------
-constexpr int STRIP_W = 2048;
+// (STRIP_W: nice_geom.h)
 constexpr int STRIP_RS = STRIP_W + 8;              // window words (+3 each side, padded)
 constexpr int STRIP_LD = (STRIP_W + 6 + CLS_THREADS - 1) / CLS_THREADS;   // window loads per thread (5)
 

@@ -7,6 +7,8 @@
 #pragma once
 #include <stdint.h>
 
+#include "nice_geom.h"
+
 namespace nice {
 
 // Prefix symbols (stream SC_PREFIXES).
@@ -32,11 +34,11 @@ constexpr int N_STREAMS = 10;
 constexpr int N_BINS = 858;  // sum of alphabet sizes
 constexpr int MAX_ALPHABET = 343;
 
-__host__ __device__ constexpr int stream_size(int s) {
+NICE_HD constexpr int stream_size(int s) {
   return s == 0 ? 256 : s == 1 ? 13 : s == 2 ? 64 : s == 3 ? 32 : s == 4 ? 11
        : s == 5 ? 343 : s == 6 ? 64 : s == 7 ? 32 : s == 8 ? 32 : 11;
 }
-__host__ __device__ constexpr int stream_base(int s) {
+NICE_HD constexpr int stream_base(int s) {
   return s == 0 ? 0 : s == 1 ? 256 : s == 2 ? 269 : s == 3 ? 333 : s == 4 ? 365
        : s == 5 ? 376 : s == 6 ? 719 : s == 7 ? 783 : s == 8 ? 815 : 847;
 }
@@ -64,13 +66,13 @@ constexpr int FAST_MAX_CODE_BITS = 25;
 
 // Reference offsets expressed as (rows back, pixels back): off = k*W + d.
 // Back references, code.rs:145: [1, W, W-1, 2, 2W].
-__host__ __device__ constexpr int br_rows(int k) { return k == 0 ? 0 : k == 1 ? 1 : k == 2 ? 1 : k == 3 ? 0 : 2; }
-__host__ __device__ constexpr int br_px(int k) { return k == 0 ? 1 : k == 1 ? 0 : k == 2 ? -1 : k == 3 ? 2 : 0; }
+NICE_HD constexpr int br_rows(int k) { return k == 0 ? 0 : k == 1 ? 1 : k == 2 ? 1 : k == 3 ? 0 : 2; }
+NICE_HD constexpr int br_px(int k) { return k == 0 ? 1 : k == 1 ? 0 : k == 2 ? -1 : k == 3 ? 2 : 0; }
 // Luma references, code.rs:141-142: [1, W, W-1, W-3, 3, 3W-1, 3W, 3W+1, W+3, 3W+3, 3W-3].
-__host__ __device__ constexpr int lr_rows(int k) {
+NICE_HD constexpr int lr_rows(int k) {
   return k == 0 ? 0 : k <= 3 ? 1 : k == 4 ? 0 : k <= 7 ? 3 : k == 8 ? 1 : 3;
 }
-__host__ __device__ constexpr int lr_px(int k) {
+NICE_HD constexpr int lr_px(int k) {
   return k == 0 ? 1 : k == 1 ? 0 : k == 2 ? -1 : k == 3 ? -3 : k == 4 ? 3 : k == 5 ? -1
        : k == 6 ? 0 : k == 7 ? 1 : k == 8 ? 3 : k == 9 ? 3 : -3;
 }

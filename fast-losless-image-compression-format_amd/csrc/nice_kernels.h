@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "nice_geom.h"
+
 namespace nice {
 
 constexpr int ENC_TILE = 1024;          // pixels per encoder tile (raster-contiguous)
@@ -88,7 +90,6 @@ __global__ void enc_classify_ring(EncArgs a);    // RGBA
 __global__ void enc_classify_ring3(EncArgs a);   // RGB, 4-byte aligned frames
 __global__ void enc_classify_strip_m(EncArgs a);
 __global__ void enc_classify_strip(EncArgs a);   // RGBA, W % 1024 == 0, W > CLS_RING_MAX_W (tiles_per_block = rows per block)
-constexpr uint32_t STRIP_W_HOST = 2048;          // == STRIP_W (nice_encode.hip)
 // the 16K-pixel ring holds 3W + 3 pixels of references plus two tiles (the one
 // being classified and the next one being staged): 3W + 3 + 2048 <= 16384
 constexpr uint32_t CLS_RING_MAX_W = 4777;
@@ -121,7 +122,6 @@ constexpr uint32_t CLS_PAIR_MAX_W = 4095;
 #define NICE_PARSE_THREADS 512
 #endif
 constexpr uint32_t DEC_PARSE_THREADS = NICE_PARSE_THREADS;
-constexpr uint32_t CLS_THREADS_HOST = 512;   // == CLS_THREADS (nice_encode.hip)   // enc_classify_ring: 3W + 3 + 2 tiles fit its 16K-pixel ring
 __global__ void enc_tailruns(EncArgs a);
 __global__ void enc_tables(EncArgs a);
 __global__ void enc_code_lengths_test(const uint32_t* counts, int n, uint8_t* aob);
@@ -164,15 +164,7 @@ __global__ void enc_pack_long(EncArgs a, int phase);
 
 namespace nice {
 
-// sync checkpoint spacing inside a slice (DecArgs::ck_bits, chosen per call:
-// at most one emit sub-slice; 128: +30 % dec_sync -- scattered stores)
-constexpr uint32_t DEC_CK_BITS = 1024;      // slices of 8K bits and more (the bench's 512 x 4K)
-constexpr uint32_t DEC_CK_BITS_SMALL = 512;  // shorter slices (small batches)
-constexpr uint32_t DEC_MIN_CHUNK_BITS = 1024;   // speculative-parse slice: a power of two
-constexpr uint32_t DEC_MAX_CHUNK_BITS = 16384;  // chosen per call (nice_capi.hip)
 constexpr uint32_t DEC_PLACE_WAVES = 4;          // dec_place: one wave per slice (2 or 8 per block: slower; several slices per wave, their bookkeeping loads batched: slower too)
-constexpr uint32_t DEC_EMIT_BITS = 1024;        // record-emission sub-slice (<= the slice)
-constexpr int DEC_MAX_SEGS = 64;            // one lane per row segment
 
 struct DecArgs {
   const uint8_t* streams;
@@ -261,12 +253,8 @@ __global__ void dec_reconstruct(DecArgs a);
 __global__ void dec_rows(DecArgs a);
 __global__ void dec_rows_wide(DecArgs a);
 __global__ void dec_rows8(DecArgs a);
-__global__ void dec_rows_flow(DecArgs a);   // small batches: rows in flight, LDS stamps (W <= 4096)
-constexpr uint32_t FLOW_THREADS_HOST = 512, FLOW_CTL_BYTES_HOST = 2752;   // == FLOW_THREADS, sizeof(FlowCtl)
-constexpr uint32_t FLOW_MAX_W_HOST = 8192;   // 8 waves of 16-pixel segments per row (FLOW_MAXW)
+__global__ void dec_rows_flow(DecArgs a);   // small batches: rows in flight, LDS stamps (W <= FLOW_MAX_W)
 __global__ void dec_rows_split(DecArgs a);
-constexpr uint32_t SPLIT_THREADS_HOST = 256;   // == SPLIT_THREADS (nice_decode.hip): lanes per strip
-constexpr uint32_t SPLIT_GRAN_HOST = 8;        // == SPLIT_GRAN
 
 // Inclusive wave64 prefix sum by DPP: shifts 1, 2, 4, 8 inside each row of 16
 // lanes, then row 15 -> rows 1 and 3, row 31 -> rows 2 and 3.

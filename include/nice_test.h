@@ -39,6 +39,15 @@ int nice_test_set_option(int id, int64_t value);
 /* every option back to unset */
 void nice_test_reset_options(void);
 
+struct nice_ctx;
+/* frames of the context's last split / dataflow decode, and how many of them
+ * went to the fallback launch (synchronises the device) */
+int nice_test_split_redos(struct nice_ctx* ctx, uint32_t* split_frames, uint32_t* redos);
+/* the row kernel of the context's last decode and of its fallback launch:
+ * 0 none, 1 dec_reconstruct, 2 dec_rows, 3 dec_rows8, 4 dec_rows_wide,
+ * 5 dec_rows_flow, 6 dec_rows_split.  ctx NULL: the context nice_decode uses */
+int nice_test_last_dec_route(struct nice_ctx* ctx, uint32_t* route, uint32_t* fallback);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,48 @@
+"""The decoder's launch planner on the CPU (tools/dec_plan_check.cpp, built here
+with g++ once per session) and the library's report of the route it took
+(nice_test_last_dec_route), for the tests that compare the two."""
+import atexit
+import ctypes
+import functools
+import os
+import shutil
+import subprocess
+import tempfile
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "fast-losless-image-compression-format_amd", "csrc")
+
+# DecRoute (csrc/nice_dec_plan.hpp)
+ROUTE_IDS = {"none": 0, "dec_reconstruct": 1, "dec_rows": 2, "dec_rows8": 3, "dec_rows_wide": 4,
+             "dec_rows_flow": 5, "dec_rows_split": 6}
+ROUTE_NAMES = {v: k for k, v in ROUTE_IDS.items()}
+
+
+@functools.lru_cache(maxsize=None)
+def exe():
+    d = tempfile.mkdtemp(prefix="dec_plan_check_")
+    atexit.register(shutil.rmtree, d, ignore_errors=True)
+    out = os.path.join(d, "dec_plan_check")
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-I", CSRC, "-o", out,
+                           os.path.join(ROOT, "tools", "dec_plan_check.cpp")])
+    return out
+
+
+def plan(w, h, n_frames, cus, **options):
+    """One plan as a dict: route / fallback by kernel name, the numbers as ints.
+    options: single_wave, seg, split, flow (unset unless given)."""
+    args = [exe(), "plan", str(w), str(h), str(n_frames), str(cus)] + [f"{k}={v}" for k, v in options.items()]
+    line = subprocess.run(args, capture_output=True, text=True, check=True, timeout=60).stdout
+    kv = dict(f.split("=") for f in line.split())
+    return {k: v if k in ("route", "fallback") else int(v) for k, v in kv.items()}
+
+
+def last_route(nice, ctx=None):
+    """(route, fallback) kernel names of the last decode on ctx (None: the
+    context behind decode_bytes)."""
+    L = nice.lib()
+    L.nice_test_last_dec_route.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32),
+                                           ctypes.POINTER(ctypes.c_uint32)]
+    r, f = ctypes.c_uint32(), ctypes.c_uint32()
+    assert L.nice_test_last_dec_route(ctx.ptr if ctx is not None else None, ctypes.byref(r), ctypes.byref(f)) == 0
+    return ROUTE_NAMES[r.value], ROUTE_NAMES[f.value]

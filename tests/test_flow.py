@@ -14,6 +14,8 @@ group, 4-row ring) take this kernel too instead of the strip split."""
 import numpy as np
 import pytest
 
+import plan_driver
+
 pytestmark = pytest.mark.gpu
 
 
@@ -51,6 +53,8 @@ def test_flow_widths(nice, O, W, opts):
         for k in ("0", "1", "2", "3", "4"):
             opts.setenv("NICE_DEC_FLOW", k)
             assert np.array_equal(_decode(nice, s, C), rgb), (W, C, k)
+            # the forced kernel really ran (k = 0: any other row kernel)
+            assert (plan_driver.last_route(nice)[0] == "dec_rows_flow") == (k != "0"), (W, C, k)
 
 
 def test_flow_batch(nice, O, opts):
@@ -128,3 +132,4 @@ def test_flow_timeout_falls_back(nice, O, opts, k):
     nf, nr = ctypes.c_uint32(), ctypes.c_uint32()
     assert L.nice_test_split_redos(ctx.ptr, ctypes.byref(nf), ctypes.byref(nr)) == 0
     assert (nf.value, nr.value) == (1, 1)
+    assert plan_driver.last_route(nice, ctx) == ("dec_rows_flow", "dec_rows")

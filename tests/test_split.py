@@ -11,6 +11,8 @@ import time
 import numpy as np
 import pytest
 
+import plan_driver
+
 pytestmark = pytest.mark.gpu
 
 
@@ -33,9 +35,16 @@ def _cases(O):
     return cases
 
 
-def _check(nice, O, px, w, h, c):
+def _check(nice, O, px, w, h, c, split=None):
+    """Decodes through the host API; split = k: NICE_DEC_SPLIT=k is set, and the
+    decode must have taken the route the planner gives for it."""
     s = O.encode(px, w, h, c)
     got, img = nice.decode_bytes(s, flags=nice.DEC_ALPHA_FILL_FF | nice.DEC_TOLERANT_HEADER)
+    if split is not None:
+        import torch
+        want = plan_driver.plan(w, h, 1, torch.cuda.get_device_properties(0).multi_processor_count, split=split)
+        assert plan_driver.last_route(nice) == (want["route"], want["fallback"]), (w, split)
+        assert (want["route"] == "dec_rows_split") == (split >= 2), (w, split)   # these shapes: every k accepted
     g = np.frombuffer(got, np.uint8).reshape(-1, c)
     return np.array_equal(g[:, :3], px.reshape(-1, c)[:, :3])
 
@@ -44,15 +53,16 @@ def _check(nice, O, px, w, h, c):
 def test_split_forced_strips(nice, O, k, opts):
     opts.setenv("NICE_DEC_SPLIT", str(k))
     for name, px, w, h, c in _cases(O):
-        assert _check(nice, O, px, w, h, c), (name, k)
+        assert _check(nice, O, px, w, h, c, split=k), (name, k)
 
 
 def test_split_default_wide(nice, O, opts):
     """W > 4096 splits by default (ceil(W / 16 / 256) strips); =0 disables."""
     px = O.gen_syn_v1(8200, 9, 4, 8)
     assert _check(nice, O, px, 8200, 9, 4)
+    assert plan_driver.last_route(nice) == ("dec_rows_split", "dec_rows_wide")
     opts.setenv("NICE_DEC_SPLIT", "0")
-    assert _check(nice, O, px, 8200, 9, 4)
+    assert _check(nice, O, px, 8200, 9, 4, split=0)
 
 
 def test_split_batch_rgb_out(nice, O, opts):
@@ -71,9 +81,11 @@ def test_split_batch_rgb_out(nice, O, opts):
     lens = torch.tensor([len(s) for s in streams], dtype=torch.int64, device="cuda")
     dec = torch.zeros((n, w * h * 3), dtype=torch.uint8, device="cuda")
     status = torch.zeros(n, dtype=torch.int32, device="cuda")
-    nice.decode_batch(sb, lens, w, h, 3, dec, status, flags=nice.DEC_TOLERANT_HEADER)
+    ctx = nice.Context(0)
+    nice.decode_batch(sb, lens, w, h, 3, dec, status, flags=nice.DEC_TOLERANT_HEADER, ctx=ctx)
     torch.cuda.synchronize()
     assert status.cpu().tolist() == [0] * n
+    assert plan_driver.last_route(nice, ctx) == ("dec_rows_split", "dec_rows_wide")
     for i in range(n):
         assert np.array_equal(dec[i].cpu().numpy(), frames[i].reshape(-1, 4)[:, :3].reshape(-1)), i
 
@@ -97,7 +109,7 @@ def test_split_corrupt_stream_fails_fast(nice, O, opts):
         except nice.NiceError:
             pass
         assert time.time() - t0 < 3.0, trial
-    assert _check(nice, O, px, w, h, c)   # the context still decodes afterwards
+    assert _check(nice, O, px, w, h, c, split=4)   # the context still decodes afterwards
 
 
 @pytest.mark.parametrize("seg", ["8", "16"])
@@ -150,6 +162,7 @@ def test_split_wider_than_16384(nice, O):
     assert np.array_equal(dec[0].view(-1, 4)[:, :3].cpu().numpy(), px.reshape(-1, 4)[:, :3])
     nf, nr = _split_stats(nice, ctx)
     assert nf == 1 and nr == 0
+    assert plan_driver.last_route(nice, ctx) == ("dec_rows_split", "dec_reconstruct")
 
 
 def test_split_not_coresident_falls_back(nice, O):
@@ -182,6 +195,7 @@ def test_split_not_coresident_falls_back(nice, O):
     nice.decode_batch(sb, lens, w, h, 4, dec, status, flags=flags, stream=work, ctx=ctx)
     torch.cuda.synchronize()
     assert int(status[0]) == 0 and _split_stats(nice, ctx) == (1, 0)
+    assert plan_driver.last_route(nice, ctx) == ("dec_rows_split", "dec_rows_wide")
     dec.zero_()
     torch.cuda.synchronize()
     # one block per CU (96 KB of LDS each: no 82 KB strip block fits beside it);
@@ -218,4 +232,5 @@ def test_split_absent_strip_redone(nice, O, shape, opts):
     assert int(status[0]) == 0
     assert np.array_equal(dec[0].view(-1, 4)[:, :3].cpu().numpy(), px.reshape(-1, c)[:, :3])
     assert _split_stats(nice, ctx) == (1, 1)
+    assert plan_driver.last_route(nice, ctx) == ("dec_rows_split", "dec_rows_wide" if w <= 16384 else "dec_reconstruct")
     assert dt < 5.0, dt
