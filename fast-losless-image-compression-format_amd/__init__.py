@@ -27,6 +27,8 @@ __all__ = [
     "Image", "encode", "decode", "encode_bytes", "decode_bytes", "encode_bound",
     "encode_batch", "decode_batch", "Context", "Pipeline", "NiceError", "lib", "LIB_PATH",
     "packed_bound", "pack_streams", "encode_batch_packed", "decode_batch_packed", "save_packed", "load_packed",
+    "TiledImage", "tile_grid", "tile_select", "tiled_bound", "encode_tiled", "decode_tiled", "save_tiled",
+    "load_tiled", "DEFAULT_TILE",
     "DEC_STRICT_REFERENCE", "DEC_ALPHA_FILL_FF", "DEC_TOLERANT_HEADER",
 ]
 
@@ -53,6 +55,8 @@ EXPORTS = [
     "nice_pipe_create", "nice_pipe_destroy", "nice_pipe_stream_stride", "nice_pipe_encode",
     "nice_pipe_decode", "nice_pipe_set_checksums",
     "nice_packed_bound", "nice_pack_streams_dev", "nice_encode_batch_packed_dev", "nice_decode_packed_dev",
+    "nice_tile_grid", "nice_tiled_bound", "nice_tile_select", "nice_tiles_split_dev", "nice_tiles_merge_dev",
+    "nice_encode_tiled_dev", "nice_decode_tiled_dev",
 ]
 
 
@@ -108,6 +112,20 @@ def lib():
                                                ctypes.c_uint8, ctypes.c_uint8, u8p, u64, u8p, u8p, u8p]
     L.nice_decode_packed_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, u8p, u64, u8p, u8p, ctypes.c_void_p,
                                          u32, u32, u32, ctypes.c_uint8, u8p, u64, u32, u8p]
+    u8 = ctypes.c_uint8
+    u32p = ctypes.POINTER(u32)
+    L.nice_tile_grid.argtypes = [u32, u32, u32, u32, u32p, u32p]
+    L.nice_tiled_bound.restype = u64
+    L.nice_tiled_bound.argtypes = [u32, u32, u32, u32]
+    L.nice_tile_select.argtypes = [u32] * 8 + [u32p] * 4
+    L.nice_tiles_split_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, u8p, u64, u32, u32, u8, u32, u32, u8p, u64]
+    L.nice_tiles_merge_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, u8p, u64, u8p, u32, u8, u32, u32, u32, u32,
+                                       u32, u32, u32, u32, u8, u8, u8p, u64]
+    L.nice_encode_tiled_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, u8p, u64, u32, u32, u8, u8, u32, u32, u8p,
+                                        u64, u8p, u8p, u8p, u8p]
+    L.nice_decode_tiled_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, u8p, u64, ctypes.c_void_p, ctypes.c_void_p,
+                                        ctypes.c_void_p, u32, u32, u32, u32, u32, u32, u32, u32, u8, u8p, u64, u32,
+                                        u8p]
     L.nice_pipe_create.argtypes = [ctypes.c_int, u32, u32, ctypes.c_uint8, u32, u32,
                                    ctypes.POINTER(ctypes.c_void_p)]
     L.nice_pipe_destroy.argtypes = [ctypes.c_void_p]
@@ -462,6 +480,269 @@ def load_packed(path, device=None):
     if device is not None:
         packed, off, stream_len = packed.to(device), off.to(device), stream_len.to(device)
     return packed, off, stream_len, width, height, channels
+
+
+# ---- tiled images (include/nice.h, "tiled images") ---------------------------
+# One image as nx * ny independent tiles in one packed batch: a single large
+# image decodes on the whole device, a region decodes from the tiles it touches,
+# and tiles the format cannot carry are stored raw, so every input round-trips.
+# 1024 x 512: of 512 x 512, 1024 x 1024 and 1024 x 512 the fastest to decode and encode and the
+# smallest container on a 4K and a 16384 x 16384 frame (tools/bench_tiled.py; DESIGN.md, "Tiled images").
+DEFAULT_TILE = (1024, 512)
+
+
+@dataclass
+class TiledImage:
+    """A tiled image: ``packed`` (uint8 tensor) holds tile t at
+    ``off[t] : off[t] + stream_len[t]``; ``kind[t]`` is 0 for a NICE stream of
+    the padded tile and 1 for raw RGB.  ``off`` (n + 1, int64), ``stream_len``
+    (n, int64) and ``kind`` (n, uint8) are CPU tensors."""
+    width: int
+    height: int
+    channels: int
+    tile_w: int
+    tile_h: int
+    packed: object
+    off: object
+    stream_len: object
+    kind: object
+
+    @property
+    def nx(self) -> int:
+        return -(-self.width // self.tile_w)
+
+    @property
+    def ny(self) -> int:
+        return -(-self.height // self.tile_h)
+
+    @property
+    def nbytes(self) -> int:
+        """Bytes of the packed tiles (the container adds its tables)."""
+        return int(self.off[-1])
+
+
+def tile_grid(width: int, height: int, tile_w: int, tile_h: int):
+    """(nx, ny) of a tiled image; NiceError(E_ARG) for a geometry outside the limits."""
+    nx, ny = ctypes.c_uint32(), ctypes.c_uint32()
+    _check(lib().nice_tile_grid(width, height, tile_w, tile_h, ctypes.byref(nx), ctypes.byref(ny)), "nice_tile_grid")
+    return nx.value, ny.value
+
+
+def _u32_args(*vals):
+    if any(v < 0 or v >= 1 << 32 for v in vals):
+        raise NiceError(E_ARG, "argument outside 32 bits")
+    return vals
+
+
+def tile_select(width: int, height: int, tile_w: int, tile_h: int, x0: int, y0: int, rw: int, rh: int):
+    """(tx0, ty0, tx1, ty1): the half-open tile range the rectangle touches;
+    NiceError(E_ARG) for an empty rectangle or one that leaves the image."""
+    r = [ctypes.c_uint32() for _ in range(4)]
+    _check(lib().nice_tile_select(*_u32_args(width, height, tile_w, tile_h, x0, y0, rw, rh),
+                                  *[ctypes.byref(v) for v in r]), "nice_tile_select")
+    return tuple(v.value for v in r)
+
+
+def tiled_bound(width: int, height: int, tile_w: int, tile_h: int) -> int:
+    """Worst-case packed size of the tiled image (0: bad geometry)."""
+    return int(lib().nice_tiled_bound(width, height, tile_w, tile_h))
+
+
+def _rows_view(t, what):
+    """Row pitch in bytes of a [H, W, C] uint8 cuda tensor whose rows may be strided."""
+    if t.dim() != 3 or str(t.dtype) != "torch.uint8" or not t.is_cuda:
+        raise NiceError(E_ARG, f"{what}: a uint8 cuda tensor [H, W, C]")
+    c = t.shape[2]
+    if c not in (3, 4) or t.stride(2) != 1 or t.stride(1) != c or (t.shape[0] > 1 and t.stride(0) < t.shape[1] * c):
+        raise NiceError(E_ARG, f"{what}: C of 3 or 4, stride(2) == 1, stride(1) == C, rows not overlapping")
+    return t.stride(0) if t.shape[0] > 1 else t.shape[1] * c
+
+
+def encode_tiled(img, tile=None, channels_out: int | None = None, stream=None, ctx: "_Ctx | None" = None,
+                 packed=None) -> TiledImage:
+    """Encode ``img`` (uint8 cuda tensor [H, W, C], C 3 or 4, rows may be
+    strided: ``stride(1) == C``, ``stride(2) == 1``) as tiles of ``tile`` =
+    (tile_w, tile_h) pixels (default ``DEFAULT_TILE``).  Every tile is verified
+    by decoding it; the few the format cannot carry are stored raw, so
+    ``decode_tiled`` returns the input's RGB for every input (alpha is not
+    coded).  ``packed`` (optional uint8 cuda buffer, 16-byte aligned) receives
+    the tiles; too small a buffer raises NiceError(E_CAPACITY).  The result's
+    ``packed`` is trimmed to ``off[n]``.  Waits for the device (the tables come
+    back to the host)."""
+    import torch
+    tw, th = DEFAULT_TILE if tile is None else tile
+    pitch = _rows_view(img, "encode_tiled: img")
+    h, w, c = img.shape
+    nx, ny = tile_grid(w, h, tw, th)
+    n = nx * ny
+    dev = img.device
+    if packed is None:
+        packed = torch.empty(tiled_bound(w, h, tw, th), dtype=torch.uint8, device=dev)
+    off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    lens = torch.empty(n, dtype=torch.int64, device=dev)
+    kind = torch.empty(n, dtype=torch.uint8, device=dev)
+    status = torch.full((1,), 99, dtype=torch.int32, device=dev)
+    rc = lib().nice_encode_tiled_dev(
+        (ctx or _ctx(dev.index or 0)).ptr, _stream_of(torch, stream, dev), ctypes.c_void_p(img.data_ptr()), pitch,
+        w, h, c, c if channels_out is None else channels_out, tw, th, ctypes.c_void_p(packed.data_ptr()),
+        packed.numel(), ctypes.c_void_p(off.data_ptr()), ctypes.c_void_p(lens.data_ptr()),
+        ctypes.c_void_p(kind.data_ptr()), ctypes.c_void_p(status.data_ptr()))
+    _check(rc, "nice_encode_tiled_dev")
+    if stream is not None:
+        stream.synchronize()
+    _check(int(status.cpu()[0]), "nice_encode_tiled_dev")
+    off_h = off.cpu()
+    return TiledImage(w, h, c, tw, th, packed[:int(off_h[n])], off_h, lens.cpu(), kind.cpu())
+
+
+def decode_tiled(timg: TiledImage, roi=None, out=None, out_channels: int | None = None,
+                 flags: int = DEC_ALPHA_FILL_FF, stream=None, ctx: "_Ctx | None" = None):
+    """Decode ``timg`` (``packed`` on the GPU), or its rectangle ``roi`` =
+    (x, y, w, h), into a uint8 cuda tensor [rh, rw, out_channels]
+    (``out_channels`` defaults to ``out``'s, else the image's channels).  Only
+    the tiles the rectangle touches are decoded.  ``out`` may be a row-strided
+    view of a larger tensor.  If any tile fails, its pixels of the window are
+    left as they were, the other tiles are written, and NiceError is raised
+    with ``.statuses`` (one per selected tile, row-major) and ``.out``.  Waits
+    for the device (the statuses come back)."""
+    import torch
+    x0, y0, rw, rh = (0, 0, timg.width, timg.height) if roi is None else roi
+    tw, th = timg.tile_w, timg.tile_h
+    tx0, ty0, tx1, ty1 = tile_select(timg.width, timg.height, tw, th, x0, y0, rw, rh)
+    nx, ny = tile_grid(timg.width, timg.height, tw, th)
+    n = nx * ny
+    packed = timg.packed
+    if not packed.is_cuda:
+        raise NiceError(E_ARG, "decode_tiled: timg.packed must be on the GPU (load_tiled(path, device=...))")
+    off = timg.off.to("cpu", torch.int64).contiguous()
+    lens = timg.stream_len.to("cpu", torch.int64).contiguous()
+    kind = timg.kind.to("cpu", torch.uint8).contiguous()
+    if off.numel() < n + 1 or lens.numel() != n or kind.numel() != n or int(off[n]) > packed.numel():
+        raise NiceError(E_ARG, "decode_tiled: tables do not match the grid")
+    dev = packed.device
+    if out is None:
+        oc = timg.channels if out_channels is None else out_channels
+        out = torch.empty((rh, rw, oc), dtype=torch.uint8, device=dev)
+    else:
+        if out.dim() != 3 or tuple(out.shape[:2]) != (rh, rw) or (out_channels not in (None, out.shape[2])):
+            raise NiceError(E_ARG, "decode_tiled: out must be [rh, rw, out_channels]")
+        if out.device != dev:
+            raise NiceError(E_ARG, "decode_tiled: out on another device")
+    pitch = _rows_view(out, "decode_tiled: out")
+    m = (tx1 - tx0) * (ty1 - ty0)
+    status = torch.full((m,), 99, dtype=torch.int32, device=dev)
+    rc = lib().nice_decode_tiled_dev(
+        (ctx or _ctx(dev.index or 0)).ptr, _stream_of(torch, stream, dev), ctypes.c_void_p(packed.data_ptr()),
+        int(off[n]), ctypes.c_void_p(off.data_ptr()), ctypes.c_void_p(lens.data_ptr()),
+        ctypes.c_void_p(kind.data_ptr()), timg.width, timg.height, tw, th, x0, y0, rw, rh, out.shape[2],
+        ctypes.c_void_p(out.data_ptr()), pitch, flags, ctypes.c_void_p(status.data_ptr()))
+    _check(rc, "nice_decode_tiled_dev")
+    if stream is not None:
+        stream.synchronize()
+    st = status.cpu().tolist()
+    bad = [s for s in st if s != OK]
+    if bad:
+        err = NiceError(bad[0], f"nice_decode_tiled_dev: {len(bad)} of {m} tiles failed")
+        err.statuses = st
+        err.out = out
+        raise err
+    return out
+
+
+# Host-side container of a tiled image: one file, little-endian throughout
+# (NICEPACK version 1 above is a different file and stays as it is).
+#   header (56 bytes): magic "NICETILE", u32 version (1), u32 width, height,
+#                      channels, tile_w, tile_h, nx, ny, u32 reserved (0), u64 packed size
+#   n x u64 lengths, (n + 1) x u64 offsets, n x u8 kinds zero-padded to a
+#   multiple of 8 bytes, then the packed bytes
+_TILE_MAGIC = b"NICETILE"
+_TILE_VERSION = 1
+_TILE_HEADER = "<8sIIIIIIIIIQ"
+
+
+def save_tiled(path, timg: TiledImage) -> None:
+    """Write ``timg`` (tensors on the GPU or the CPU) to ``path``."""
+    import struct
+    import numpy as np
+    n = timg.nx * timg.ny
+    lens = np.asarray(timg.stream_len.detach().cpu().numpy(), dtype=np.int64).reshape(-1)
+    offs = np.asarray(timg.off.detach().cpu().numpy(), dtype=np.int64).reshape(-1)
+    kinds = np.asarray(timg.kind.detach().cpu().numpy(), dtype=np.uint8).reshape(-1)
+    if lens.size != n or offs.size != n + 1 or kinds.size != n:
+        raise NiceError(E_ARG, f"save_tiled: tables do not match the {timg.nx} x {timg.ny} grid")
+    size = int(offs[n])
+    if size < 0 or size > timg.packed.numel():
+        raise NiceError(E_ARG, "save_tiled: off[n] exceeds the packed buffer")
+    blob = timg.packed.detach().reshape(-1)[:size].cpu().numpy()
+    with open(path, "wb") as fh:
+        fh.write(struct.pack(_TILE_HEADER, _TILE_MAGIC, _TILE_VERSION, timg.width, timg.height, timg.channels,
+                             timg.tile_w, timg.tile_h, timg.nx, timg.ny, 0, size))
+        fh.write(lens.astype("<u8").tobytes())
+        fh.write(offs.astype("<u8").tobytes())
+        fh.write(kinds.tobytes() + bytes(-n % 8))
+        fh.write(blob.tobytes())
+
+
+def load_tiled(path, device=None) -> TiledImage:
+    """Read a ``save_tiled`` file.  ``packed`` goes to ``device`` (one
+    host-to-device copy), or stays on the CPU with ``device=None`` (no GPU and
+    no libnice_hip.so needed); the tables are CPU tensors.  A file that is not
+    a consistent tiled image raises NiceError(E_FORMAT)."""
+    import struct
+    import numpy as np
+    import torch
+
+    def bad(why):
+        return NiceError(E_FORMAT, f"load_tiled({path}): {why}")
+
+    hsz = struct.calcsize(_TILE_HEADER)
+    fsize = os.path.getsize(path)
+    with open(path, "rb") as fh:
+        head = fh.read(hsz)
+        if len(head) < hsz:
+            raise bad("truncated header")
+        magic, version, w, h, c, tw, th, nx, ny, reserved, size = struct.unpack(_TILE_HEADER, head)
+        if magic != _TILE_MAGIC:
+            raise bad("wrong magic")
+        if version != _TILE_VERSION:
+            raise bad(f"version {version}")
+        if c not in (3, 4) or w == 0 or h == 0 or w * h > 1 << 30 or reserved != 0:
+            raise bad("image size or channels")
+        if not (2 <= tw <= 8192 and 2 <= th <= 8192):
+            raise bad("tile size")
+        if nx != -(-w // tw) or ny != -(-h // th):
+            raise bad("grid does not match the image and tile sizes")
+        n = nx * ny
+        if n * (-(-tw * th // 1024)) >= 1 << 32:
+            raise bad("too many tiles")
+        if size % 16 or size >= 1 << 62:
+            raise bad("packed size")
+        kpad = n + (-n % 8)
+        if fsize != hsz + 8 * n + 8 * (n + 1) + kpad + size:
+            raise bad("file size does not match the header")
+        lens = np.frombuffer(fh.read(8 * n), "<u8")
+        offs = np.frombuffer(fh.read(8 * (n + 1)), "<u8")
+        kinds = np.frombuffer(fh.read(kpad), np.uint8)
+        if lens.size != n or offs.size != n + 1 or kinds.size != kpad:
+            raise bad("truncated")
+        if offs[0] != 0 or offs[n] != size or (offs % 16).any():
+            raise bad("offsets not 16-byte aligned from 0 to the packed size")
+        if (offs[1:] < offs[:-1]).any():
+            raise bad("offsets not monotone")
+        if (lens > offs[1:] - offs[:-1]).any():
+            raise bad("a tile overlaps the next")
+        if kinds[n:].any() or (kinds[:n] > 1).any():
+            raise bad("tile kinds")
+        if (lens[kinds[:n] == 1] != tw * th * 3).any():
+            raise bad("raw tile length")
+        blob = np.frombuffer(fh.read(size), np.uint8)
+        if blob.size != size:
+            raise bad("truncated")
+    packed = torch.from_numpy(blob.copy())
+    if device is not None:
+        packed = packed.to(device)
+    return TiledImage(w, h, c, tw, th, packed, torch.from_numpy(offs.astype(np.int64)),
+                      torch.from_numpy(lens.astype(np.int64)), torch.from_numpy(kinds[:n].copy()))
 
 
 def checksum64(buf) -> int:

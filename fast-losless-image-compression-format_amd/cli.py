@@ -11,6 +11,14 @@ through libnice_hip.so.  Streams the reference decoder cannot read (4-channel
 headers, spilled table headers of small/flat images) are decoded with the
 tolerant options; --strict refuses them as the reference would.  Timings are
 printed like the reference's (milliseconds).
+
+Tiled images (this project's own container, lossless for every input):
+
+    python fast-losless-image-compression-format_amd/cli.py IN.png OUT --tile WxH
+    python fast-losless-image-compression-format_amd/cli.py IN.nicet OUT[.png] [--roi X,Y,W,H]
+
+--tile writes OUT.nicet (".nicet" appended when missing); a .nicet input is
+decoded, whole or the --roi rectangle alone, and written as an RGB PNG.
 """
 from __future__ import annotations
 
@@ -42,12 +50,51 @@ def main(argv=None) -> int:
     ap.add_argument("src")
     ap.add_argument("dst")
     ap.add_argument("--strict", action="store_true", help="decode only what the reference decoder can")
+    ap.add_argument("--tile", metavar="WxH", help="encode a .png as a tiled image (.nicet) with tiles of W x H pixels")
+    ap.add_argument("--roi", metavar="X,Y,W,H", help="decode only this rectangle of a .nicet")
     args = ap.parse_args(argv)
+    try:
+        tile = tuple(int(v) for v in args.tile.lower().split("x")) if args.tile else None
+        roi = tuple(int(v) for v in args.roi.split(",")) if args.roi else None
+        if (tile and len(tile) != 2) or (roi and len(roi) != 4):
+            raise ValueError
+    except ValueError:
+        ap.error("--tile takes WxH, --roi takes X,Y,W,H")
+    if roi and not args.src.endswith(".nicet"):
+        ap.error("--roi needs a .nicet input")
+    if tile and not args.src.endswith(".png"):
+        ap.error("--tile needs a .png input")
     nice = _pkg()
     png = importlib.import_module(nice.__name__ + ".png")
     dst = args.dst
     print(f"a_file_from: {args.src}")
     print(f"a_file_to: {dst}")
+    if args.src.endswith(".png") and tile:
+        import torch
+        t0 = time.perf_counter()
+        px, w, h, ch = png.read_png(args.src)
+        print(f"png: {(time.perf_counter() - t0) * 1e3:.0f}")
+        if not dst.endswith(".nicet"):
+            dst += ".nicet"
+        print(f"bytes length: {px.size}")
+        t1 = time.perf_counter()
+        timg = nice.encode_tiled(torch.from_numpy(np.array(px, np.uint8).reshape(h, w, ch)).cuda(), tile=tile)
+        print(f"{(time.perf_counter() - t1) * 1e3:.0f}")
+        nice.save_tiled(dst, timg)
+        print(f"tiles: {timg.nx}x{timg.ny} raw: {int(timg.kind.sum())} bytes: {timg.nbytes}")
+        return 0
+    if args.src.endswith(".nicet"):
+        timg = nice.load_tiled(args.src, device="cuda")
+        t0 = time.perf_counter()
+        out = nice.decode_tiled(timg, roi=roi, out_channels=3)
+        rgb = out.cpu().numpy()
+        print(f"nice elapsed in: {(time.perf_counter() - t0) * 1e3:.0f}")
+        if not dst.endswith(".png"):
+            dst += ".png"
+        t1 = time.perf_counter()
+        png.write_png(dst, rgb.reshape(-1, 3), rgb.shape[1], rgb.shape[0], 3)
+        print(f"png{(time.perf_counter() - t1) * 1e3:.0f}")
+        return 0
     if args.src.endswith(".png"):
         t0 = time.perf_counter()
         px, w, h, ch = png.read_png(args.src)
@@ -76,7 +123,7 @@ def main(argv=None) -> int:
         png.write_png(dst, rgb, img.width, img.height, 3)
         print(f"png{(time.perf_counter() - t1) * 1e3:.0f}")
         return 0
-    print("input must be a .png or a .nice file", file=sys.stderr)
+    print("input must be a .png, a .nice or a .nicet file", file=sys.stderr)
     return 2
 
 

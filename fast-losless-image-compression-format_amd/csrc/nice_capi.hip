@@ -169,6 +169,10 @@ struct nice_ctx {
   std::mutex mu;
   Arena enc, dec, host_px, host_out, dev_len, band, band_hdr;
   Arena pack;   // nice_encode_batch_packed_dev: the strided streams before they are packed
+  // tiled images: the split tiles, the decoded tiles, and the small tables
+  // (gathered offsets, tile indices, statuses) of one call
+  Arena tiles, tile_dec, tile_tab;
+  uint32_t last_tiled_coded = 0, last_tiled_raw = 0;   // test hook nice_test_last_tiled
   PhaseTimer timer;
   BandState bs;
   // decoder record tags (DecArgs::rec_tag): the region the last call used and its tag
@@ -237,6 +241,9 @@ void nice_ctx_destroy(nice_ctx* ctx) {
   ctx->band.release();
   ctx->band_hdr.release();
   ctx->pack.release();
+  ctx->tiles.release();
+  ctx->tile_dec.release();
+  ctx->tile_tab.release();
   ctx->timer.release();
   (void)hipSetDevice(prev);
   delete ctx;
@@ -971,6 +978,200 @@ int nice::decode_batch_impl(nice_ctx* ctx, void* stream, const uint8_t* d_stream
 
 extern "C" {
 
+// ---- tiled images ----------------------------------------------------------
+int nice_tile_grid(uint32_t w, uint32_t h, uint32_t tile_w, uint32_t tile_h, uint32_t* nx, uint32_t* ny) {
+  if (!nx || !ny) return NICE_E_ARG;
+  if (w == 0 || h == 0 || (uint64_t)w * h > (1ull << 30)) return NICE_E_ARG;
+  if (tile_w < 2 || tile_h < 2 || tile_w > 8192 || tile_h > 8192) return NICE_E_ARG;
+  const uint64_t gx = ((uint64_t)w + tile_w - 1) / tile_w, gy = ((uint64_t)h + tile_h - 1) / tile_h;
+  // the batch encoder's 32-bit work counter: tiles x their 1024-pixel encoder tiles
+  if (gx * gy * tiles_for(tile_w, tile_h) >= (1ull << 32)) return NICE_E_ARG;
+  *nx = (uint32_t)gx;
+  *ny = (uint32_t)gy;
+  return NICE_OK;
+}
+
+uint64_t nice_tiled_bound(uint32_t w, uint32_t h, uint32_t tile_w, uint32_t tile_h) {
+  uint32_t nx, ny;
+  if (nice_tile_grid(w, h, tile_w, tile_h, &nx, &ny)) return 0;
+  return nice_packed_bound(nx * ny, tile_w, tile_h);
+}
+
+int nice_tile_select(uint32_t w, uint32_t h, uint32_t tile_w, uint32_t tile_h, uint32_t x0, uint32_t y0, uint32_t rw,
+                     uint32_t rh, uint32_t* tx0, uint32_t* ty0, uint32_t* tx1, uint32_t* ty1) {
+  uint32_t nx, ny;
+  if (!tx0 || !ty0 || !tx1 || !ty1) return NICE_E_ARG;
+  int rc = nice_tile_grid(w, h, tile_w, tile_h, &nx, &ny);
+  if (rc) return rc;
+  if (rw == 0 || rh == 0 || (uint64_t)x0 + rw > w || (uint64_t)y0 + rh > h) return NICE_E_ARG;
+  *tx0 = x0 / tile_w;
+  *ty0 = y0 / tile_h;
+  *tx1 = (x0 + rw - 1) / tile_w + 1;
+  *ty1 = (y0 + rh - 1) / tile_h + 1;
+  return NICE_OK;
+}
+
+int nice_tiles_split_dev(nice_ctx* ctx, void* stream, const uint8_t* d_img, uint64_t row_pitch, uint32_t w, uint32_t h,
+                         uint8_t channels, uint32_t tile_w, uint32_t tile_h, uint8_t* d_tiles, uint64_t tile_stride) {
+  if (!ctx || !d_img || !d_tiles || (channels != 3 && channels != 4)) return NICE_E_ARG;
+  uint32_t nx, ny;
+  int rc = nice_tile_grid(w, h, tile_w, tile_h, &nx, &ny);
+  if (rc) return rc;
+  if (row_pitch < (uint64_t)w * channels || tile_stride < (uint64_t)tile_w * tile_h * channels) return NICE_E_ARG;
+  NICE_HIP(hipSetDevice(ctx->device));
+  return nice::tiles_split_launch(stream, d_img, row_pitch, w, h, channels, tile_w, tile_h, nx, ny, d_tiles,
+                                  tile_stride);
+}
+
+int nice_tiles_merge_dev(nice_ctx* ctx, void* stream, const uint8_t* d_tiles, uint64_t tile_stride,
+                         const uint32_t* d_tile_idx, uint32_t n_slots, uint8_t tile_channels, uint32_t w, uint32_t h,
+                         uint32_t tile_w, uint32_t tile_h, uint32_t x0, uint32_t y0, uint32_t rw, uint32_t rh,
+                         uint8_t out_channels, uint8_t alpha, uint8_t* d_out, uint64_t out_pitch) {
+  if (!ctx || !d_out) return NICE_E_ARG;
+  if ((tile_channels != 3 && tile_channels != 4) || (out_channels != 3 && out_channels != 4)) return NICE_E_ARG;
+  uint32_t a, b, c, d, nx, ny;
+  int rc = nice_tile_select(w, h, tile_w, tile_h, x0, y0, rw, rh, &a, &b, &c, &d);
+  if (rc) return rc;
+  (void)nice_tile_grid(w, h, tile_w, tile_h, &nx, &ny);
+  if (out_pitch < (uint64_t)rw * out_channels) return NICE_E_ARG;
+  if (n_slots == 0) return NICE_OK;
+  if (!d_tiles || !d_tile_idx || tile_stride < (uint64_t)tile_w * tile_h * tile_channels) return NICE_E_ARG;
+  NICE_HIP(hipSetDevice(ctx->device));
+  return nice::tiles_merge_launch(stream, d_tiles, tile_stride, nullptr, d_tile_idx, nullptr, n_slots, w, h, tile_w,
+                                  tile_h, nx, ny, x0, y0, rw, rh, tile_channels, out_channels, alpha, d_out, out_pitch);
+}
+
+int nice_encode_tiled_dev(nice_ctx* ctx, void* stream, const uint8_t* d_img, uint64_t row_pitch, uint32_t w, uint32_t h,
+                          uint8_t channels, uint8_t channels_out, uint32_t tile_w, uint32_t tile_h, uint8_t* d_packed,
+                          uint64_t packed_cap, uint64_t* d_off, uint64_t* d_len, uint8_t* d_kind, int32_t* d_status) {
+  if (!ctx || !d_img || !d_off || !d_len || !d_kind || !d_status) return NICE_E_ARG;
+  if (channels != 3 && channels != 4) return NICE_E_ARG;
+  if ((!d_packed && packed_cap) || ((uintptr_t)d_packed & 15)) return NICE_E_ARG;
+  uint32_t nx, ny;
+  int rc = nice_tile_grid(w, h, tile_w, tile_h, &nx, &ny);
+  if (rc) return rc;
+  if (row_pitch < (uint64_t)w * channels) return NICE_E_ARG;
+  NICE_HIP(hipSetDevice(ctx->device));
+  const uint32_t n = nx * ny, npx = tile_w * tile_h;
+  const uint64_t tile_stride = align_up((size_t)npx * channels, 16);
+  const uint64_t slot = packed_slot_bytes(tile_w, tile_h);
+  if ((rc = ctx->tiles.grow((size_t)n * tile_stride))) return rc;
+  if ((rc = ctx->tile_dec.grow((size_t)n * tile_stride))) return rc;
+  if ((rc = ctx->pack.grow((size_t)n * slot))) return rc;
+  if ((rc = ctx->tile_tab.grow((size_t)n * 4))) return rc;
+  uint8_t* tiles = (uint8_t*)ctx->tiles.ptr;
+  uint8_t* back = (uint8_t*)ctx->tile_dec.ptr;
+  uint8_t* slots = (uint8_t*)ctx->pack.ptr;
+  int32_t* dec_status = (int32_t*)ctx->tile_tab.ptr;
+  if ((rc = nice::tiles_split_launch(stream, d_img, row_pitch, w, h, channels, tile_w, tile_h, nx, ny, tiles,
+                                     tile_stride)))
+    return rc;
+  if ((rc = nice_encode_batch_dev(ctx, stream, tiles, tile_stride, n, tile_w, tile_h, channels, channels_out, slots,
+                                  slot, d_len)))
+    return rc;
+  // verify: a table header the format cannot carry (SURVEY.md Appendix A.5,
+  // DESIGN.md "Tiled images") shows as a failed or a different decode
+  if ((rc = nice::decode_batch_impl(ctx, stream, slots, slot, d_len, nullptr, n, tile_w, tile_h, channels, back,
+                                    tile_stride, NICE_DEC_TOLERANT_HEADER, dec_status)))
+    return rc;
+  if ((rc = nice::tiles_compare_launch(stream, tiles, tile_stride, back, tile_stride, channels, n, npx, dec_status,
+                                       d_kind)))
+    return rc;
+  if ((rc = nice::tiles_store_raw_launch(stream, tiles, tile_stride, channels, n, npx, d_kind, slots, slot, d_len)))
+    return rc;
+  return nice::pack_streams_launch(stream, ctx->cus, slots, slot, d_len, n, d_packed, packed_cap, d_off, d_status);
+}
+
+int nice_decode_tiled_dev(nice_ctx* ctx, void* stream, const uint8_t* d_packed, uint64_t packed_bytes,
+                          const uint64_t* h_off, const uint64_t* h_len, const uint8_t* h_kind, uint32_t w, uint32_t h,
+                          uint32_t tile_w, uint32_t tile_h, uint32_t x0, uint32_t y0, uint32_t rw, uint32_t rh,
+                          uint8_t out_channels, uint8_t* d_out, uint64_t out_pitch, uint32_t flags, int32_t* d_status) {
+  if (!ctx || !d_packed || !h_off || !h_len || !h_kind || !d_out || !d_status) return NICE_E_ARG;
+  if (out_channels != 3 && out_channels != 4) return NICE_E_ARG;
+  if ((flags & NICE_DEC_STRICT_REFERENCE) || ((uintptr_t)d_packed & 15)) return NICE_E_ARG;
+  uint32_t nx, ny, tx0, ty0, tx1, ty1;
+  int rc = nice_tile_select(w, h, tile_w, tile_h, x0, y0, rw, rh, &tx0, &ty0, &tx1, &ty1);
+  if (rc) return rc;
+  (void)nice_tile_grid(w, h, tile_w, tile_h, &nx, &ny);
+  if (out_pitch < (uint64_t)rw * out_channels) return NICE_E_ARG;
+  NICE_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = (hipStream_t)stream;
+  const uint32_t m = (tx1 - tx0) * (ty1 - ty0);
+  const uint64_t npx = (uint64_t)tile_w * tile_h;
+  // the selected tiles by kind; a tile refused here keeps its status and is not touched
+  std::vector<uint64_t> c_off, c_len, r_off;
+  std::vector<uint32_t> c_idx, c_pos, r_idx;
+  std::vector<int32_t> init(m, NICE_OK);
+  uint32_t p = 0;
+  for (uint32_t ty = ty0; ty < ty1; ++ty) {
+    for (uint32_t tx = tx0; tx < tx1; ++tx, ++p) {
+      const uint32_t t = ty * nx + tx;
+      if (h_kind[t] == 0) {   // (its offset and length are checked on the device, as for any packed batch)
+        c_off.push_back(h_off[t]);
+        c_len.push_back(h_len[t]);
+        c_idx.push_back(t);
+        c_pos.push_back(p);
+      } else if (h_kind[t] != 1) {
+        init[p] = NICE_E_FORMAT;
+      } else if ((h_off[t] & 15) || h_off[t] > packed_bytes || h_len[t] > packed_bytes - h_off[t]) {
+        init[p] = NICE_E_ARG;
+      } else if (h_len[t] != 3 * npx) {
+        init[p] = NICE_E_FORMAT;
+      } else {
+        r_off.push_back(h_off[t]);
+        r_idx.push_back(t);
+      }
+    }
+  }
+  const uint32_t nc = (uint32_t)c_idx.size(), nr = (uint32_t)r_idx.size();
+  ctx->last_tiled_coded = nc;
+  ctx->last_tiled_raw = nr;
+  // one upload: u64 {coded offsets, coded lengths, raw offsets}, u32 {coded
+  // tile indices, coded positions, raw tile indices}, then the coded statuses
+  const size_t o_coff = 0, o_clen = o_coff + 8ull * nc, o_roff = o_clen + 8ull * nc, o_cidx = o_roff + 8ull * nr,
+               o_cpos = o_cidx + 4ull * nc, o_ridx = o_cpos + 4ull * nc, o_cst = align_up(o_ridx + 4ull * nr, 16),
+               tab_bytes = o_cst + 4ull * nc;
+  std::vector<uint8_t> tab(o_cst);
+  if (nc) {
+    memcpy(&tab[o_coff], c_off.data(), 8ull * nc);
+    memcpy(&tab[o_clen], c_len.data(), 8ull * nc);
+    memcpy(&tab[o_cidx], c_idx.data(), 4ull * nc);
+    memcpy(&tab[o_cpos], c_pos.data(), 4ull * nc);
+  }
+  if (nr) {
+    memcpy(&tab[o_roff], r_off.data(), 8ull * nr);
+    memcpy(&tab[o_ridx], r_idx.data(), 4ull * nr);
+  }
+  if ((rc = ctx->tile_tab.grow(std::max<size_t>(tab_bytes, 16)))) return rc;
+  uint8_t* dt = (uint8_t*)ctx->tile_tab.ptr;
+  if (o_cst) NICE_HIP(hipMemcpyAsync(dt, tab.data(), o_cst, hipMemcpyHostToDevice, st));
+  NICE_HIP(hipMemcpyAsync(d_status, init.data(), 4ull * m, hipMemcpyHostToDevice, st));
+  if (nc) {
+    const uint64_t stride = align_up((size_t)npx * out_channels, 16);
+    if ((rc = ctx->tile_dec.grow((size_t)nc * stride))) return rc;
+    uint8_t* dec = (uint8_t*)ctx->tile_dec.ptr;
+    int32_t* cst = (int32_t*)(dt + o_cst);
+    const uint32_t f = (flags & NICE_DEC_ALPHA_FILL_FF) | NICE_DEC_TOLERANT_HEADER;
+    if ((rc = nice::decode_batch_impl(ctx, stream, d_packed, 0, (const uint64_t*)(dt + o_clen), c_len.data(), nc, tile_w,
+                                      tile_h, out_channels, dec, stride, f, cst, (const uint64_t*)(dt + o_coff),
+                                      packed_bytes)))
+      return rc;
+    if ((rc = nice::tiles_scatter_status_launch(stream, cst, (const uint32_t*)(dt + o_cpos), nc, d_status))) return rc;
+    if ((rc = nice::tiles_merge_launch(stream, dec, stride, nullptr, (const uint32_t*)(dt + o_cidx), cst, nc, w, h,
+                                       tile_w, tile_h, nx, ny, x0, y0, rw, rh, out_channels, out_channels, 0, d_out,
+                                       out_pitch)))
+      return rc;
+  }
+  if (nr) {
+    const uint32_t fill = (flags & NICE_DEC_ALPHA_FILL_FF) ? 255u : 0u;
+    if ((rc = nice::tiles_merge_launch(stream, d_packed, 0, (const uint64_t*)(dt + o_roff),
+                                       (const uint32_t*)(dt + o_ridx), nullptr, nr, w, h, tile_w, tile_h, nx, ny, x0, y0,
+                                       rw, rh, 3, out_channels, fill, d_out, out_pitch)))
+      return rc;
+  }
+  return NICE_OK;
+}
+
 // ---- one image sharded over ranks ------------------------
 int nice_band_classify(nice_ctx* ctx, void* stream, const uint8_t* d_px, uint64_t px0, uint64_t px_count,
                        uint32_t w, uint32_t h, uint8_t channels, uint8_t channels_out, uint32_t tile_lo,
@@ -1341,6 +1542,13 @@ int nice_test_last_dec_route(nice_ctx* ctx, uint32_t* route, uint32_t* fallback)
   if (!ctx || !route || !fallback) return NICE_E_ARG;
   *route = ctx->last_dec_route;
   *fallback = ctx->last_dec_fallback;
+  return NICE_OK;
+}
+
+int nice_test_last_tiled(nice_ctx* ctx, uint32_t* coded, uint32_t* raw) {
+  if (!ctx || !coded || !raw) return NICE_E_ARG;
+  *coded = ctx->last_tiled_coded;
+  *raw = ctx->last_tiled_raw;
   return NICE_OK;
 }
 

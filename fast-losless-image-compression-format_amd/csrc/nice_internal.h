@@ -26,6 +26,32 @@ int pack_streams_launch(void* stream, int cus, const uint8_t* d_streams, uint64_
                         const uint64_t* d_stream_len, uint32_t n_frames, uint8_t* d_packed, uint64_t packed_cap,
                         uint64_t* d_off, int32_t* d_status);
 
+// ---- tiled images (nice_tiles.hip) -----------------------------------------
+// Arguments are checked by the callers (nice_capi.hip); every launch is
+// asynchronous on `stream`.  NICE_E_ARG: the grid would not fit a launch.
+// Image -> nx * ny dense tiles with clamped-coordinate padding.
+int tiles_split_launch(void* stream, const uint8_t* d_img, uint64_t row_pitch, uint32_t w, uint32_t h, uint32_t channels,
+                       uint32_t tile_w, uint32_t tile_h, uint32_t nx, uint32_t ny, uint8_t* d_tiles,
+                       uint64_t tile_stride);
+// Slot i (at d_tiles + i * tile_stride, or d_tiles + d_src_off[i]) holds tile
+// d_tile_idx[i]; its part inside the rectangle and the image goes to the
+// window.  A slot with d_slot_status[i] != 0 (d_slot_status may be null) is
+// skipped.  fill: byte +3 of a 4-byte output pixel when the slots hold 3.
+int tiles_merge_launch(void* stream, const uint8_t* d_tiles, uint64_t tile_stride, const uint64_t* d_src_off,
+                       const uint32_t* d_tile_idx, const int32_t* d_slot_status, uint32_t n_slots, uint32_t w,
+                       uint32_t h, uint32_t tile_w, uint32_t tile_h, uint32_t nx, uint32_t ny, uint32_t x0, uint32_t y0,
+                       uint32_t rw, uint32_t rh, uint32_t tile_channels, uint32_t out_channels, uint32_t fill,
+                       uint8_t* d_out, uint64_t out_pitch);
+// d_kind[t] = 0 if bytes +0..+2 of every pixel agree and d_status[t] == 0, else 1.
+int tiles_compare_launch(void* stream, const uint8_t* d_a, uint64_t stride_a, const uint8_t* d_b, uint64_t stride_b,
+                         uint32_t channels, uint32_t n, uint32_t npx, const int32_t* d_status, uint8_t* d_kind);
+// Tiles with d_kind[t] == 1: slot t = the tile's RGB, d_len[t] = 3 * npx.
+int tiles_store_raw_launch(void* stream, const uint8_t* d_tiles, uint64_t tile_stride, uint32_t channels, uint32_t n,
+                           uint32_t npx, const uint8_t* d_kind, uint8_t* d_slots, uint64_t slot_stride,
+                           uint64_t* d_len);
+// d_out[d_pos[i]] = d_st[i]
+int tiles_scatter_status_launch(void* stream, const int32_t* d_st, const uint32_t* d_pos, uint32_t n, int32_t* d_out);
+
 // nice_ctx_reserve; with_packed: also the strided scratch of
 // nice_encode_batch_packed_dev (n_frames stream slots).
 int ctx_reserve_impl(nice_ctx* ctx, uint32_t n_frames, uint32_t w, uint32_t h, bool with_packed);

@@ -1,0 +1,357 @@
+// nice_tiles.hip -- tiled images (include/nice.h, "Tiled images"): the copies
+// between one pitched image and its dense, equally sized tiles, the compare
+// behind the encoder's verify pass, and the raw fallback of a tile the format
+// cannot carry.  All of it moves bytes: a block takes a band of rows of one
+// tile, a wave one row at a time, a lane one pixel (or four, 16 bytes).
+// Everything but the lane's column is wave-uniform; a lane's loads are issued
+// before its stores.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <algorithm>
+
+#include "../../include/nice.h"
+#include "nice_internal.h"
+
+namespace nice {
+
+constexpr uint32_t TL_THREADS = 256;
+constexpr uint32_t TL_WAVES = TL_THREADS / 64;
+constexpr uint32_t TL_UNROLL = 4;            // 4 x 1 KiB of loads in flight per wave on the 16-byte path
+constexpr uint32_t TL_BLOCK_BYTES = 32768;   // a block's band of tile rows: about this many bytes
+
+// how a row is moved: per pixel byte by byte (any channels, any alignment),
+// per RGBA pixel as one dword, or four RGBA pixels as 16 bytes
+enum TileMode { TL_BYTES = 0, TL_DWORD = 1, TL_QUAD = 2 };
+
+struct TileGrid {
+  uint32_t w, h, tw, th, nx;
+  uint32_t bands, rows_pb;   // blocks per tile, tile rows per block
+};
+
+__device__ __forceinline__ uint32_t tl_wave() { return (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); }
+__device__ __forceinline__ uint32_t ld32(const uint8_t* p) { return *reinterpret_cast<const uint32_t*>(p); }
+
+// One pixel of `c` (3 or 4) bytes at p, byte loads: bytes +0..+2 in the low 24
+// bits, byte +3 (c == 4) or `fill` on top.
+__device__ __forceinline__ uint32_t ld_px_bytes(const uint8_t* p, uint32_t c, uint32_t fill) {
+  const uint32_t b0 = p[0], b1 = p[1], b2 = p[2];
+  const uint32_t b3 = c == 4 ? (uint32_t)p[3] : fill;
+  return b0 | (b1 << 8) | (b2 << 16) | (b3 << 24);
+}
+__device__ __forceinline__ void st_px_bytes(uint8_t* p, uint32_t c, uint32_t v) {
+  p[0] = (uint8_t)v;
+  p[1] = (uint8_t)(v >> 8);
+  p[2] = (uint8_t)(v >> 16);
+  if (c == 4) p[3] = (uint8_t)(v >> 24);
+}
+
+// Image -> tiles.  Tile position (r, g) takes the image pixel at the clamped
+// coordinate (min(x, w - 1), min(y, h - 1)): every load is inside the image,
+// every store inside the tile.
+template <int MODE>
+__global__ __launch_bounds__(TL_THREADS) void tiles_split(const uint8_t* __restrict__ img, uint64_t pitch, uint32_t C,
+                                                          TileGrid q, uint8_t* __restrict__ tiles,
+                                                          uint64_t tile_stride) {
+  const uint32_t t = blockIdx.x / q.bands, band = blockIdx.x % q.bands;
+  const uint32_t ty = t / q.nx, tx = t % q.nx;
+  const uint32_t lane = threadIdx.x & 63u, wave = tl_wave();
+  const uint32_t r0 = band * q.rows_pb, r1 = min(r0 + q.rows_pb, q.th);
+  const uint32_t x0 = tx * q.tw, xl = q.w - 1;
+  uint8_t* dt = tiles + (uint64_t)t * tile_stride;
+  for (uint32_t r = r0 + wave; r < r1; r += TL_WAVES) {
+    const uint32_t y = min(ty * q.th + r, q.h - 1);
+    const uint8_t* srow = img + (uint64_t)y * pitch;
+    uint8_t* drow = dt + (uint64_t)r * q.tw * C;
+    if (MODE == TL_QUAD) {
+      const uint32_t G = q.tw >> 2;
+      for (uint32_t g0 = 0; g0 < G; g0 += 64u * TL_UNROLL) {
+        uint4 v[TL_UNROLL];
+#pragma unroll
+        for (uint32_t u = 0; u < TL_UNROLL; ++u) {
+          const uint32_t g = g0 + 64u * u + lane;
+          if (g < G) {
+            const uint32_t x = x0 + 4u * g;
+            if (x + 4u <= q.w) {
+              v[u] = *reinterpret_cast<const uint4*>(srow + 4ull * x);
+            } else {   // the image's right edge runs through or before this group
+              v[u].x = ld32(srow + 4ull * min(x, xl));
+              v[u].y = ld32(srow + 4ull * min(x + 1u, xl));
+              v[u].z = ld32(srow + 4ull * min(x + 2u, xl));
+              v[u].w = ld32(srow + 4ull * min(x + 3u, xl));
+            }
+          }
+        }
+#pragma unroll
+        for (uint32_t u = 0; u < TL_UNROLL; ++u) {
+          const uint32_t g = g0 + 64u * u + lane;
+          if (g < G) *reinterpret_cast<uint4*>(drow + 16ull * g) = v[u];
+        }
+      }
+    } else {
+      for (uint32_t g0 = 0; g0 < q.tw; g0 += 64u * TL_UNROLL) {
+        uint32_t v[TL_UNROLL];
+#pragma unroll
+        for (uint32_t u = 0; u < TL_UNROLL; ++u) {
+          const uint32_t g = g0 + 64u * u + lane;
+          if (g < q.tw) {
+            const uint8_t* s = srow + (uint64_t)min(x0 + g, xl) * C;
+            v[u] = MODE == TL_DWORD ? ld32(s) : ld_px_bytes(s, C, 0u);
+          }
+        }
+#pragma unroll
+        for (uint32_t u = 0; u < TL_UNROLL; ++u) {
+          const uint32_t g = g0 + 64u * u + lane;
+          if (g < q.tw) {
+            if (MODE == TL_DWORD) *reinterpret_cast<uint32_t*>(drow + 4ull * g) = v[u];
+            else st_px_bytes(drow + (uint64_t)g * C, C, v[u]);
+          }
+        }
+      }
+    }
+  }
+}
+
+struct MergeArgs {
+  const uint8_t* tiles;
+  uint64_t tile_stride;
+  const unsigned long long* src_off;   // non-null: slot i at tiles + src_off[i]
+  const uint32_t* tile_idx;
+  const int32_t* slot_status;          // non-null: a slot with a nonzero status is skipped
+  uint32_t n_tiles;                    // nx * ny
+  uint32_t x0, y0, rw, rh;
+  uint32_t tc, oc, fill;               // bytes per pixel in the slots, in the window; byte +3 when tc == 3
+  uint8_t* out;
+  uint64_t out_pitch;
+};
+
+// Tiles -> window.  Slot i's tile, cut to the rectangle and to the image (no
+// padding is ever written), goes to out + (y - y0) * out_pitch + (x - x0) * oc.
+template <int MODE>
+__global__ __launch_bounds__(TL_THREADS) void tiles_merge(MergeArgs a, TileGrid q) {
+  const uint32_t slot = blockIdx.x / q.bands, band = blockIdx.x % q.bands;
+  if (a.slot_status && a.slot_status[slot] != 0) return;
+  const uint32_t t = a.tile_idx[slot];
+  if (t >= a.n_tiles) return;
+  const uint32_t ty = t / q.nx, tx = t % q.nx;
+  const uint32_t lane = threadIdx.x & 63u, wave = tl_wave();
+  // the tile's pixels inside the rectangle and the image: [xa, xb) x [ya, yb)
+  const uint64_t tx0 = (uint64_t)tx * q.tw, ty0 = (uint64_t)ty * q.th;
+  const uint64_t xa64 = max(tx0, (uint64_t)a.x0);
+  const uint64_t xb64 = min(min(tx0 + q.tw, (uint64_t)a.x0 + a.rw), (uint64_t)q.w);
+  const uint64_t ya64 = max(ty0 + (uint64_t)band * q.rows_pb, (uint64_t)a.y0);
+  const uint64_t yb64 = min(min(ty0 + min((uint64_t)(band + 1) * q.rows_pb, (uint64_t)q.th), (uint64_t)a.y0 + a.rh),
+                            (uint64_t)q.h);
+  if (xa64 >= xb64 || ya64 >= yb64) return;
+  const uint32_t xa = (uint32_t)xa64, xb = (uint32_t)xb64, ya = (uint32_t)ya64, yb = (uint32_t)yb64;
+  const uint8_t* st = a.tiles + (a.src_off ? (uint64_t)a.src_off[slot] : (uint64_t)slot * a.tile_stride);
+  const uint32_t nxp = xb - xa;
+  for (uint32_t y = ya + wave; y < yb; y += TL_WAVES) {
+    const uint8_t* srow = st + ((uint64_t)(y - (uint32_t)ty0) * q.tw + (xa - (uint32_t)tx0)) * a.tc;
+    uint8_t* drow = a.out + (uint64_t)(y - a.y0) * a.out_pitch + (uint64_t)(xa - a.x0) * a.oc;
+    if (MODE == TL_QUAD) {   // xa, x0 and the tile's x origin are multiples of 4: both rows are 16-byte aligned
+      const uint32_t G = (nxp + 3u) >> 2;
+      for (uint32_t g0 = 0; g0 < G; g0 += 64u * TL_UNROLL) {
+        uint4 v[TL_UNROLL];
+#pragma unroll
+        for (uint32_t u = 0; u < TL_UNROLL; ++u) {
+          const uint32_t g = g0 + 64u * u + lane;
+          // (the source group is whole inside the tile: tw % 4 == 0)
+          if (g < G) v[u] = *reinterpret_cast<const uint4*>(srow + 16ull * g);
+        }
+#pragma unroll
+        for (uint32_t u = 0; u < TL_UNROLL; ++u) {
+          const uint32_t g = g0 + 64u * u + lane;
+          if (g < G) {
+            uint8_t* d = drow + 16ull * g;
+            if (4u * g + 4u <= nxp) {
+              *reinterpret_cast<uint4*>(d) = v[u];
+            } else {   // the window or the image ends inside this group
+              const uint32_t k = nxp - 4u * g;   // 1..3 pixels
+              *reinterpret_cast<uint32_t*>(d) = v[u].x;
+              if (k > 1) *reinterpret_cast<uint32_t*>(d + 4) = v[u].y;
+              if (k > 2) *reinterpret_cast<uint32_t*>(d + 8) = v[u].z;
+            }
+          }
+        }
+      }
+    } else {
+      for (uint32_t g0 = 0; g0 < nxp; g0 += 64u * TL_UNROLL) {
+        uint32_t v[TL_UNROLL];
+#pragma unroll
+        for (uint32_t u = 0; u < TL_UNROLL; ++u) {
+          const uint32_t g = g0 + 64u * u + lane;
+          if (g < nxp) v[u] = MODE == TL_DWORD ? ld32(srow + 4ull * g) : ld_px_bytes(srow + (uint64_t)g * a.tc, a.tc, a.fill);
+        }
+#pragma unroll
+        for (uint32_t u = 0; u < TL_UNROLL; ++u) {
+          const uint32_t g = g0 + 64u * u + lane;
+          if (g < nxp) {
+            if (MODE == TL_DWORD) *reinterpret_cast<uint32_t*>(drow + 4ull * g) = v[u];
+            else st_px_bytes(drow + (uint64_t)g * a.oc, a.oc, v[u]);
+          }
+        }
+      }
+    }
+  }
+}
+
+// kind[t] = 1 where bytes +0..+2 of some pixel of tile t differ between the two
+// arrays or status[t] != 0 (kind is zeroed before the launch; every writer
+// stores the same 1).  dword: both arrays hold 4-byte aligned RGBA pixels.
+__global__ __launch_bounds__(TL_THREADS) void tiles_compare(const uint8_t* __restrict__ A, uint64_t stride_a,
+                                                            const uint8_t* __restrict__ B, uint64_t stride_b,
+                                                            uint32_t C, uint32_t npx, uint32_t chunks, uint32_t per,
+                                                            int dword, const int32_t* __restrict__ status,
+                                                            uint8_t* __restrict__ kind) {
+  const uint32_t t = blockIdx.x / chunks, chunk = blockIdx.x % chunks;
+  if (status[t] != 0) {   // nothing to compare: the decode wrote no defined pixels
+    if (chunk == 0 && threadIdx.x == 0) kind[t] = 1;
+    return;
+  }
+  const uint8_t* a = A + (uint64_t)t * stride_a;
+  const uint8_t* b = B + (uint64_t)t * stride_b;
+  const uint64_t p0 = (uint64_t)chunk * per;
+  const uint32_t p1 = (uint32_t)min(p0 + per, (uint64_t)npx);
+  bool diff = false;
+  for (uint64_t pb = p0; pb < p1; pb += (uint64_t)TL_THREADS * TL_UNROLL) {
+    uint32_t va[TL_UNROLL], vb[TL_UNROLL];
+#pragma unroll
+    for (uint32_t u = 0; u < TL_UNROLL; ++u) {
+      const uint64_t p = pb + (uint64_t)u * TL_THREADS + threadIdx.x;
+      va[u] = vb[u] = 0;
+      if (p < p1) {
+        va[u] = dword ? ld32(a + 4ull * p) : ld_px_bytes(a + p * C, 3, 0u);
+        vb[u] = dword ? ld32(b + 4ull * p) : ld_px_bytes(b + p * C, 3, 0u);
+      }
+    }
+#pragma unroll
+    for (uint32_t u = 0; u < TL_UNROLL; ++u) diff |= ((va[u] ^ vb[u]) & 0xFFFFFFu) != 0;
+  }
+  if (__ballot(diff) != 0ull && (threadIdx.x & 63u) == 0) kind[t] = 1;
+}
+
+// A tile with kind[t] == 1: its slot takes the tile's RGB (3 bytes per pixel,
+// row-major) and len[t] their count.
+__global__ __launch_bounds__(TL_THREADS) void tiles_store_raw(const uint8_t* __restrict__ tiles, uint64_t tile_stride,
+                                                              uint32_t C, uint32_t npx, uint32_t chunks, uint32_t per,
+                                                              const uint8_t* __restrict__ kind,
+                                                              uint8_t* __restrict__ slots, uint64_t slot_stride,
+                                                              unsigned long long* __restrict__ len) {
+  const uint32_t t = blockIdx.x / chunks, chunk = blockIdx.x % chunks;
+  if (kind[t] == 0) return;
+  if (chunk == 0 && threadIdx.x == 0) len[t] = 3ull * npx;
+  const uint8_t* s = tiles + (uint64_t)t * tile_stride;
+  uint8_t* d = slots + (uint64_t)t * slot_stride;
+  const uint64_t p0 = (uint64_t)chunk * per;
+  const uint32_t p1 = (uint32_t)min(p0 + per, (uint64_t)npx);
+  for (uint64_t pb = p0; pb < p1; pb += (uint64_t)TL_THREADS * TL_UNROLL) {
+    uint32_t v[TL_UNROLL];
+#pragma unroll
+    for (uint32_t u = 0; u < TL_UNROLL; ++u) {
+      const uint64_t p = pb + (uint64_t)u * TL_THREADS + threadIdx.x;
+      if (p < p1) v[u] = ld_px_bytes(s + p * C, 3, 0u);
+    }
+#pragma unroll
+    for (uint32_t u = 0; u < TL_UNROLL; ++u) {
+      const uint64_t p = pb + (uint64_t)u * TL_THREADS + threadIdx.x;
+      if (p < p1) st_px_bytes(d + 3ull * p, 3, v[u]);
+    }
+  }
+}
+
+// out[pos[i]] = st[i]: the coded tiles' decode statuses to their places among the selected tiles
+__global__ void tiles_scatter_status(const int32_t* __restrict__ st, const uint32_t* __restrict__ pos, uint32_t n,
+                                     int32_t* __restrict__ out) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) out[pos[i]] = st[i];
+}
+
+namespace {
+// Blocks per tile and rows per block for rows of row_bytes; false if the grid does not fit.
+bool tile_bands(uint32_t slots, uint32_t th, uint64_t row_bytes, TileGrid& q) {
+  uint64_t rows = TL_BLOCK_BYTES / std::max<uint64_t>(row_bytes, 1);
+  rows = std::min<uint64_t>(std::max<uint64_t>(rows, TL_WAVES), th);
+  q.rows_pb = (uint32_t)rows;
+  q.bands = (th + q.rows_pb - 1) / q.rows_pb;
+  return (uint64_t)slots * q.bands <= 0x7FFFFFFFull;
+}
+// Pixels per block of the two per-pixel kernels.
+bool px_chunks(uint32_t n, uint32_t npx, uint32_t& chunks, uint32_t& per) {
+  per = TL_THREADS * TL_UNROLL * 8;
+  chunks = (npx + per - 1) / per;
+  return (uint64_t)n * chunks <= 0x7FFFFFFFull;
+}
+inline bool al(const void* p, uint64_t s, uint32_t a) { return ((uintptr_t)p & (a - 1)) == 0 && (s & (a - 1)) == 0; }
+}  // namespace
+
+int tiles_split_launch(void* stream, const uint8_t* d_img, uint64_t row_pitch, uint32_t w, uint32_t h, uint32_t channels,
+                       uint32_t tile_w, uint32_t tile_h, uint32_t nx, uint32_t ny, uint8_t* d_tiles,
+                       uint64_t tile_stride) {
+  TileGrid q{w, h, tile_w, tile_h, nx, 0, 0};
+  const uint32_t n = nx * ny;
+  if (!tile_bands(n, tile_h, (uint64_t)tile_w * channels, q)) return NICE_E_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid(n * q.bands), block(TL_THREADS);
+  const bool rgba = channels == 4;
+  if (rgba && (tile_w & 3u) == 0 && al(d_img, row_pitch, 16) && al(d_tiles, tile_stride, 16))
+    hipLaunchKernelGGL(tiles_split<TL_QUAD>, grid, block, 0, st, d_img, row_pitch, channels, q, d_tiles, tile_stride);
+  else if (rgba && al(d_img, row_pitch, 4) && al(d_tiles, tile_stride, 4))
+    hipLaunchKernelGGL(tiles_split<TL_DWORD>, grid, block, 0, st, d_img, row_pitch, channels, q, d_tiles, tile_stride);
+  else
+    hipLaunchKernelGGL(tiles_split<TL_BYTES>, grid, block, 0, st, d_img, row_pitch, channels, q, d_tiles, tile_stride);
+  return hipGetLastError() == hipSuccess ? NICE_OK : NICE_E_HIP;
+}
+
+int tiles_merge_launch(void* stream, const uint8_t* d_tiles, uint64_t tile_stride, const uint64_t* d_src_off,
+                       const uint32_t* d_tile_idx, const int32_t* d_slot_status, uint32_t n_slots, uint32_t w,
+                       uint32_t h, uint32_t tile_w, uint32_t tile_h, uint32_t nx, uint32_t ny, uint32_t x0, uint32_t y0,
+                       uint32_t rw, uint32_t rh, uint32_t tile_channels, uint32_t out_channels, uint32_t fill,
+                       uint8_t* d_out, uint64_t out_pitch) {
+  if (n_slots == 0) return NICE_OK;
+  TileGrid q{w, h, tile_w, tile_h, nx, 0, 0};
+  if (!tile_bands(n_slots, tile_h, (uint64_t)tile_w * tile_channels, q)) return NICE_E_ARG;
+  MergeArgs a{d_tiles, tile_stride, (const unsigned long long*)d_src_off, d_tile_idx, d_slot_status, nx * ny,
+              x0, y0, rw, rh, tile_channels, out_channels, fill, d_out, out_pitch};
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid(n_slots * q.bands), block(TL_THREADS);
+  const bool rgba = tile_channels == 4 && out_channels == 4 && !d_src_off;
+  if (rgba && (tile_w & 3u) == 0 && (x0 & 3u) == 0 && al(d_tiles, tile_stride, 16) && al(d_out, out_pitch, 16))
+    hipLaunchKernelGGL(tiles_merge<TL_QUAD>, grid, block, 0, st, a, q);
+  else if (rgba && al(d_tiles, tile_stride, 4) && al(d_out, out_pitch, 4))
+    hipLaunchKernelGGL(tiles_merge<TL_DWORD>, grid, block, 0, st, a, q);
+  else
+    hipLaunchKernelGGL(tiles_merge<TL_BYTES>, grid, block, 0, st, a, q);
+  return hipGetLastError() == hipSuccess ? NICE_OK : NICE_E_HIP;
+}
+
+int tiles_compare_launch(void* stream, const uint8_t* d_a, uint64_t stride_a, const uint8_t* d_b, uint64_t stride_b,
+                         uint32_t channels, uint32_t n, uint32_t npx, const int32_t* d_status, uint8_t* d_kind) {
+  uint32_t chunks, per;
+  if (!px_chunks(n, npx, chunks, per)) return NICE_E_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  if (hipMemsetAsync(d_kind, 0, n, st) != hipSuccess) return NICE_E_HIP;
+  const int dword = channels == 4 && al(d_a, stride_a, 4) && al(d_b, stride_b, 4);
+  hipLaunchKernelGGL(tiles_compare, dim3(n * chunks), dim3(TL_THREADS), 0, st, d_a, stride_a, d_b, stride_b, channels,
+                     npx, chunks, per, dword, d_status, d_kind);
+  return hipGetLastError() == hipSuccess ? NICE_OK : NICE_E_HIP;
+}
+
+int tiles_store_raw_launch(void* stream, const uint8_t* d_tiles, uint64_t tile_stride, uint32_t channels, uint32_t n,
+                           uint32_t npx, const uint8_t* d_kind, uint8_t* d_slots, uint64_t slot_stride,
+                           uint64_t* d_len) {
+  uint32_t chunks, per;
+  if (!px_chunks(n, npx, chunks, per)) return NICE_E_ARG;
+  hipLaunchKernelGGL(tiles_store_raw, dim3(n * chunks), dim3(TL_THREADS), 0, (hipStream_t)stream, d_tiles, tile_stride,
+                     channels, npx, chunks, per, d_kind, d_slots, slot_stride, (unsigned long long*)d_len);
+  return hipGetLastError() == hipSuccess ? NICE_OK : NICE_E_HIP;
+}
+
+int tiles_scatter_status_launch(void* stream, const int32_t* d_st, const uint32_t* d_pos, uint32_t n, int32_t* d_out) {
+  if (n == 0) return NICE_OK;
+  hipLaunchKernelGGL(tiles_scatter_status, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, d_st, d_pos, n,
+                     d_out);
+  return hipGetLastError() == hipSuccess ? NICE_OK : NICE_E_HIP;
+}
+
+}  // namespace nice

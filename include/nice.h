@@ -175,6 +175,104 @@ int nice_decode_packed_dev(nice_ctx* ctx, void* stream, const uint8_t* d_packed,
                            uint32_t n_frames, uint32_t w, uint32_t h, uint8_t out_channels, uint8_t* d_px,
                            uint64_t px_stride, uint32_t flags, int32_t* d_status);
 
+/* ---- tiled images ----
+ * One image cut into independent tiles, coded as one packed batch: a single
+ * large image decodes on the whole device instead of row by row on one compute
+ * unit, a rectangle decodes from the tiles it touches alone, and the result is
+ * lossless for every input (below).
+ *
+ * Geometry.  The image is w x h (w, h >= 1, w * h <= 2^30) with `channels` 3
+ * or 4; the tile is tile_w x tile_h, 2 <= tile_w, tile_h <= 8192.
+ *   nx = ceil(w / tile_w), ny = ceil(h / tile_h), n = nx * ny
+ *   tile t = ty * nx + tx covers image pixels [tx*tile_w, ..) x [ty*tile_h, ..)
+ * Every tile is coded at the full tile_w x tile_h, edge tiles and images
+ * smaller than one tile included: a position outside the image takes the
+ * pixel at the clamped coordinate (min(x, w - 1), min(y, h - 1)).  n times the
+ * 1024-pixel encoder tiles of one tile must stay below 2^32 (the batch
+ * encoder's work counter).  Anything else is NICE_E_ARG.
+ * As everywhere in this codec only bytes +0..+2 of a pixel are coded: the
+ * tiled path does not preserve alpha either.
+ *
+ * Layout.  The n tiles are a packed batch (above): d_packed, off[n + 1],
+ * len[n], plus kind[n] (u8).  kind 0: an ordinary NICE stream, byte for byte
+ * what nice_encode gives for the padded tile's pixels.  kind 1: the tile's raw
+ * RGB, tile_w * tile_h * 3 bytes in row-major order.  Raw tiles exist because
+ * the format cannot carry every table its encoder builds: a Huffman table
+ * whose longest code exceeds 128 bits gets a header no decoder can read, and
+ * small, smooth tiles do produce such tables.  The encoder therefore decodes
+ * every tile back, compares, and stores the failing ones raw. */
+/* Validates the geometry; *nx, *ny receive the grid. */
+int nice_tile_grid(uint32_t w, uint32_t h, uint32_t tile_w, uint32_t tile_h, uint32_t* nx, uint32_t* ny);
+/* nice_packed_bound(nx * ny, tile_w, tile_h): always enough for d_packed (a
+ * raw tile is smaller than nice_encode_bound).  0 for a bad geometry. */
+uint64_t nice_tiled_bound(uint32_t w, uint32_t h, uint32_t tile_w, uint32_t tile_h);
+/* The half-open tile range [tx0, tx1) x [ty0, ty1) that the rectangle
+ * [x0, x0 + rw) x [y0, y0 + rh) touches.  An empty rectangle or one that
+ * leaves the image is NICE_E_ARG. */
+int nice_tile_select(uint32_t w, uint32_t h, uint32_t tile_w, uint32_t tile_h, uint32_t x0, uint32_t y0, uint32_t rw,
+                     uint32_t rh, uint32_t* tx0, uint32_t* ty0, uint32_t* tx1, uint32_t* ty1);
+/* Image -> tiles.  d_img: rows of w pixels, row y at d_img + y*row_pitch
+ * (row_pitch >= w*channels; any alignment).  Tile t is written dense at
+ * d_tiles + t*tile_stride (tile_stride >= tile_w*tile_h*channels), padded by
+ * the clamp rule.  RGBA with tile_w % 4 == 0 and 16-byte aligned d_img,
+ * row_pitch, d_tiles and tile_stride moves 16 bytes per lane; other RGBA with
+ * 4-byte alignment one dword per pixel; everything else bytes.  Asynchronous. */
+int nice_tiles_split_dev(nice_ctx* ctx, void* stream, const uint8_t* d_img, uint64_t row_pitch, uint32_t w, uint32_t h,
+                         uint8_t channels, uint32_t tile_w, uint32_t tile_h, uint8_t* d_tiles, uint64_t tile_stride);
+/* Tiles -> window.  Slot i (d_tiles + i*tile_stride, tile_channels bytes per
+ * pixel) holds tile d_tile_idx[i]; d_tile_idx is device memory, slots in any
+ * order, an index >= nx*ny is skipped.  For each slot the intersection of its
+ * tile, the rectangle (inside the image, as for nice_tile_select) and the
+ * image is written to d_out + (y - y0)*out_pitch + (x - x0)*out_channels
+ * (out_pitch >= rw*out_channels).  Nothing outside the rw x rh window is
+ * written, and no padding.  tile_channels 3 -> out_channels 4 writes `alpha`
+ * as byte +3; 4 -> 3 drops it.  The 16-byte path needs RGBA on both sides,
+ * tile_w % 4 == 0, x0 % 4 == 0 and 16-byte aligned bases, stride and pitch.
+ * Asynchronous. */
+int nice_tiles_merge_dev(nice_ctx* ctx, void* stream, const uint8_t* d_tiles, uint64_t tile_stride,
+                         const uint32_t* d_tile_idx, uint32_t n_slots, uint8_t tile_channels, uint32_t w, uint32_t h,
+                         uint32_t tile_w, uint32_t tile_h, uint32_t x0, uint32_t y0, uint32_t rw, uint32_t rh,
+                         uint8_t out_channels, uint8_t alpha, uint8_t* d_out, uint64_t out_pitch);
+/* Encodes one device-resident image as n tiles: split into context scratch,
+ * nice_encode_batch_dev into the context's strided stream slots, decode of
+ * every tile with NICE_DEC_TOLERANT_HEADER, compare with the split tiles
+ * (bytes +0..+2), raw RGB over the slot of every tile that failed or differed,
+ * then the pack into d_packed (16-byte aligned, packed_cap bytes;
+ * nice_tiled_bound() always suffices).  d_off (n + 1 u64) and *d_status are
+ * written as by nice_encode_batch_packed_dev, d_len[t] (n u64) = tile t's
+ * length, d_kind[t] (n u8) = 0 coded, 1 raw; all device memory.
+ * The call waits once for the work it queued itself (the stream lengths size
+ * the verify decode's scratch, as in nice_decode_batch_dev); the verify
+ * decode, compare, raw store and pack are only enqueued.
+ * Scratch, owned and reused by the context, nice_ctx_reserve does not
+ * pre-size it: the split tiles and the decoded tiles (padded image x channels
+ * each), the stream slots (nice_encode_bound per tile, about 4 bytes per
+ * pixel) and the batch encoder's and decoder's own scratch. */
+int nice_encode_tiled_dev(nice_ctx* ctx, void* stream, const uint8_t* d_img, uint64_t row_pitch, uint32_t w, uint32_t h,
+                          uint8_t channels, uint8_t channels_out, uint32_t tile_w, uint32_t tile_h, uint8_t* d_packed,
+                          uint64_t packed_cap, uint64_t* d_off /* n + 1 */, uint64_t* d_len /* n */,
+                          uint8_t* d_kind /* n */, int32_t* d_status /* 1 */);
+/* Decodes the rectangle [x0, x0 + rw) x [y0, y0 + rh) of a tiled image into
+ * d_out (row pitch out_pitch >= rw*out_channels, out_channels 3 or 4).
+ * h_off, h_len, h_kind: the tables of all n tiles in host memory (h_off needs
+ * n entries).  Only the tiles the rectangle touches are read: coded tiles are
+ * decoded in place from d_packed (16-byte aligned) into context scratch, raw
+ * tiles are expanded from their 3-byte pixels, and both are merged into the
+ * window.  The tolerant table header is always on; NICE_DEC_ALPHA_FILL_FF is
+ * honoured (raw tiles included); NICE_DEC_STRICT_REFERENCE is NICE_E_ARG.
+ * d_status: one entry per selected tile, row-major over [ty0, ty1) x [tx0, tx1)
+ * of nice_tile_select.  A tile whose status is not NICE_OK leaves its pixels
+ * of the window untouched; the others are written.  Per tile: an offset that
+ * is not a multiple of 16 or off + len > packed_bytes is NICE_E_ARG, a kind
+ * other than 0 or 1 or a raw length other than tile_w*tile_h*3 NICE_E_FORMAT,
+ * a coded tile reports its decode status.
+ * The call uploads the gathered tables of the selected tiles (a few KB) and
+ * otherwise only enqueues work. */
+int nice_decode_tiled_dev(nice_ctx* ctx, void* stream, const uint8_t* d_packed, uint64_t packed_bytes,
+                          const uint64_t* h_off, const uint64_t* h_len, const uint8_t* h_kind, uint32_t w, uint32_t h,
+                          uint32_t tile_w, uint32_t tile_h, uint32_t x0, uint32_t y0, uint32_t rw, uint32_t rh,
+                          uint8_t out_channels, uint8_t* d_out, uint64_t out_pitch, uint32_t flags, int32_t* d_status);
+
 /* ---- one image sharded over ranks (config 4) ----
  * The image's raster is cut into bands of whole encoder tiles (1024 pixels in
  * raster order); rank r encodes tiles [tile_lo, tile_hi).  The caller runs the

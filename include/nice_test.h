@@ -47,6 +47,10 @@ int nice_test_split_redos(struct nice_ctx* ctx, uint32_t* split_frames, uint32_t
  * 0 none, 1 dec_reconstruct, 2 dec_rows, 3 dec_rows8, 4 dec_rows_wide,
  * 5 dec_rows_flow, 6 dec_rows_split.  ctx NULL: the context nice_decode uses */
 int nice_test_last_dec_route(struct nice_ctx* ctx, uint32_t* route, uint32_t* fallback);
+/* tiles the context's last nice_decode_tiled_dev decoded as streams and
+ * expanded from raw pixels: together the tiles its rectangle selected, minus
+ * those refused on the host (bad kind, raw length or raw offset) */
+int nice_test_last_tiled(struct nice_ctx* ctx, uint32_t* coded, uint32_t* raw);
 
 #ifdef __cplusplus
 }
