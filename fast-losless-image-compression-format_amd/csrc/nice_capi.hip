@@ -17,6 +17,7 @@
 #include "nice_bits.hpp"
 #include "nice_kernels.h"
 #include "nice_dec_plan.hpp"
+#include "nice_enc_plan.hpp"
 #include "nice_rec.hpp"
 #include "nice_internal.h"
 
@@ -64,8 +65,8 @@ inline bool opt_on(int id) { return opt_set(id) && opt_val(id) != 0; }
 struct EncLayout {
   size_t zero_bytes, total;
   size_t o_hist, o_flags, o_ctr, o_status, o_overn, o_overl;
-  size_t o_first, o_last, o_next, o_tbl, o_tblcode, o_len8, o_smax, o_seedbit, o_seedsuf,
-      o_hdrbytes, o_hdrcache, o_hdrbitoff, o_recs, o_tbits, o_toff, o_dend, o_packtab, o_gacc, o_bhist, o_cmask;
+  size_t o_first, o_last, o_next, o_tblcode, o_len8, o_smax, o_seedbit, o_recs, o_tbits, o_toff, o_dend, o_packtab,
+      o_gacc, o_bhist, o_cmask;
 };
 
 EncLayout enc_layout(uint32_t n_frames, uint32_t T, uint64_t npx) {
@@ -82,15 +83,10 @@ EncLayout enc_layout(uint32_t n_frames, uint32_t T, uint64_t npx) {
   L.o_first = take((size_t)n_frames * T * 4);
   L.o_last = take((size_t)n_frames * T * 4);
   L.o_next = take((size_t)n_frames * T * 4);
-  L.o_tbl = take((size_t)n_frames * N_BINS * 4);
   L.o_tblcode = take((size_t)n_frames * N_BINS * 4);
   L.o_len8 = take((size_t)n_frames * N_BINS);
   L.o_smax = take((size_t)n_frames * N_STREAMS);
   L.o_seedbit = take((size_t)n_frames * 8);
-  L.o_seedsuf = take((size_t)n_frames * 4);
-  L.o_hdrbytes = take((size_t)n_frames * 8);
-  L.o_hdrcache = take((size_t)n_frames * 4);
-  L.o_hdrbitoff = take((size_t)n_frames);
   L.o_recs = take((size_t)n_frames * ((npx + 3) & ~3ull) * 4);
   L.o_tbits = take((size_t)n_frames * T * 4);
   L.o_toff = take((size_t)n_frames * T * 8);
@@ -156,6 +152,7 @@ struct PhaseTimer {
 struct BandState {
   bool classified = false, tabled = false;
   nice::EncArgs a{};
+  nice::EncPlan plan{};   // of the band's classify, runs and pack
   uint64_t band_bits = 0, seed_bit = 0;
   // the band's own symbol counts (nice_band_runs), for its bit count
   uint32_t* bhist = nullptr;
@@ -249,11 +246,6 @@ void nice_ctx_destroy(nice_ctx* ctx) {
   delete ctx;
 }
 
-static uint32_t tiles_for(uint32_t w, uint32_t h) {
-  const uint64_t N = (uint64_t)w * h;
-  return (uint32_t)((N + ENC_TILE - 1) / ENC_TILE);
-}
-
 int nice_ctx_reserve(nice_ctx* ctx, uint32_t n_frames, uint32_t w, uint32_t h) {
   return nice::ctx_reserve_impl(ctx, n_frames, w, h, true);
 }
@@ -266,15 +258,19 @@ static uint64_t packed_slot_bytes(uint32_t w, uint32_t h) { return align_up(nice
 int nice::ctx_reserve_impl(nice_ctx* ctx, uint32_t n_frames, uint32_t w, uint32_t h, bool with_packed) {
   if (!ctx) return NICE_E_ARG;
   NICE_HIP(hipSetDevice(ctx->device));
-  EncLayout L = enc_layout(n_frames, tiles_for(w, h), (uint64_t)w * h);
+  EncLayout L = enc_layout(n_frames, enc_tiles(w, h), (uint64_t)w * h);
   int rc = ctx->enc.grow(L.total);
   if (rc == NICE_OK && with_packed) rc = ctx->pack.grow((size_t)n_frames * packed_slot_bytes(w, h));
   return rc;
 }
 
 namespace {
-EncArgs enc_args(const EncLayout& L, uint8_t* base, uint32_t n_frames, uint32_t w, uint32_t h,
-                 uint8_t channels, uint8_t channels_out, uint32_t T, uint64_t N) {
+// The kernel arguments of a plan: scratch pointers from the layout, the plan's
+// launch-dependent fields (tile range, groups, tiles per block, pack slots).
+EncArgs enc_args(const nice_ctx* ctx, const EncLayout& L, uint8_t* base, const EncPlan& p, uint32_t n_frames,
+                 uint32_t w, uint32_t h, uint8_t channels, uint8_t channels_out) {
+  const uint64_t N = (uint64_t)w * h;
+  const uint32_t T = p.tiles_per_frame;
   EncArgs a{};
   a.n_frames = n_frames;
   a.W = w;
@@ -282,148 +278,121 @@ EncArgs enc_args(const EncLayout& L, uint8_t* base, uint32_t n_frames, uint32_t 
   a.C = channels;
   a.channels_out = channels_out;
   a.tiles_per_frame = T;
+  a.tiles_per_block = p.tiles_per_block;
   a.hist = (uint32_t*)(base + L.o_hist);
   a.frame_flags = (uint32_t*)(base + L.o_flags);
   a.tile_first = (uint32_t*)(base + L.o_first);
   a.tile_last = (uint32_t*)(base + L.o_last);
   a.tile_next = (uint32_t*)(base + L.o_next);
-  a.cmask = (uint32_t*)(base + L.o_cmask);
-  a.tbl = (uint32_t*)(base + L.o_tbl);
+  a.cmask = p.flags_out ? (uint32_t*)(base + L.o_cmask) : nullptr;
+  a.cmask_std = p.cmask_std;
   a.tbl_code = (uint32_t*)(base + L.o_tblcode);
   a.tbl_len8 = base + L.o_len8;
   a.stream_max = base + L.o_smax;
   a.seed_bit = (unsigned long long*)(base + L.o_seedbit);
-  a.seed_suf = (uint32_t*)(base + L.o_seedsuf);
-  a.hdr_bytes = (unsigned long long*)(base + L.o_hdrbytes);
-  a.hdr_cache = (uint32_t*)(base + L.o_hdrcache);
-  a.hdr_bitoff = base + L.o_hdrbitoff;
   a.recs = (uint32_t*)(base + L.o_recs);
   a.rec_stride = (N + 3) & ~3ull;
   a.tile_bits = (uint32_t*)(base + L.o_tbits);
   a.packtab = base + L.o_packtab;
   a.pack_ctr = (uint32_t*)(base + L.o_ctr);
-  {   // frames packed at once: <= 64, dividing the frames about evenly
-    const uint32_t per = (n_frames + 63) / 64;
-    a.pack_slots = (n_frames + per - 1) / per;
-  }
+  a.pack_slots = p.pack_slots;
   a.status = (unsigned long long*)(base + L.o_status);
-  a.pack_mode = 0;
-  a.long_only = 1;
   a.tile_off = (unsigned long long*)(base + L.o_toff);
   a.data_end = (unsigned long long*)(base + L.o_dend);
-  a.tile_lo = 0;
-  a.tile_hi = T;
-  a.groups = T ? (T + ENC_GROUP_TILES - 1) / ENC_GROUP_TILES : 1;
+  a.tile_lo = p.tile_lo;
+  a.tile_hi = p.tile_hi;
+  a.groups = p.groups;
   a.gacc = (unsigned long long*)(base + L.o_gacc);
   a.px_lo = 0;
   a.px_hi = (int64_t)N;
   a.band = 0;
   a.over_count = (uint32_t*)(base + L.o_overn);
   a.over_list = (uint2*)(base + L.o_overl);
-  a.pack_cap_bits = (uint32_t)PACK_SUB * ENC_TILE * NICE_PACK_CAP_BPP;
+  a.pack_cap_bits = (uint32_t)PACK_SUB * ENC_TILE * (ctx->test_pack_cap_bpp ? ctx->test_pack_cap_bpp : NICE_PACK_CAP_BPP);
   return a;
 }
-}  // namespace
 
-// enc_classify_strip: rows per block (about three blocks per CU over all
-// frames and strips, >= 16 rows so the 3-row prefill stays small) and the grid
-static uint32_t strip_rows(const nice_ctx* ctx, uint32_t n_frames, uint32_t w, uint32_t rows_total, uint32_t* blocks) {
-  const uint64_t strips = (w + STRIP_W - 1) / STRIP_W;
-  const uint64_t want = 3ull * (uint64_t)ctx->cus;
-  uint64_t r = (rows_total * strips * n_frames + want - 1) / want;
-  if (r < 16) r = 16;
-  if (r > rows_total) r = rows_total ? rows_total : 1;
-  *blocks = (uint32_t)(n_frames * strips * ((rows_total + r - 1) / r));
-  return (uint32_t)r;
+EncOpts enc_opts() {
+  return EncOpts{opt_on(NICE_OPT_ENC_NO_RING), opt_on(NICE_OPT_ENC_NO_PAIR), opt_on(NICE_OPT_ENC_NO_SLIDE)};
 }
 
-// The classify kernel for a frame shape (every kernel writes the same
-// records, histogram and tile edges): the LDS ring (each pixel loaded once)
-// wherever the rows fit it, the strip kernel for wider RGBA rows of whole
-// tiles, per-tile row windows for every other wide shape, and the round-1
-// window kernel for pixel memory that is not 4-byte aligned.  `aligned`: the
-// pixel base (frames: and stride) is 4-byte aligned, as the ring, strip and
-// tile-window loads need.
-// `frames_al16` (frames, not a band; pixel base and frame stride 16-byte
-// aligned): the per-lane sliding-window kernel for RGBA rows that fit the ring.
-enum ClsKind { CLS_K_WINDOW, CLS_K_TINY, CLS_K_RING, CLS_K_RING2, CLS_K_STRIP, CLS_K_PAIR, CLS_K_TWIN, CLS_K_SLIDE };
-static ClsKind pick_classify(uint32_t w, uint8_t channels, bool aligned, bool frames_al16 = false) {
-  if (w < 3) return CLS_K_TINY;
-  if (!aligned || opt_on(NICE_OPT_ENC_NO_RING)) return CLS_K_WINDOW;
-  const bool no_pair = opt_on(NICE_OPT_ENC_NO_PAIR);   // A/B: one tile per iteration
-  if (channels == 4 && w <= CLS_PAIR_MAX_W && frames_al16 && !no_pair && !opt_on(NICE_OPT_ENC_NO_SLIDE))
-    return CLS_K_SLIDE;
-  if (channels == 4 && w <= CLS_PAIR_MAX_W && !no_pair) return CLS_K_PAIR;
-  if (w <= CLS_RING_MAX_W) return CLS_K_RING;
-  if (channels == 4 && w % ENC_TILE == 0) return CLS_K_STRIP;
-  if (w <= CLS_RING2_MAX_W) return CLS_K_RING2;
-  return CLS_K_TWIN;   // per-tile row windows: any wider shape
-}
-// Launches it over `work` tiles (frames x band tiles); rows_total: the rows the
-// strip kernel walks per frame.
-static void launch_classify(nice_ctx* ctx, ClsKind k, EncArgs& a, uint64_t work, uint32_t rows_total,
-                            hipStream_t st) {
-  const bool ringk = k == CLS_K_RING || k == CLS_K_RING2 || k == CLS_K_PAIR || k == CLS_K_SLIDE;
-  // contiguous tile chunks per block: keeps rows-above reuse in L2 and flushes
-  // each block's LDS histogram once per frame; ring kernels: >= 16 tiles per
-  // block (the 3-row prefill amortised), 2 blocks per CU (ring2: 1)
-  uint64_t blocks = (k == CLS_K_RING || k == CLS_K_PAIR || k == CLS_K_SLIDE) ? 2ull * ctx->cus : k == CLS_K_RING2 ? (uint64_t)ctx->cus : 2048;
-  uint64_t per = (work + blocks - 1) / blocks;
-  if (per < (ringk ? 16u : 1u)) per = ringk ? 16 : 1;
-  if (ringk && per > 16384) per = 16384;   // its 16-bit per-thread prefix counters
-  blocks = (work + per - 1) / per;
-  a.tiles_per_block = (uint32_t)per;
-  const bool rgb = a.C == 3;
-  switch (k) {
-    case CLS_K_STRIP: {
-      uint32_t sblocks;
-      a.tiles_per_block = strip_rows(ctx, a.n_frames, a.W, rows_total, &sblocks);
-      hipLaunchKernelGGL(a.cmask ? enc_classify_strip_m : enc_classify_strip, dim3(sblocks), dim3(CLS_THREADS), 0, st, a);
-      break;
-    }
-    case CLS_K_RING:   // (frames: the _m forms, as for the pair kernel below)
-      if (rgb) hipLaunchKernelGGL(a.cmask ? enc_classify_ring3_m : enc_classify_ring3, dim3((uint32_t)blocks),
-                                  dim3(CLS_THREADS), 0, st, a);
-      else hipLaunchKernelGGL(a.cmask ? enc_classify_ring_m : enc_classify_ring, dim3((uint32_t)blocks),
-                              dim3(CLS_THREADS), 0, st, a);
-      break;
-    case CLS_K_PAIR:
-      // frames: coded flags out, run digits by enc_rundigits (below); bands:
-      // run digits in the kernel
-      if (a.cmask) hipLaunchKernelGGL(enc_classify_pair_m, dim3((uint32_t)blocks), dim3(CLS_THREADS), 0, st, a);
-      else hipLaunchKernelGGL(enc_classify_pair, dim3((uint32_t)blocks), dim3(CLS_THREADS), 0, st, a);
-      break;
-    case CLS_K_SLIDE: {   // frames only (coded flags out in ballot order)
-      const dim3 g((uint32_t)blocks), b(CLS_THREADS);
-      switch (a.W & 3u) {
-        case 0: hipLaunchKernelGGL(enc_classify_slide0, g, b, 0, st, a); break;
-        case 1: hipLaunchKernelGGL(enc_classify_slide1, g, b, 0, st, a); break;
-        case 2: hipLaunchKernelGGL(enc_classify_slide2, g, b, 0, st, a); break;
-        default: hipLaunchKernelGGL(enc_classify_slide3, g, b, 0, st, a); break;
-      }
-      break;
-    }
-    case CLS_K_RING2:
-      if (rgb) hipLaunchKernelGGL(a.cmask ? enc_classify_ring2_3_m : enc_classify_ring2_3, dim3((uint32_t)blocks),
-                                  dim3(CLS_THREADS), 0, st, a);
-      else hipLaunchKernelGGL(a.cmask ? enc_classify_ring2_m : enc_classify_ring2, dim3((uint32_t)blocks),
-                              dim3(CLS_THREADS), 0, st, a);
-      break;
-    case CLS_K_TINY:
-      hipLaunchKernelGGL(enc_classify_tiny, dim3((uint32_t)blocks), dim3(256), 0, st, a);
-      break;
-    case CLS_K_TWIN: {
-      const uint64_t tb = 2ull * ctx->cus, tper = (work + tb - 1) / tb;
-      a.tiles_per_block = (uint32_t)tper;
-      const dim3 g((uint32_t)((work + tper - 1) / tper));
-      if (rgb) hipLaunchKernelGGL(a.cmask ? enc_classify_twin3_m : enc_classify_twin3, g, dim3(CLS_THREADS), 0, st, a);
-      else hipLaunchKernelGGL(a.cmask ? enc_classify_twin_m : enc_classify_twin, g, dim3(CLS_THREADS), 0, st, a);
-      break;
-    }
-    default:
-      hipLaunchKernelGGL(enc_classify, dim3((uint32_t)blocks), dim3(256), 0, st, a);
+// The classify kernels: -1 matches either value.  A plan without an entry
+// (there is no RGB strip, pair or slide kernel) is an error, never another kernel.
+struct ClsEntry {
+  ClsKind kind;
+  int rgb, flags_out, wmod4;
+  void (*fn)(EncArgs);
+};
+const ClsEntry kClassify[] = {
+    {CLS_K_WINDOW, -1, -1, -1, enc_classify},
+    {CLS_K_TINY, -1, -1, -1, enc_classify_tiny},
+    {CLS_K_RING, 0, 0, -1, enc_classify_ring},
+    {CLS_K_RING, 0, 1, -1, enc_classify_ring_m},
+    {CLS_K_RING, 1, 0, -1, enc_classify_ring3},
+    {CLS_K_RING, 1, 1, -1, enc_classify_ring3_m},
+    {CLS_K_RING2, 0, 0, -1, enc_classify_ring2},
+    {CLS_K_RING2, 0, 1, -1, enc_classify_ring2_m},
+    {CLS_K_RING2, 1, 0, -1, enc_classify_ring2_3},
+    {CLS_K_RING2, 1, 1, -1, enc_classify_ring2_3_m},
+    {CLS_K_STRIP, 0, 0, -1, enc_classify_strip},
+    {CLS_K_STRIP, 0, 1, -1, enc_classify_strip_m},
+    {CLS_K_PAIR, 0, 0, -1, enc_classify_pair},
+    {CLS_K_PAIR, 0, 1, -1, enc_classify_pair_m},
+    {CLS_K_TWIN, 0, 0, -1, enc_classify_twin},
+    {CLS_K_TWIN, 0, 1, -1, enc_classify_twin_m},
+    {CLS_K_TWIN, 1, 0, -1, enc_classify_twin3},
+    {CLS_K_TWIN, 1, 1, -1, enc_classify_twin3_m},
+    {CLS_K_SLIDE, 0, 1, 0, enc_classify_slide0},   // frames only: coded flags out in ballot order
+    {CLS_K_SLIDE, 0, 1, 1, enc_classify_slide1},
+    {CLS_K_SLIDE, 0, 1, 2, enc_classify_slide2},
+    {CLS_K_SLIDE, 0, 1, 3, enc_classify_slide3},
+};
+
+inline dim3 grid_of(const EncLaunch& l) { return dim3(l.x, l.y); }
+
+// Classify and, for frames, the in-tile run digits from the coded flags.
+int launch_classify(const EncPlan& p, const EncArgs& a, hipStream_t st) {
+  auto is = [](int want, int got) { return want < 0 || want == got; };
+  for (const ClsEntry& e : kClassify) {
+    if (e.kind != p.kind || !is(e.rgb, p.rgb) || !is(e.flags_out, p.flags_out) || !is(e.wmod4, (int)p.wmod4)) continue;
+    hipLaunchKernelGGL(e.fn, grid_of(p.classify), dim3(p.classify.threads), 0, st, a);
+    if (p.rundigits.on())
+      hipLaunchKernelGGL(enc_rundigits, grid_of(p.rundigits), dim3(p.rundigits.threads), 0, st, a, p.il);
+    return NICE_OK;
   }
+  return NICE_E_ARG;
 }
+
+// Runs crossing tile ends: the groups' first coded pixels, then the tail runs.
+void launch_runs(const EncPlan& p, const EncArgs& a, hipStream_t st) {
+  if (p.group_reduce.on())
+    hipLaunchKernelGGL(enc_group_reduce, grid_of(p.group_reduce), dim3(p.group_reduce.threads), 0, st, a, 0);
+  hipLaunchKernelGGL(enc_tailruns, grid_of(p.tailruns), dim3(p.tailruns.threads), 0, st, a);
+}
+
+// Bit placement.  tm: the frames' phase timer, or null (bands).
+void launch_pack(const EncPlan& p, const EncArgs& a, hipStream_t st, PhaseTimer* tm) {
+  auto begin = [&](int phase) { if (tm) tm->begin(phase, st); };
+  auto end = [&]() { if (tm) tm->end(st); };
+  // frames (bands) with codes over 25 bits or composed entries over 32
+  // (FLAG_LONG; the launches return at once for the others): tile bits, their
+  // scan, codes that fit the cache, then the wrapped writes
+  begin(NICE_PH_ENC_LONG);
+  hipLaunchKernelGGL(enc_tilebits, grid_of(p.long_path), dim3(p.long_path.threads), 0, st, a);
+  if (p.group_reduce.on())
+    hipLaunchKernelGGL(enc_group_reduce, grid_of(p.group_reduce), dim3(p.group_reduce.threads), 0, st, a, 1);
+  hipLaunchKernelGGL(enc_tilescan, grid_of(p.tilescan), dim3(p.tilescan.threads), 0, st, a);
+  hipLaunchKernelGGL(enc_pack_long, grid_of(p.long_path), dim3(p.long_path.threads), 0, st, a, 0);
+  hipLaunchKernelGGL(enc_pack_long, grid_of(p.long_path), dim3(p.long_path.threads), 0, st, a, 1);
+  end();
+  // every other frame (band): one pass, group offsets by look-back
+  begin(NICE_PH_ENC_PACK);
+  hipLaunchKernelGGL(enc_pack, grid_of(p.pack), dim3(p.pack.threads), 0, st, a);
+  hipLaunchKernelGGL(enc_pack_over, grid_of(p.pack_over), dim3(p.pack_over.threads), 0, st, a);
+  hipLaunchKernelGGL(enc_edges, grid_of(p.edges), dim3(p.edges.threads), 0, st, a);
+  end();
+}
+}  // namespace
 
 extern "C" {
 
@@ -443,73 +412,53 @@ int nice_encode_batch_dev(nice_ctx* ctx, void* stream, const uint8_t* d_px, uint
   if (N > 0 && frame_stride < N * channels) return NICE_E_ARG;
   NICE_HIP(hipSetDevice(ctx->device));
   hipStream_t st = (hipStream_t)stream;
-  const uint32_t T = tiles_for(w, h);
-  // one frame: its stride is never applied (an odd W*H*3 RGB stride is fine)
-  const bool aligned = ((uintptr_t)d_px & 3) == 0 && (n_frames == 1 || (frame_stride & 3) == 0);
-  const bool al16 = ((uintptr_t)d_px & 15) == 0 && (n_frames == 1 || (frame_stride & 15) == 0);
-  const ClsKind ck = pick_classify(w, channels, aligned, al16);
+  const uint32_t T = enc_tiles(w, h);
   if ((uint64_t)n_frames * T >= (1ull << 32)) return NICE_E_ARG;   // enc_pack's 32-bit work counter
+  EncShape shape{};
+  shape.n_frames = n_frames;
+  shape.w = w;
+  shape.h = h;
+  shape.channels = channels;
+  shape.cus = ctx->cus;
+  // one frame: its stride is never applied (an odd W*H*3 RGB stride is fine)
+  shape.aligned4 = ((uintptr_t)d_px & 3) == 0 && (n_frames == 1 || (frame_stride & 3) == 0);
+  shape.aligned16 = ((uintptr_t)d_px & 15) == 0 && (n_frames == 1 || (frame_stride & 15) == 0);
+  const EncPlan P = plan_encode(shape, enc_opts());
   EncLayout L = enc_layout(n_frames, T, N);
   int rc = ctx->enc.grow(L.total);
   if (rc) return rc;
   uint8_t* base = (uint8_t*)ctx->enc.ptr;
-  EncArgs a = enc_args(L, base, n_frames, w, h, channels, channels_out, T, N);
-  if (ctx->test_pack_cap_bpp) a.pack_cap_bits = (uint32_t)PACK_SUB * ENC_TILE * ctx->test_pack_cap_bpp;
+  EncArgs a = enc_args(ctx, L, base, P, n_frames, w, h, channels, channels_out);
   a.px = d_px;
   a.frame_stride = frame_stride;
   a.out = d_out;
   a.out_stride = out_stride;
   a.out_len = (unsigned long long*)d_out_len;
   NICE_HIP(hipMemsetAsync(base, 0, L.zero_bytes, st));
-  const uint64_t total_tiles = (uint64_t)n_frames * T;
+  PhaseTimer& tm = ctx->timer;
   if (T > 0) {
-    PhaseTimer& tm = ctx->timer;
     tm.begin(NICE_PH_ENC_CLASSIFY, st);
-    launch_classify(ctx, ck, a, total_tiles, h, st);
-    if (ck != CLS_K_WINDOW && ck != CLS_K_TINY)   // in-tile run digits, from the coded flags
-      hipLaunchKernelGGL(enc_rundigits,
-                         dim3(std::min<uint32_t>((T + 7) / 8, std::max<uint32_t>(64u, 2048u / n_frames)), n_frames),
-                         dim3(256), 0, st, a, ck == CLS_K_SLIDE ? 1 : 0);   // (>= 2048 blocks in all for few, large frames)
-    ctx->last_classify = (int)ck;
-    a.cmask_std = (ck != CLS_K_WINDOW && ck != CLS_K_TINY) ? 1u : 0u;   // (enc_pack reads the flags)
+    if ((rc = launch_classify(P, a, st))) return rc;
+    ctx->last_classify = (int)P.kind;
     tm.end(st);
     tm.begin(NICE_PH_ENC_TAILRUNS, st);
-    if (a.groups > 1) hipLaunchKernelGGL(enc_group_reduce, dim3(a.groups, n_frames), dim3(256), 0, st, a, 0);
-    hipLaunchKernelGGL(enc_tailruns, dim3(a.groups, n_frames), dim3(1024), 0, st, a);
+    launch_runs(P, a, st);
     tm.end(st);
   }
-  ctx->timer.begin(NICE_PH_ENC_TABLES, st);
-  hipLaunchKernelGGL(enc_tables, dim3(n_frames * N_STREAMS), dim3(64), 0, st, a);
-  ctx->timer.end(st);
-  ctx->timer.begin(NICE_PH_ENC_HEADER, st);
-  hipLaunchKernelGGL(enc_header, dim3(n_frames), dim3(64), 0, st, a);
-  ctx->timer.end(st);
+  tm.begin(NICE_PH_ENC_TABLES, st);
+  hipLaunchKernelGGL(enc_tables, grid_of(P.tables), dim3(P.tables.threads), 0, st, a);
+  tm.end(st);
+  tm.begin(NICE_PH_ENC_HEADER, st);
+  hipLaunchKernelGGL(enc_header, grid_of(P.header), dim3(P.header.threads), 0, st, a);
+  tm.end(st);
   if (T > 0) {
-    ctx->timer.begin(NICE_PH_ENC_TILEBITS, st);
-    hipLaunchKernelGGL(enc_packtab, dim3(n_frames), dim3(256), 0, st, a);
-    ctx->timer.end(st);
-    // frames with codes over 25 bits or composed entries over 32 (FLAG_LONG;
-    // the launches return at once for the others): tile bits, their scan,
-    // codes that fit the cache, then the wrapped writes
-    const uint32_t tblocks = (uint32_t)(total_tiles < 2048 ? total_tiles : 2048);
-    ctx->timer.begin(NICE_PH_ENC_LONG, st);
-    hipLaunchKernelGGL(enc_tilebits, dim3(tblocks), dim3(256), 0, st, a);
-    if (a.groups > 1) hipLaunchKernelGGL(enc_group_reduce, dim3(a.groups, n_frames), dim3(256), 0, st, a, 1);
-    hipLaunchKernelGGL(enc_tilescan, dim3(a.groups, n_frames), dim3(1024), 0, st, a);
-    hipLaunchKernelGGL(enc_pack_long, dim3(tblocks), dim3(256), 0, st, a, 0);
-    hipLaunchKernelGGL(enc_pack_long, dim3(tblocks), dim3(256), 0, st, a, 1);
-    ctx->timer.end(st);
-    // every other frame: one pass, tile offsets by look-back
-    const uint64_t pblocks = std::min<uint64_t>(total_tiles, (uint64_t)ctx->cus * PACK_BLOCKS_PER_CU);
-    ctx->timer.begin(NICE_PH_ENC_PACK, st);
-    hipLaunchKernelGGL(enc_pack, dim3((uint32_t)pblocks), dim3(256), 0, st, a);
-    hipLaunchKernelGGL(enc_pack_over, dim3(PACK_OVER_BLOCKS), dim3(256), 0, st, a);
-    hipLaunchKernelGGL(enc_edges, dim3(std::min<uint32_t>((T + 255) / 256, 64u), std::min<uint32_t>(n_frames, 4096u)),
-                       dim3(256), 0, st, a);
-    ctx->timer.end(st);
-    ctx->timer.begin(NICE_PH_ENC_TAIL, st);
-    hipLaunchKernelGGL(enc_tail, dim3((n_frames + 63) / 64), dim3(64), 0, st, a);
-    ctx->timer.end(st);
+    tm.begin(NICE_PH_ENC_TILEBITS, st);
+    hipLaunchKernelGGL(enc_packtab, grid_of(P.packtab), dim3(P.packtab.threads), 0, st, a);
+    tm.end(st);
+    launch_pack(P, a, st, &tm);
+    tm.begin(NICE_PH_ENC_TAIL, st);
+    hipLaunchKernelGGL(enc_tail, grid_of(P.tail), dim3(P.tail.threads), 0, st, a);
+    tm.end(st);
   }
   NICE_HIP(hipGetLastError());
   return NICE_OK;
@@ -985,7 +934,7 @@ int nice_tile_grid(uint32_t w, uint32_t h, uint32_t tile_w, uint32_t tile_h, uin
   if (tile_w < 2 || tile_h < 2 || tile_w > 8192 || tile_h > 8192) return NICE_E_ARG;
   const uint64_t gx = ((uint64_t)w + tile_w - 1) / tile_w, gy = ((uint64_t)h + tile_h - 1) / tile_h;
   // the batch encoder's 32-bit work counter: tiles x their 1024-pixel encoder tiles
-  if (gx * gy * tiles_for(tile_w, tile_h) >= (1ull << 32)) return NICE_E_ARG;
+  if (gx * gy * enc_tiles(tile_w, tile_h) >= (1ull << 32)) return NICE_E_ARG;
   *nx = (uint32_t)gx;
   *ny = (uint32_t)gy;
   return NICE_OK;
@@ -1178,7 +1127,7 @@ int nice_band_classify(nice_ctx* ctx, void* stream, const uint8_t* d_px, uint64_
                        uint32_t tile_hi, uint32_t* d_edges) {
   if (!ctx || !d_px || !d_edges || (channels != 3 && channels != 4)) return NICE_E_ARG;
   const uint64_t N = (uint64_t)w * h;
-  const uint32_t T = tiles_for(w, h);
+  const uint32_t T = enc_tiles(w, h);
   if (N == 0 || N > (1ull << 30) || tile_lo >= tile_hi || tile_hi > T) return NICE_E_ARG;
   // pixel memory must hold the band and the 3 rows + 3 pixels its references reach
   const uint64_t band_px0 = (uint64_t)tile_lo * ENC_TILE;
@@ -1192,37 +1141,39 @@ int nice_band_classify(nice_ctx* ctx, void* stream, const uint8_t* d_px, uint64_
   int rc = ctx->band.grow(L.total);
   if (rc) return rc;
   uint8_t* base = (uint8_t*)ctx->band.ptr;
-  EncArgs a = enc_args(L, base, 1, w, h, channels, channels_out, T, N);
-  if (ctx->test_pack_cap_bpp) a.pack_cap_bits = (uint32_t)PACK_SUB * ENC_TILE * ctx->test_pack_cap_bpp;
-  a.cmask = nullptr;   // band tiles: the pair kernel counts its run digits itself
-  // virtual bases: global pixel index g addresses d_px + (g - px0) * channels,
-  // band records are stored from the band's first pixel
-  a.px = d_px - (int64_t)px0 * channels;
+  // virtual base: global pixel index g addresses d_px + (g - px0) * channels
+  const uint8_t* vpx = d_px - (int64_t)px0 * channels;
+  EncShape shape{};
+  shape.n_frames = 1;
+  shape.w = w;
+  shape.h = h;
+  shape.channels = channels;
+  shape.cus = ctx->cus;
+  // the ring / strip kernels read the band's pixels through the virtual base
+  // as 32-bit words: it must be 4-byte aligned
+  shape.aligned4 = ((uintptr_t)vpx & 3) == 0;
+  shape.aligned16 = ((uintptr_t)vpx & 15) == 0;
+  shape.band = true;
+  shape.tile_lo = tile_lo;
+  shape.tile_hi = tile_hi;
+  const EncPlan P = plan_encode(shape, enc_opts());
+  // one-pass packer with look-back from band_bit0; FLAG_LONG bands take the
+  // long-code path (tile bits, their scan) like frames
+  EncArgs a = enc_args(ctx, L, base, P, 1, w, h, channels, channels_out);
+  a.px = vpx;
   a.frame_stride = 0;
-  a.recs = (uint32_t*)(base + L.o_recs) - band_px0;
-  a.tile_lo = tile_lo;
-  a.tile_hi = tile_hi;
-  a.groups = (tile_hi - tile_lo + ENC_GROUP_TILES - 1) / ENC_GROUP_TILES;
+  a.recs = (uint32_t*)(base + L.o_recs) - band_px0;   // band records are stored from the band's first pixel
   a.px_lo = (int64_t)px0;
   a.px_hi = (int64_t)(px0 + px_count);
   a.band = 1;
-  // one-pass packer with look-back from band_bit0; FLAG_LONG bands take the
-  // long-code path (tile bits, their scan) like frames
-  a.pack_mode = 0;
-  a.long_only = 1;
   NICE_HIP(hipMemsetAsync(base, 0, L.zero_bytes, st));
-  // the ring / strip kernels read the band's pixels through the virtual base
-  // as 32-bit words: it must be 4-byte aligned
-  const ClsKind ck = pick_classify(w, channels, ((uintptr_t)a.px & 3) == 0);
-  // strip kernel: the band's rows (tiles outside the band are staged, not classified)
-  const uint32_t tpr = std::max<uint32_t>(w / ENC_TILE, 1u);
-  const uint32_t rows_band = (tile_hi + tpr - 1) / tpr - tile_lo / tpr;
-  launch_classify(ctx, ck, a, tile_hi - tile_lo, rows_band, st);
-  ctx->last_classify = (int)ck;
-  hipLaunchKernelGGL(enc_band_edges, dim3(1), dim3(256), 0, st, a, d_edges);
+  if ((rc = launch_classify(P, a, st))) return rc;
+  ctx->last_classify = (int)P.kind;
+  hipLaunchKernelGGL(enc_band_edges, dim3(1), dim3(BAND_THREADS), 0, st, a, d_edges);
   NICE_HIP(hipGetLastError());
   ctx->bs = BandState{};
   ctx->bs.a = a;
+  ctx->bs.plan = P;
   ctx->bs.bhist = (uint32_t*)(base + L.o_bhist);
   ctx->bs.classified = true;
   return NICE_OK;
@@ -1236,8 +1187,7 @@ static int band_runs(nice_ctx* ctx, void* stream, uint32_t band_next, const uint
   EncArgs& a = ctx->bs.a;
   a.band_next = band_next;
   a.band_next_dev = d_band_next;
-  if (a.groups > 1) hipLaunchKernelGGL(enc_group_reduce, dim3(a.groups, 1), dim3(256), 0, st, a, 0);
-  hipLaunchKernelGGL(enc_tailruns, dim3(a.groups, 1), dim3(1024), 0, st, a);
+  launch_runs(ctx->bs.plan, a, st);
   a.band_next_dev = nullptr;
   NICE_HIP(hipMemcpyAsync(ctx->bs.bhist, a.hist, N_BINS * 4, hipMemcpyDeviceToDevice, st));
   NICE_HIP(hipMemcpyAsync(d_hist, a.hist, N_BINS * 4, hipMemcpyDeviceToDevice, st));
@@ -1259,14 +1209,15 @@ int nice_band_runs_dev(nice_ctx* ctx, void* stream, const uint32_t* d_band_next,
 static int band_tables(nice_ctx* ctx, hipStream_t st, const uint32_t* d_hist_total, unsigned long long* d_info) {
   EncArgs& a = ctx->bs.a;
   NICE_HIP(hipMemcpyAsync(a.hist, d_hist_total, N_BINS * 4, hipMemcpyDeviceToDevice, st));
-  hipLaunchKernelGGL(enc_tables, dim3(N_STREAMS), dim3(64), 0, st, a);
+  const EncPlan& P = ctx->bs.plan;
+  hipLaunchKernelGGL(enc_tables, grid_of(P.tables), dim3(P.tables.threads), 0, st, a);
   EncArgs h = a;   // the header goes to the context's header buffer
   h.out = (uint8_t*)ctx->band_hdr.ptr;
   h.out_stride = 4096;
   h.out_len = (unsigned long long*)((uint8_t*)ctx->band_hdr.ptr + 4096);
-  hipLaunchKernelGGL(enc_header, dim3(1), dim3(64), 0, st, h);
-  hipLaunchKernelGGL(enc_packtab, dim3(1), dim3(256), 0, st, a);
-  hipLaunchKernelGGL(enc_band_sum, dim3(1), dim3(256), 0, st, a, (const uint32_t*)ctx->bs.bhist, d_info);
+  hipLaunchKernelGGL(enc_header, grid_of(P.header), dim3(P.header.threads), 0, st, h);
+  hipLaunchKernelGGL(enc_packtab, grid_of(P.packtab), dim3(P.packtab.threads), 0, st, a);
+  hipLaunchKernelGGL(enc_band_sum, dim3(1), dim3(BAND_THREADS), 0, st, a, (const uint32_t*)ctx->bs.bhist, d_info);
   NICE_HIP(hipGetLastError());
   return NICE_OK;
 }
@@ -1339,7 +1290,8 @@ int nice_band_pack_bits(nice_ctx* ctx, void* stream, uint64_t band_bit0, uint64_
   // pack kernels skip the band and the trailer carries BAND_FIX_BAD, which
   // nice_band_assemble reports
   if (ctx->bs.d_info)
-    hipLaunchKernelGGL(enc_band_check, dim3(1), dim3(64), 0, st, a, ctx->bs.d_info, (unsigned long long)band_bits);
+    hipLaunchKernelGGL(enc_band_check, dim3(1), dim3(ENC_WAVE_THREADS), 0, st, a, ctx->bs.d_info,
+                       (unsigned long long)band_bits);
   if (band_bits == 0) {   // no data words: the trailer only
     NICE_HIP(hipGetLastError());
     return NICE_OK;
@@ -1351,19 +1303,8 @@ int nice_band_pack_bits(nice_ctx* ctx, void* stream, uint64_t band_bit0, uint64_
   NICE_HIP(hipMemsetAsync(a.status, 0, (size_t)ng * 8, st));
   NICE_HIP(hipMemsetAsync(a.pack_ctr, 0, 4, st));
   NICE_HIP(hipMemsetAsync(a.over_count, 0, 4, st));
-  // FLAG_LONG (the launches return at once otherwise): tile bits, their scan from
-  // band_bit0, the codes that fit the cache, then the wrapped writes
-  const uint32_t tblocks = std::min<uint32_t>(nt, 2048u);
-  hipLaunchKernelGGL(enc_tilebits, dim3(tblocks), dim3(256), 0, st, a);
-  if (a.groups > 1) hipLaunchKernelGGL(enc_group_reduce, dim3(a.groups, 1), dim3(256), 0, st, a, 1);
-  hipLaunchKernelGGL(enc_tilescan, dim3(a.groups, 1), dim3(1024), 0, st, a);
-  hipLaunchKernelGGL(enc_pack_long, dim3(tblocks), dim3(256), 0, st, a, 0);
-  hipLaunchKernelGGL(enc_pack_long, dim3(tblocks), dim3(256), 0, st, a, 1);
-  // every other band: one pass, group offsets by look-back from band_bit0
-  hipLaunchKernelGGL(enc_pack, dim3((uint32_t)std::min<uint64_t>(nt, (uint64_t)ctx->cus * PACK_BLOCKS_PER_CU)),
-                     dim3(256), 0, st, a);
-  hipLaunchKernelGGL(enc_pack_over, dim3(PACK_OVER_BLOCKS), dim3(256), 0, st, a);
-  hipLaunchKernelGGL(enc_edges, dim3(std::min<uint32_t>((ng + 255) / 256, 64u), 1), dim3(256), 0, st, a);
+  // the scan and the look-back start from band_bit0
+  launch_pack(ctx->bs.plan, a, st, nullptr);
   NICE_HIP(hipGetLastError());
   return NICE_OK;
 }
@@ -1411,9 +1352,9 @@ int nice_band_assemble(nice_ctx* ctx, void* stream, const uint32_t* d_words, con
   {
     uint64_t most = 0;
     for (uint32_t r = 0; r < n_bands; ++r) most = std::max<uint64_t>(most, meta[n_bands + r + 1] - meta[n_bands + r]);
-    hipLaunchKernelGGL(enc_band_merge, dim3((uint32_t)((most + 4095) / 4096), n_bands), dim3(256), 0, st,
+    hipLaunchKernelGGL(enc_band_merge, dim3((uint32_t)((most + 4095) / 4096), n_bands), dim3(BAND_THREADS), 0, st,
                        (uint32_t*)d_out, d_words, dmeta, dmeta + n_bands, n_bands);
-    hipLaunchKernelGGL(enc_band_fix, dim3(1), dim3(64), 0, st, d_out, d_words, dmeta + 2 * n_bands + 3,
+    hipLaunchKernelGGL(enc_band_fix, dim3(1), dim3(ENC_WAVE_THREADS), 0, st, d_out, d_words, dmeta + 2 * n_bands + 3,
                        dmeta + n_bands, n_bands, dmeta + 3 * n_bands + 3);
   }
   EncArgs a = ctx->bs.a;
@@ -1422,7 +1363,7 @@ int nice_band_assemble(nice_ctx* ctx, void* stream, const uint32_t* d_words, con
   a.n_frames = 1;
   a.data_end = dmeta + 2 * n_bands + 1;
   a.out_len = dmeta + 2 * n_bands + 2;
-  hipLaunchKernelGGL(enc_tail, dim3(1), dim3(64), 0, st, a);
+  hipLaunchKernelGGL(enc_tail, grid_of(ctx->bs.plan.tail), dim3(ctx->bs.plan.tail.threads), 0, st, a);
   unsigned long long bad = 0;
   NICE_HIP(hipMemcpyAsync(&bad, dmeta + 3 * n_bands + 3, 8, hipMemcpyDeviceToHost, st));
   NICE_HIP(hipStreamSynchronize(st));   // `meta` lives on this stack frame
@@ -1472,7 +1413,7 @@ int nice_test_code_lengths(const uint32_t* counts, int n_vec, int n, uint8_t* ao
   int rc = NICE_OK;
   if (hipMemcpy(dc, counts, cb, hipMemcpyHostToDevice) != hipSuccess) rc = NICE_E_HIP;
   if (!rc) {
-    hipLaunchKernelGGL(enc_code_lengths_test, dim3(n_vec), dim3(64), 0, 0, (const uint32_t*)dc, n, (uint8_t*)da);
+    hipLaunchKernelGGL(enc_code_lengths_test, dim3(n_vec), dim3(ENC_WAVE_THREADS), 0, 0, (const uint32_t*)dc, n, (uint8_t*)da);
     if (hipGetLastError() != hipSuccess || hipMemcpy(aob, da, ab, hipMemcpyDeviceToHost) != hipSuccess)
       rc = NICE_E_HIP;
   }

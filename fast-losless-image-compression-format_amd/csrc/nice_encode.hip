@@ -33,7 +33,7 @@
 
 namespace nice {
 
-constexpr int ENC_THREADS = 256;
+// (ENC_TILE, ENC_THREADS and every other block size: nice_geom.h)
 constexpr int PX_PER_THREAD = ENC_TILE / ENC_THREADS;  // 4
 constexpr int WIN = ENC_TILE + 6;
 constexpr uint32_t NONE = 0xFFFFFFFFu;
@@ -471,9 +471,8 @@ __global__ __launch_bounds__(ENC_THREADS) void enc_classify_tiny(EncArgs a) { en
 //  * the five mode-prefix counts are accumulated per thread in packed
 //    registers and added to the histogram once per frame.
 // ---------------------------------------------------------------------------
-// (CLS_THREADS: nice_geom.h)
+// (CLS_THREADS, CLS_RING: nice_geom.h)
 constexpr int CLS_PPT = ENC_TILE / CLS_THREADS;   // 2 pixels per thread
-constexpr int CLS_RING = 16384;                   // ring words (64 KB)
 // words 0..CLS_GUARD-1 of the ring mirrored past its end: a neighbour group
 // (pixels b .. b+6 for b = ((s - rows*W - 3) mod CLS_RING) + tid, s the
 // wave-uniform part of the pixel index) is one base address plus immediate
@@ -1494,7 +1493,7 @@ __global__ __launch_bounds__(CLS_THREADS, 2) void enc_classify_slide3(EncArgs a)
 // of a tile: words 8w + 2q + h = half h of the ballot of its lanes' q-th
 // pixels, pixel 256w + 4 lane + q), transposed here: standard word k holds
 // byte k % 8 of each ballot q, bit m at 4m + q.
-__global__ __launch_bounds__(256) void enc_rundigits(EncArgs a, int il) {
+__global__ __launch_bounds__(RUNDIGITS_THREADS) void enc_rundigits(EncArgs a, int il) {
   __shared__ uint32_t bins[8];
   if (threadIdx.x < 8) bins[threadIdx.x] = 0;
   __syncthreads();
@@ -1955,10 +1954,10 @@ __global__ __launch_bounds__(CLS_THREADS) void enc_classify_strip_m(EncArgs a) {
 // tile_next[t] = first coded pixel after tile t (N if none).
 // ---------------------------------------------------------------------------
 // Aggregate of each group of ENC_GROUP_TILES tiles (grid: groups x frames).
-__global__ __launch_bounds__(256) void enc_group_reduce(EncArgs a, int what) {
+__global__ __launch_bounds__(GROUP_THREADS) void enc_group_reduce(EncArgs a, int what) {
   __shared__ unsigned long long part[4];
   const uint32_t g = blockIdx.x, f = blockIdx.y;
-  if (what == 1 && a.long_only && !(a.frame_flags[f] & FLAG_LONG)) return;   // bit totals: long path only
+  if (what == 1 && !(a.frame_flags[f] & FLAG_LONG)) return;   // bit totals: long path only
   const uint32_t nt = a.tile_hi - a.tile_lo;
   const uint32_t t0 = g * ENC_GROUP_TILES, t1 = min(t0 + ENC_GROUP_TILES, nt);
   const uint64_t base = (uint64_t)f * a.tiles_per_frame + a.tile_lo;
@@ -1980,7 +1979,6 @@ __global__ __launch_bounds__(256) void enc_group_reduce(EncArgs a, int what) {
   }
 }
 
-constexpr int TR_THREADS = 1024;
 __global__ __launch_bounds__(TR_THREADS) void enc_tailruns(EncArgs a) {
   __shared__ uint32_t chunk_min[TR_THREADS];
   __shared__ uint32_t digits[8];   // run-digit counts, added to the histogram once
@@ -2042,7 +2040,7 @@ __global__ __launch_bounds__(TR_THREADS) void enc_tailruns(EncArgs a) {
 // table entry: code in bits [5, 31), length in bits [0, 5) when length <= 25;
 // the full u8 length is also kept for the header (len8).
 // ---------------------------------------------------------------------------
-__global__ __launch_bounds__(64) void enc_tables(EncArgs a) {
+__global__ __launch_bounds__(ENC_WAVE_THREADS) void enc_tables(EncArgs a) {
   __shared__ HeapLds h;
   __shared__ uint32_t counts[MAX_ALPHABET];
   // stream-major, largest alphabets first (343, 256, 64, 64, 32 x 3, 13, 11,
@@ -2188,7 +2186,6 @@ __global__ __launch_bounds__(64) void enc_tables(EncArgs a) {
       const uint64_t e = (uint64_t)f * N_BINS + sb + i;
       a.tbl_len8[e] = (uint8_t)av;
       a.tbl_code[e] = (uint32_t)code;
-      a.tbl[e] = (av <= FAST_MAX_CODE_BITS) ? (uint32_t)((code << 5) | av) : 0u;
     }
   }
   // wave max
@@ -2212,7 +2209,7 @@ __global__ __launch_bounds__(64) void enc_tables(EncArgs a) {
 
 // Test hook (nice_test_code_lengths): code lengths of n_vec count vectors of
 // n symbols, one wave each, through the same heap replay as enc_tables.
-__global__ __launch_bounds__(64) void enc_code_lengths_test(const uint32_t* counts, int n, uint8_t* aob) {
+__global__ __launch_bounds__(ENC_WAVE_THREADS) void enc_code_lengths_test(const uint32_t* counts, int n, uint8_t* aob) {
   __shared__ HeapLds h;
   __shared__ uint32_t c[MAX_ALPHABET];
   const uint32_t v = blockIdx.x;
@@ -2268,9 +2265,9 @@ __device__ __forceinline__ uint8_t field_bits(uint8_t max_aob) {
 
 // ---------------------------------------------------------------------------
 // K4: headers. One wave per frame. Writes bytes [0, 4*floor(data_start/32)) and
-// the frame's seed (data start bit, last 32 bits before it).
+// the frame's data start bit.
 // ---------------------------------------------------------------------------
-__global__ __launch_bounds__(64) void enc_header(EncArgs a) {
+__global__ __launch_bounds__(ENC_WAVE_THREADS) void enc_header(EncArgs a) {
   __shared__ uint32_t words[200];   // 6160 bits = 192.5 words in the normal layout
   const uint32_t f = blockIdx.x;
   const int lane = threadIdx.x;
@@ -2317,13 +2314,7 @@ __global__ __launch_bounds__(64) void enc_header(EncArgs a) {
     const uint32_t nwords = (pos + 31) >> 5;
     for (int w = lane; w < (int)nwords; w += 64)
       reinterpret_cast<uint32_t*>(out)[w] = __builtin_bswap32(words[w]);
-    if (lane == 0) {
-      a.seed_bit[f] = pos;
-      // last 32 bits before pos: bits [pos-32, pos)
-      const uint32_t o = pos & 31;
-      const uint32_t hi = words[(pos >> 5) - 1], lo = words[pos >> 5];
-      a.seed_suf[f] = o ? ((hi << o) | (lo >> (32 - o))) : hi;
-    }
+    if (lane == 0) a.seed_bit[f] = pos;
     return;
   }
   if (lane != 0) return;
@@ -2340,17 +2331,8 @@ __global__ __launch_bounds__(64) void enc_header(EncArgs a) {
     for (int i = 0; i < stream_size(s); ++i)
       bw.write_8bits(fb, a.tbl_len8[(uint64_t)f * N_BINS + stream_base(s) + i]);
   }
-  a.hdr_bytes[f] = bw.pos;
-  a.hdr_cache[f] = bw.cache;
-  a.hdr_bitoff[f] = bw.bit_offset;
   const uint64_t pos = bw.pos * 8 + bw.bit_offset;
   a.seed_bit[f] = pos;
-  // last 32 bits before pos
-  uint64_t acc = 0;
-  for (int k = 4; k >= 1; --k) acc = (acc << 8) | (bw.pos >= (uint64_t)k ? out[bw.pos - k] : 0);
-  uint32_t suf = (uint32_t)acc;
-  if (bw.bit_offset) suf = (suf << bw.bit_offset) | (bw.cache >> (32 - bw.bit_offset));
-  a.seed_suf[f] = suf;
   if (N > 0) {
     // pending bits (top bit_offset bits of the cache), then zeros to the end of
     // the word holding the data start: the first data tile ORs into it
@@ -2380,10 +2362,10 @@ __global__ __launch_bounds__(64) void enc_header(EncArgs a) {
 //   enc_pack      per tile, one pass: the pixels' codes from three lookups
 //                 each, a block scan of their lengths, the tile's stream
 //                 offset by a decoupled look-back over the preceding tiles'
-//                 status words (pack_mode 0; bands: from enc_tilescan,
-//                 pack_mode 1), codes MSB-first into an LDS bit buffer
+//                 status words (frames: from the data start; bands: from
+//                 band_bit0), codes MSB-first into an LDS bit buffer
 //                 (bitwriter.rs:55-73), then shifted to the offset and stored
-//   enc_edges     ORs each tile's first partial word into the word the tile
+//   enc_edges     ORs each group's first partial word into the word the group
 //                 before it (or the header) wrote
 //   enc_tail      per frame: [P, P, 0, 0, 0] after the data (hfe.rs:115,
 //                 code.rs:421-422) and the stream length
@@ -2396,7 +2378,6 @@ __global__ __launch_bounds__(64) void enc_header(EncArgs a) {
 // (denser groups go to enc_pack_over)
 constexpr int PACK_CAP_BITS = PACK_SUB * ENC_TILE * NICE_PACK_CAP_BPP;
 constexpr int PACK_MAX_WORDS = PACK_CAP_BITS / 32 + 2;
-constexpr int PK_THREADS = 256;
 
 struct TileQuad {
   uint32_t rc[4];
@@ -2483,16 +2464,16 @@ __device__ __forceinline__ void tile_range(const EncArgs& a, uint64_t& w0, uint6
   w1 = w0 + per < total ? w0 + per : total;
 }
 
-// frames the long-code path handles: all (bands), or those with FLAG_LONG
+// frames (bands) the long-code path handles: those with FLAG_LONG
 __device__ __forceinline__ bool long_path(const EncArgs& a, uint32_t f) {
-  return (!a.long_only || (a.frame_flags[f] & FLAG_LONG)) && !(a.frame_flags[f] & FLAG_BAD);
+  return (a.frame_flags[f] & FLAG_LONG) && !(a.frame_flags[f] & FLAG_BAD);
 }
 
 __global__ __launch_bounds__(ENC_THREADS) void enc_tilebits(EncArgs a) {
   __shared__ uint32_t tbl[N_BINS];
   __shared__ uint32_t mask[ENC_TILE / 32];
   __shared__ uint32_t wsum[ENC_THREADS / 64];
-  if (a.long_only && !(a.frame_flags[a.n_frames] & FLAG_LONG)) return;   // no long-code frame in the batch
+  if (!(a.frame_flags[a.n_frames] & FLAG_LONG)) return;   // no long-code frame in the batch
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const int64_t N = (int64_t)a.W * a.H;
   const int p0 = 4 * threadIdx.x;
@@ -2525,7 +2506,7 @@ __global__ __launch_bounds__(ENC_THREADS) void enc_tilebits(EncArgs a) {
 // One 1024-thread block per frame.
 // block (group g, frame f): tiles [g, g + 1) x ENC_GROUP_TILES of the band,
 // from the bits of the earlier groups on
-__global__ __launch_bounds__(1024) void enc_tilescan(EncArgs a) {
+__global__ __launch_bounds__(SCAN_THREADS) void enc_tilescan(EncArgs a) {
   __shared__ unsigned long long part[1024];
   const uint32_t g = blockIdx.x, f = blockIdx.y;
   if (!long_path(a, f)) return;
@@ -2571,7 +2552,7 @@ __global__ __launch_bounds__(1024) void enc_tilescan(EncArgs a) {
 // of its symbols in emission order; entries whose symbols all occur in the
 // frame must fit 32 bits with every code <= FAST_MAX_CODE_BITS, else the frame
 // is FLAG_LONG (entries of absent symbols are never looked up).
-__global__ __launch_bounds__(256) void enc_packtab(EncArgs a) {
+__global__ __launch_bounds__(PACKTAB_THREADS) void enc_packtab(EncArgs a) {
   __shared__ uint32_t code[N_BINS];
   __shared__ uint8_t len[N_BINS], pres[N_BINS];
   __shared__ uint32_t s_long;
@@ -2638,7 +2619,7 @@ __global__ __launch_bounds__(256) void enc_packtab(EncArgs a) {
   }
 }
 
-// Tile status words of the decoupled look-back (pack_mode 0): the tile's bit
+// Tile status words of the decoupled look-back: the tile's bit
 // count (ST_AGG) as soon as it is known, then its absolute end bit (ST_INCL).
 constexpr unsigned long long ST_AGG = 1ull << 62, ST_INCL = 2ull << 62, ST_VAL = (1ull << 62) - 1;
 __device__ __forceinline__ void st_store(unsigned long long* p, unsigned long long v) {
@@ -3018,7 +2999,6 @@ __global__ __launch_bounds__(PK_THREADS, PACK_BLOCKS_PER_CU) void enc_pack(EncAr
   const uint32_t nt = a.tile_hi - a.tile_lo;
   const uint32_t ng = (nt + PACK_SUB - 1) / PACK_SUB;   // groups per frame
   const uint32_t T = a.tiles_per_frame;
-  const bool lookback_mode = a.pack_mode == 0;
   const uint32_t I = a.pack_slots, slot = blockIdx.x % a.pack_slots;
   uint32_t cf = NONE, ck = 0, seq = 0;   // wave 0's work cursor
 #ifdef NICE_PACK_PROF
@@ -3074,14 +3054,14 @@ __global__ __launch_bounds__(PK_THREADS, PACK_BLOCKS_PER_CU) void enc_pack(EncAr
 #ifndef NICE_PACK_LATE_AGG
     // the group's count goes out before the puts: the look-backs of the
     // groups after it wait on it (a look-back was ~40 % of a group's time)
-    const bool agg_out = lookback_mode && g > 0;
+    const bool agg_out = g > 0;
     if (agg_out && tid == 0) st_store(&a.status[f * ng + g], ST_AGG | gbits);
 #else
     const bool agg_out = false;
 #endif
     if (!over && mine && P.nb) lane_emit(tab, P, bits, wbase + x - P.nb);
     PROF_MARK(2);
-    if (wid == 0 && lookback_mode) {
+    if (wid == 0) {
       // the look-back first: the groups behind wait on its published prefix
       // (pack 8.12 -> 8.04 ms per 512 frames, profiles/r06zg_ab_prio.log)
       __builtin_amdgcn_s_setprio(3);
@@ -3093,7 +3073,7 @@ __global__ __launch_bounds__(PK_THREADS, PACK_BLOCKS_PER_CU) void enc_pack(EncAr
     __syncthreads();
     PROF_MARK(3);
     // place the group's bits at its stream offset
-    const unsigned long long s0 = lookback_mode ? s_off : a.tile_off[t0], e0 = s0 + gbits;
+    const unsigned long long s0 = s_off, e0 = s0 + gbits;
     const uint32_t sh = (uint32_t)(s0 & 31);
     const uint64_t w0 = s0 >> 5;
     const uint32_t nw = gbits ? (uint32_t)(((e0 + 31) >> 5) - w0) : 0u;
@@ -3103,24 +3083,18 @@ __global__ __launch_bounds__(PK_THREADS, PACK_BLOCKS_PER_CU) void enc_pack(EncAr
         const uint32_t hi = m ? bits[m - 1] : 0u;
         const uint32_t lo = bits[m];   // zero past the group's bits
         const uint32_t v = sh ? (uint32_t)((((uint64_t)hi << 32) | lo) >> sh) : lo;
-        if (lookback_mode) {
-          // a word is stored by the group holding its first bit (zeros past
-          // the group's end); this group's bits in the word holding its
-          // start go to enc_edges
-          if (m == 0 && sh) a.tile_bits[t0] = v;
-          else out32[w0 + m] = __builtin_bswap32(v);
-        } else {   // every partial word was zeroed by enc_tilescan
-          const bool shared = (m == 0 && sh) || (m == nw - 1 && (e0 & 31));
-          if (shared) atomicOr(&out32[w0 + m], __builtin_bswap32(v));
-          else out32[w0 + m] = __builtin_bswap32(v);
-        }
+        // a word is stored by the group holding its first bit (zeros past
+        // the group's end); this group's bits in the word holding its
+        // start go to enc_edges
+        if (m == 0 && sh) a.tile_bits[t0] = v;
+        else out32[w0 + m] = __builtin_bswap32(v);
       }
     } else if (tid == 0) {
       // over the LDS buffer: listed for enc_pack_over (after this kernel, before enc_edges)
       const uint32_t k = atomicAdd(a.over_count, 1u);
       a.over_list[k] = make_uint2(f * ng + g, gbits);
     }
-    if (lookback_mode && tid == 0) {
+    if (tid == 0) {
       a.tile_off[t0] = s0;
       if (over || !(nw && sh)) a.tile_bits[t0] = 0u;
       if (tt0 + nsub == T) a.data_end[f] = e0;
@@ -3172,7 +3146,6 @@ __global__ __launch_bounds__(PK_THREADS) void enc_pack_over(EncArgs a) {
   const uint32_t T = a.tiles_per_frame;
   const int64_t N = (int64_t)a.W * a.H;
   const int p0 = 4 * tid;
-  const bool lookback_mode = a.pack_mode == 0;
   uint32_t rc[4];
   for (uint32_t item = blockIdx.x; item < n_over; item += gridDim.x) {
     const uint2 it = a.over_list[item];
@@ -3190,17 +3163,16 @@ __global__ __launch_bounds__(PK_THREADS) void enc_pack_over(EncArgs a) {
     const uint32_t sh = (uint32_t)(s0 & 31);
     const uint64_t w0 = s0 >> 5;
     uint32_t* out32 = reinterpret_cast<uint32_t*>(a.out + (uint64_t)f * a.out_stride);
-      // zero the words only this group writes (look-back: every word whose
-      // first bit is the group's; bands: the interior ones, enc_tilescan
-      // zeroed the partial ones), then OR each code into place, tile by tile
-      const uint64_t z0 = (s0 + 31) >> 5, z1 = lookback_mode ? (e0 + 31) >> 5 : e0 >> 5;
+      // zero the words only this group writes (every word whose first bit is
+      // the group's), then OR each code into place, tile by tile
+      const uint64_t z0 = (s0 + 31) >> 5, z1 = (e0 + 31) >> 5;
       for (uint64_t m = z0 + tid; m < z1; m += PK_THREADS) out32[m] = 0u;
-      if (lookback_mode && tid == 0) a.tile_bits[t0] = 0u;
+      if (tid == 0) a.tile_bits[t0] = 0u;
       __threadfence();
       __syncthreads();
       auto or_word = [&](uint64_t wd, uint32_t v) {
         if (!v) return;
-        if (lookback_mode && sh && wd == w0) atomicOr(&a.tile_bits[t0], v);
+        if (sh && wd == w0) atomicOr(&a.tile_bits[t0], v);
         else atomicOr(&out32[wd], __builtin_bswap32(v));
       };
       unsigned long long run = s0;
@@ -3242,9 +3214,10 @@ __global__ __launch_bounds__(PK_THREADS) void enc_pack_over(EncArgs a) {
   }
 }
 
-// Each group's bits in the word holding its first bit (pack_mode 0), OR-ed
-// into that word once every group has stored its own words.
-__global__ __launch_bounds__(256) void enc_edges(EncArgs a) {
+// Each group's bits in the word holding its first bit (enc_pack and
+// enc_pack_over leave them in tile_bits at the group's first tile), OR-ed into
+// that word once every group has stored its own words.
+__global__ __launch_bounds__(EDGES_THREADS) void enc_edges(EncArgs a) {
   const uint32_t T = a.tiles_per_frame;
   const uint32_t ng = (a.tile_hi - a.tile_lo + PACK_SUB - 1) / PACK_SUB;   // groups of the frame (band)
   for (uint32_t f = blockIdx.y; f < a.n_frames; f += gridDim.y) {
@@ -3258,7 +3231,7 @@ __global__ __launch_bounds__(256) void enc_edges(EncArgs a) {
   }
 }
 
-__global__ __launch_bounds__(64) void enc_tail(EncArgs a) {
+__global__ __launch_bounds__(ENC_WAVE_THREADS) void enc_tail(EncArgs a) {
   const uint32_t f = blockIdx.x * 64 + threadIdx.x;
   if (f >= a.n_frames) return;
   if ((uint64_t)a.W * a.H == 0) return;
@@ -3416,7 +3389,7 @@ namespace nice {
 // band_w0[r]: first stream word of band r; band_off[r]: its first word in the
 // concatenated array; band_off[R]: total words.
 // ---------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void enc_band_merge(uint32_t* out32, const uint32_t* words,
+__global__ __launch_bounds__(BAND_THREADS) void enc_band_merge(uint32_t* out32, const uint32_t* words,
                                                       const unsigned long long* band_w0,
                                                       const unsigned long long* band_off, uint32_t R) {
   const uint32_t r = blockIdx.y;
@@ -3463,7 +3436,7 @@ namespace nice {
 
 // Band helpers: first/last coded pixel of the band (over tiles [tile_lo,
 // tile_hi) of frame 0), and the band's total data bits.
-__global__ __launch_bounds__(256) void enc_band_edges(EncArgs a, uint32_t* edges) {
+__global__ __launch_bounds__(BAND_THREADS) void enc_band_edges(EncArgs a, uint32_t* edges) {
   __shared__ uint32_t s_first, s_last;
   if (threadIdx.x == 0) { s_first = NONE; s_last = 0; }
   __syncthreads();
@@ -3496,7 +3469,7 @@ __global__ void enc_band_check(EncArgs a, const unsigned long long* info, unsign
   }
 }
 
-__global__ __launch_bounds__(256) void enc_band_sum(EncArgs a, const uint32_t* bhist, unsigned long long* info) {
+__global__ __launch_bounds__(BAND_THREADS) void enc_band_sum(EncArgs a, const uint32_t* bhist, unsigned long long* info) {
   __shared__ unsigned long long s_bits;
   __shared__ uint32_t s_mode[5];
   if (threadIdx.x == 0) s_bits = 0;

@@ -1,6 +1,7 @@
 // nice_geom.h -- the one definition of every constant and LDS layout that both
-// a kernel and the host's launch planning (nice_dec_plan.hpp, nice_capi.hip)
-// depend on.  No HIP: a plain C++ compiler reads it too (tests/test_dec_plan.py).
+// a kernel and the host's launch planning (nice_enc_plan.hpp, nice_dec_plan.hpp,
+// nice_capi.hip) depend on.  No HIP: a plain C++ compiler reads it too
+// (tests/test_enc_plan.py, tests/test_dec_plan.py).
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -20,8 +21,45 @@ constexpr uint32_t LDS_BUDGET = 160 * 1024, LDS_OPT_IN = 64 * 1024;
 NICE_HD constexpr bool lds_fits(size_t dynamic_bytes) { return dynamic_bytes + 1024 <= LDS_BUDGET; }
 
 // ---- encoder classify kernels (nice_encode.hip) -----------------------------
-constexpr int CLS_THREADS = 512;   // block size of every ring / strip / twin classify kernel
+constexpr int ENC_TILE = 1024;     // pixels per encoder tile (raster-contiguous)
+constexpr int ENC_THREADS = 256;   // enc_classify / _tiny (window kernels), enc_tilebits, enc_pack_long
+constexpr int CLS_THREADS = 512;   // block size of every ring / pair / slide / strip / twin classify kernel
 constexpr int STRIP_W = 2048;      // enc_classify_strip: columns per strip
+constexpr int CLS_RING = 16384;    // ring words (64 KB); enc_classify_ring2: twice that
+// Widest rows a ring takes: it holds 3W + 3 pixels of references plus `tiles`
+// tiles (the one being classified and the next one being staged; the pair
+// kernel works two at a time): 3W + 3 + tiles * ENC_TILE <= ring
+constexpr uint32_t cls_ring_max_w(int ring, int tiles) { return (uint32_t)((ring - tiles * ENC_TILE - 3) / 3); }
+constexpr uint32_t CLS_RING_MAX_W = cls_ring_max_w(CLS_RING, 2);        // enc_classify_ring / ring3
+constexpr uint32_t CLS_RING2_MAX_W = cls_ring_max_w(2 * CLS_RING, 2);   // enc_classify_ring2 / ring2_3
+constexpr uint32_t CLS_PAIR_MAX_W = cls_ring_max_w(CLS_RING, 4);        // enc_classify_pair, enc_classify_slide
+static_assert(CLS_RING_MAX_W == 4777, "16K ring");
+static_assert(CLS_RING2_MAX_W == 10239, "32K ring");
+static_assert(CLS_PAIR_MAX_W == 4095, "16K ring, two tiles per iteration");
+constexpr int RUNDIGITS_THREADS = 256;   // enc_rundigits
+
+// ---- encoder scans, tables and pack (nice_encode.hip) -----------------------
+// the per-frame tile scans (enc_tailruns, enc_tilescan) run as blocks of
+// ENC_GROUP_TILES tiles; enc_group_reduce gives each group's aggregate
+constexpr uint32_t ENC_GROUP_TILES = 8192;
+constexpr int GROUP_THREADS = 256;    // enc_group_reduce
+constexpr int TR_THREADS = 1024;      // enc_tailruns
+constexpr int SCAN_THREADS = 1024;    // enc_tilescan
+constexpr int ENC_WAVE_THREADS = 64;  // one wave: enc_tables, enc_header, enc_tail, enc_band_check, enc_band_fix
+constexpr int PACKTAB_THREADS = 256;  // enc_packtab
+constexpr int BAND_THREADS = 256;     // enc_band_edges, enc_band_sum, enc_band_merge
+#ifndef NICE_PACK_BPC
+#define NICE_PACK_BPC 4
+#endif
+#ifndef NICE_PACK_CAP_BPP
+#define NICE_PACK_CAP_BPP 32     // enc_pack's LDS group buffer: bits per pixel
+#endif
+constexpr int PK_THREADS = 256;                          // enc_pack, enc_pack_over
+constexpr uint32_t PACK_BLOCKS_PER_CU = NICE_PACK_BPC;   // enc_pack: a persistent grid, ~35 KB LDS per block
+constexpr int PACK_SUB = 4;                              // tiles per enc_pack work item (group)
+constexpr uint32_t PACK_OVER_BLOCKS = 64;   // enc_pack_over's grid (blocks loop over the listed groups)
+constexpr int EDGES_THREADS = 256;          // enc_edges
+constexpr uint32_t ENC_LONG_BLOCKS = 2048;  // enc_tilebits / enc_pack_long: at most (blocks take tile ranges)
 
 // ---- decoder parse (nice_decode.hip) ----------------------------------------
 // sync checkpoint spacing inside a slice (DecArgs::ck_bits, chosen per call:

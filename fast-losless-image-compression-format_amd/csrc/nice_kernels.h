@@ -1,5 +1,6 @@
-// nice_kernels.h -- kernel argument blocks and launch-visible constants shared by
-// the HIP kernels and the host runtime (nice_capi.hip).  Device pointers only.
+// nice_kernels.h -- kernel argument blocks and kernel declarations shared by the
+// HIP kernels and the host runtime (nice_capi.hip).  Device pointers only.  The
+// constants a launch depends on are in nice_geom.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -8,7 +9,6 @@
 
 namespace nice {
 
-constexpr int ENC_TILE = 1024;          // pixels per encoder tile (raster-contiguous)
 // frame emits a code longer than FAST_MAX_CODE_BITS: packed by enc_pack_long
 // (the reference writer's u32 cache wraps for such codes, bitwriter.rs:63-64)
 constexpr uint32_t FLAG_LONG = 1u;
@@ -35,27 +35,20 @@ struct EncArgs {
   uint32_t* tile_next;       // n_frames * T
   uint32_t* cmask;           // n_frames * T * 32: coded-pixel flags per tile (enc_classify_pair_m); null in band mode
   uint32_t cmask_std;        // 1: cmask holds every tile's flags in the standard order by enc_pack time
-  uint32_t* tbl;             // n_frames * 858: (code << 5) | len for len <= 25
   uint32_t* tbl_code;        // n_frames * 858: code as u32 (serial path)
   uint8_t* tbl_len8;         // n_frames * 858: u8 length
   uint8_t* stream_max;       // n_frames * 10
   uint32_t* frame_flags;     // n_frames
   unsigned long long* seed_bit;   // n_frames: absolute bit where symbol data starts
-  uint32_t* seed_suf;        // n_frames: last 32 bits before seed_bit
-  unsigned long long* hdr_bytes;  // n_frames (serial header path)
-  uint32_t* hdr_cache;       // n_frames
-  uint8_t* hdr_bitoff;       // n_frames
   uint32_t* recs;            // n_frames * rec_stride per-pixel symbol records
   uint64_t rec_stride;       // W*H rounded up to 4
-  uint32_t* tile_bits;       // n_frames * T: data bits per tile (long path); pack_mode 0: the
-                             // tile's bits in the word holding its first bit (enc_edges)
+  uint32_t* tile_bits;       // n_frames * T: data bits per tile (FLAG_LONG frames); every other frame: a
+                             // group's bits in the word holding its first bit, at its first tile (enc_edges)
   unsigned long long* tile_off;   // n_frames * T: absolute bit offset of each tile
   uint8_t* packtab;          // n_frames * sizeof(PackTab): the packer's code tables (nice_rec.hpp)
   uint32_t* pack_ctr;        // n_frames: enc_pack's per-frame tile counters (zeroed per launch)
   uint32_t pack_slots;       // enc_pack: frames worked at once (blocks per frame = grid / slots)
   unsigned long long* status;   // n_frames * (tile_hi - tile_lo): look-back status words (zeroed per launch)
-  uint32_t pack_mode;        // 0: tile offsets by look-back (frames); 1: from enc_tilescan (bands)
-  uint32_t long_only;        // 1: enc_tilebits / enc_tilescan serve FLAG_LONG frames only
   unsigned long long* data_end;   // n_frames: bit position after the last data bit
   // Band mode (one image sharded over ranks): only tiles
   // [tile_lo, tile_hi) of each frame are processed; pixel memory is valid for
@@ -82,22 +75,17 @@ struct EncArgs {
   uint32_t* over_count;      // zeroed per launch
   uint2* over_list;          // n_frames * ceil((tile_hi - tile_lo) / PACK_SUB)
 };
-constexpr uint32_t ENC_GROUP_TILES = 8192;
 
 __global__ void enc_classify(EncArgs a);        // W >= 3
 __global__ void enc_classify_tiny(EncArgs a);   // W < 3
-__global__ void enc_classify_ring(EncArgs a);    // RGBA
+__global__ void enc_classify_ring(EncArgs a);    // RGBA, 16K-pixel ring (W <= CLS_RING_MAX_W)
 __global__ void enc_classify_ring3(EncArgs a);   // RGB, 4-byte aligned frames
 __global__ void enc_classify_strip_m(EncArgs a);
 __global__ void enc_classify_strip(EncArgs a);   // RGBA, W % 1024 == 0, W > CLS_RING_MAX_W (tiles_per_block = rows per block)
-// the 16K-pixel ring holds 3W + 3 pixels of references plus two tiles (the one
-// being classified and the next one being staged): 3W + 3 + 2048 <= 16384
-constexpr uint32_t CLS_RING_MAX_W = 4777;
-// enc_classify_ring2 / ring2_3: the same with a 32K-pixel ring: 3W + 3 + 2048 <= 32768
+// enc_classify_ring2 / ring2_3: the same with a 32K-pixel ring (W <= CLS_RING2_MAX_W)
 __global__ void enc_classify_ring2(EncArgs a);
 __global__ void enc_classify_ring2_3(EncArgs a);
-constexpr uint32_t CLS_RING2_MAX_W = 10239;
-// enc_classify_pair: RGBA, two tiles per iteration, 16K ring: 3W + 3 + 4096 <= 16384
+// enc_classify_pair: RGBA, two tiles per iteration, 16K ring (W <= CLS_PAIR_MAX_W)
 __global__ void enc_classify_pair(EncArgs a);
 __global__ void enc_classify_pair_m(EncArgs a);
 __global__ void enc_classify_ring_m(EncArgs a);
@@ -116,7 +104,6 @@ __global__ void enc_classify_twin(EncArgs a);
 __global__ void enc_classify_twin_m(EncArgs a);
 __global__ void enc_classify_twin3(EncArgs a);
 __global__ void enc_classify_twin3_m(EncArgs a);
-constexpr uint32_t CLS_PAIR_MAX_W = 4095;
 // dec_sync / dec_emit block size: one LUT copy per 8 waves (LDS sets occupancy)
 #ifndef NICE_PARSE_THREADS
 #define NICE_PARSE_THREADS 512
@@ -133,16 +120,7 @@ __global__ void enc_group_reduce(EncArgs a, int what);
 __global__ void enc_packtab(EncArgs a);
 __global__ void enc_pack(EncArgs a);
 __global__ void enc_pack_over(EncArgs a);
-constexpr uint32_t PACK_OVER_BLOCKS = 64;   // enc_pack_over's grid (blocks loop over the listed groups)
 __global__ void enc_edges(EncArgs a);
-#ifndef NICE_PACK_BPC
-#define NICE_PACK_BPC 4
-#endif
-#ifndef NICE_PACK_CAP_BPP
-#define NICE_PACK_CAP_BPP 32     // enc_pack's LDS group buffer: bits per pixel
-#endif
-constexpr uint32_t PACK_BLOCKS_PER_CU = NICE_PACK_BPC;   // enc_pack: 256 threads, ~35 KB LDS
-constexpr int PACK_SUB = 4;                  // tiles per enc_pack work item (group)
 __global__ void enc_tail(EncArgs a);
 __global__ void enc_band_edges(EncArgs a, uint32_t* edges);
 __global__ void enc_band_sum(EncArgs a, const uint32_t* bhist, unsigned long long* info);

@@ -7,21 +7,15 @@ pair kernel's (NICE_ENC_NO_SLIDE): every W mod 4, the narrowest widths
 (references wrapping across rows), the ring's widest rows, frames whose pixel
 count is not a multiple of 4 (a lane's last pixels past the frame), batches
 whose blocks cross frames, and deep-code (> 25-bit) frames."""
-import ctypes
-
 import numpy as np
 import pytest
+
+import plan_driver
 
 pytestmark = pytest.mark.gpu
 
 PAIR, SLIDE = 5, 7
-
-
-def _last(nice, ctx):
-    L = nice.lib()
-    L.nice_test_last_classify.argtypes = [ctypes.c_void_p]
-    L.nice_test_last_classify.restype = ctypes.c_int
-    return L.nice_test_last_classify(ctx.ptr)
+_last = plan_driver.last_classify
 
 
 def _encode(nice, frames, w, h, ctx):

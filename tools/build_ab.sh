@@ -8,8 +8,8 @@ T=$(mktemp -d /tmp/ab_XXXX)
 git -C "$R" archive "$REV" fast-losless-image-compression-format_amd/csrc include | tar -x -C "$T"
 cd "$T/fast-losless-image-compression-format_amd"
 pids=""
-for f in nice_encode nice_decode nice_capi nice_pipe nice_image; do
-  [ -f csrc/$f.hip ] || continue
+for src in csrc/*.hip; do   # every HIP source the revision has
+  f=$(basename "$src" .hip)
   /opt/rocm/bin/hipcc -O3 -std=c++17 --offload-arch=gfx950 -fPIC -Wno-unused-function $EXTRA \
     -c csrc/$f.hip -o $T/$f.o &
   pids="$pids $!"
