@@ -16,12 +16,8 @@
 //                    with the previous parse; the sync pass also counts pixels.
 //   dec_scan         exclusive scan of the pixel counts per frame.
 //   dec_emit         one 32-bit record per coded pixel (mode + constants).
-//   dec_reconstruct  one wave per frame, rows in order, one lane per row segment:
-//                    segments start from an unknown entry tracked as per-channel
-//                    cyclic intervals (exact once they collapse -- the predictors
-//                    average with the known row above), then unconverged prefixes
-//                    are recomputed exactly in rounds once their left neighbour
-//                    segment is final.
+// The records go to the row kernels (nice_rows.hip: dec_reconstruct, dec_rows*),
+// which rebuild the pixels row by row.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -29,17 +25,11 @@
 
 #include "../../include/nice.h"
 #include "nice_bits.hpp"
+#include "nice_dec_rec.hpp"
 #include "nice_format.h"
 #include "nice_kernels.h"
 
 namespace nice {
-
-// ---------------------------------------------------------------------------
-// status helpers
-// ---------------------------------------------------------------------------
-__device__ __forceinline__ void set_status(int32_t* st, int32_t code) {
-  atomicCAS(reinterpret_cast<int*>(st), 0, code);
-}
 
 // chunk geometry: chunk j of frame f covers bits [D + j*CB, D + (j+1)*CB)
 __device__ __forceinline__ uint32_t n_chunks(uint64_t len, uint64_t D, uint32_t cb) {
@@ -1259,78 +1249,17 @@ __global__ __launch_bounds__(DEC_PARSE_THREADS) void dec_strict_refill(DecArgs a
 // ---------------------------------------------------------------------------
 // D4: per-pixel records.  With every chunk's entry state and first pixel index
 // known, each chunk decodes its symbols again and writes one 32-bit record per
-// coded pixel; run pixels keep the REC_RUN fill.  A record says how the pixel
-// follows from already decoded pixels (code.rs:579-644):
-//   value_c = src_c + c_c (mod 256), c = bits 0..23,
-//   src = floor((L + U) / 2) (L on row 0)      kind AVG: SMALL_DIFF, LUMA2, RGB
-//   src = pixel i - off(refid)                 kind REF: BACK_REF (refid 0..4),
-//                                                        LUMA (refid 5..15)
+// coded pixel, tagged with the call's tag; run pixels write nothing (a slot
+// without the tag reads as REC_RUN).  A record says how the pixel follows from
+// already decoded pixels (code.rs:579-644):
+//   value_c = src_c + c_c (mod 256), c spread over bits 0..7, 10..17, 20..27,
+//   src = floor((L + U) / 2) (L on row 0)      class 0: SMALL_DIFF, LUMA2, RGB
+//   src = pixel i - off(refid)                 classes 1..13: BACK_REF (refid
+//                                              0..4), LUMA (refid 5..15)
+// (the layout, the tag and the class tables: nice_dec_rec.hpp).
 // Records of a lane are combined into aligned groups of four and stored with
 // one 16-byte store when the group lies inside the lane's pixel range.
 // ---------------------------------------------------------------------------
-// Record (round 6): the additive constant c in the row kernels' spread form
-// (R | G << 10 | B << 20: bits 0..7, 10..17, 20..27), bits 28..31 the source
-// class: 0 = AVG, 1..3 = the pixel 1..3 back in raster order (a run pixel is
-// class 1 with c = 0), 4..13 = a pixel in a row above, at (rows back, pixels
-// back) = cls_rows / cls_px.  The record writers (dec_emit, dec_place) spread
-// the constant, so the row kernels' pre-pass -- on the row chain -- only masks
-// it (round 5 kept bytes and spread every pixel there: ~5 VALU per pixel).
-constexpr uint32_t REC_RUN = 1u << 28;
-constexpr uint32_t REC_K = 0xFFu | (0xFFu << 10) | (0xFFu << 20);   // the constant's bits
-// Records written by a decode call carry its tag (1..15) in the gap bits 8..9
-// (tag & 3) and 18..19 (tag >> 2); a slot without the current tag (stale, or
-// cleared to 0) is a run pixel.  The record buffer is then cleared only when
-// its tags wrap or its layout changes (nice_capi.hip), not prefilled with
-// REC_RUN by every call.  The canonical record keeps the tag bits: readers take
-// the class (rec_cls) and the constant (rec_c) only.
-constexpr uint32_t REC_TAG_MASK = (3u << 8) | (3u << 18);
-__device__ __forceinline__ uint32_t rec_tagbits(uint32_t tag) { return ((tag & 3u) << 8) | ((tag >> 2) << 18); }
-__device__ __forceinline__ uint32_t rec_canon(uint32_t r, uint32_t tag) {
-  return (r & REC_TAG_MASK) == rec_tagbits(tag) ? r : REC_RUN;
-}
-__device__ __forceinline__ uint32_t rec_cls(uint32_t r) { return r >> 28; }
-__device__ __forceinline__ uint32_t rec_c(uint32_t r) { return r & REC_K; }
-// R | G << 8 | B << 16 -> spread (the record writers)
-__device__ __forceinline__ uint32_t rec_spread(uint32_t v) {
-  return (v & 0xFFu) | ((v & 0xFF00u) << 2) | ((v & 0xFF0000u) << 4);
-}
-__host__ __device__ constexpr int cls_rows(int c) {
-  return c < 4 ? 0 : c == 4 ? 1 : c == 5 ? 1 : c == 6 ? 2 : c == 7 ? 1 : c <= 10 ? 3 : c == 11 ? 1 : c <= 13 ? 3 : 0;
-}
-__host__ __device__ constexpr int cls_px(int c) {
-  return c < 4 ? c : c == 4 ? 0 : c == 5 ? -1 : c == 6 ? 0 : c == 7 ? -3 : c == 8 ? -1 : c == 9 ? 0
-       : c == 10 ? 1 : c == 11 ? 3 : c == 12 ? 3 : c == 13 ? -3 : 0;
-}
-// reference id (back refs 0..4, luma refs 5..15) -> class
-__host__ __device__ constexpr int id_cls(int id) {
-  return id == 0 ? 1 : id == 1 ? 4 : id == 2 ? 5 : id == 3 ? 2 : id == 4 ? 6
-       : id == 5 ? 1 : id == 6 ? 4 : id == 7 ? 5 : id == 8 ? 7 : id == 9 ? 3 : id == 10 ? 8
-       : id == 11 ? 9 : id == 12 ? 10 : id == 13 ? 11 : id == 14 ? 12 : 13;
-}
-__host__ __device__ constexpr bool cls_table_ok() {
-  for (int id = 0; id < 16; ++id) {
-    const int rows = id < 5 ? br_rows(id) : lr_rows(id - 5), px = id < 5 ? br_px(id) : lr_px(id - 5);
-    if (cls_rows(id_cls(id)) != rows || cls_px(id_cls(id)) != px) return false;
-  }
-  return true;
-}
-static_assert(cls_table_ok(), "reference offsets (code.rs:141-145) map onto the record classes");
-constexpr unsigned long long ID_CLS_PACK = [] {
-  unsigned long long v = 0;
-  for (int id = 0; id < 16; ++id) v |= (unsigned long long)id_cls(id) << (4 * id);
-  return v;
-}();
-constexpr uint32_t CLS_ROWS_PACK = [] {
-  uint32_t v = 0;
-  for (int c = 0; c < 16; ++c) v |= (uint32_t)cls_rows(c) << (2 * c);
-  return v;
-}();
-constexpr unsigned long long CLS_PX_PACK = [] {
-  unsigned long long v = 0;
-  for (int c = 0; c < 16; ++c) v |= (unsigned long long)(cls_px(c) + 3) << (3 * c);
-  return v;
-}();
-
 
 // Record of a completed coded pixel (branch-free), as an event word: the
 // record in its spread layout (REC_K: the constant in bits 0-7, 10-17 and
@@ -1630,40 +1559,22 @@ __global__ __launch_bounds__(1024) void dec_heads(DecArgs a) {
 // make_record for dec_place: 32-bit arithmetic (q <= N <= 2^30, 3W < 2^32),
 // the SMALL_DIFF constant from a table (sdl: 343 packed constants in LDS), the
 // reference's class and offset from another (idt: 16 entries per block).
-#ifdef NICE_PLACE_ARITH
-constexpr uint32_t ID_CLS_LO = (uint32_t)ID_CLS_PACK, ID_CLS_HI = (uint32_t)(ID_CLS_PACK >> 32);
-constexpr uint32_t CLS_PX_LO = (uint32_t)CLS_PX_PACK, CLS_PX_HI = (uint32_t)(CLS_PX_PACK >> 32);
-#endif
 __device__ __forceinline__ uint32_t place_record(uint32_t ev, uint32_t q, uint32_t W, const uint32_t* sdl,
                                                  const uint2* idt, bool& bad) {
   const uint32_t pfx = ev & 7u;
-#ifndef NICE_PLACE_BRANCHY
   // prefix tests as bits of one mask: as == compares of one value, the
   // compiler turned the selects below into a switch of exec-masked branches
   const uint32_t pm = 1u << pfx;
   const bool isbr = (pm & (1u << P_BACK_REF)) != 0u, islu = (pm & (1u << P_LUMA)) != 0u;
   const bool issd = (pm & (1u << P_SMALL_DIFF)) != 0u, isl2 = (pm & (1u << P_LUMA2)) != 0u;
-#else
-  const bool isbr = pfx == (uint32_t)P_BACK_REF, islu = pfx == (uint32_t)P_LUMA;
-  const bool issd = pfx == (uint32_t)P_SMALL_DIFF, isl2 = pfx == (uint32_t)P_LUMA2;
-#endif
   const uint32_t s0 = (ev >> 3) & 511u, s1 = (ev >> 12) & 255u, s2 = (ev >> 20) & 255u, s3 = (ev >> 7) & 31u;
   const uint32_t s0l = s0 & 15u;   // LUMA: the reference (bits 3..6)
   const uint32_t id = min(isbr ? s0 : 5u + s0l, 15u);
-#ifndef NICE_PLACE_ARITH
   // class and offset + 3 of the reference from the block's 16-entry table
   // (one 8-byte LDS read instead of two packed-constant extractions, one of
   // them across a word boundary, which compiled to a branch)
   const uint2 ct = idt[id];
   const uint32_t cls = ct.x, off3 = ct.y;
-#else
-  const uint32_t cls = (id < 8u ? ID_CLS_LO >> (4u * id) : ID_CLS_HI >> (4u * id - 32u)) & 15u;
-  const uint32_t rows = (CLS_ROWS_PACK >> (2u * cls)) & 3u;
-  const uint32_t b3 = 3u * cls;   // px + 3 at bits 3cls (48 bits over two words)
-  const uint32_t pxp = (b3 < 32u ? (CLS_PX_LO >> b3) | (b3 > 29u ? CLS_PX_HI << (32u - b3) : 0u)
-                                 : CLS_PX_HI >> (b3 - 32u)) & 7u;
-  const uint32_t off3 = rows * W + pxp;   // offset + 3
-#endif
   const bool bad_ref = (isbr && s0 >= 5u) || (islu && s0l >= 11u) || off3 < 3u || q + 3u < off3;
   const uint32_t gl = (s1 - 32u) & 255u;
   const uint32_t c_lu = ((s2 - 16u + gl) & 255u) | (gl << 10) | (((s3 - 16u + gl) & 255u) << 20);
@@ -1674,7 +1585,6 @@ __device__ __forceinline__ uint32_t place_record(uint32_t ev, uint32_t q, uint32
   const uint32_t c_l2 = ((s1 - 16u + g2) & 255u) | (g2 << 10) | (((s2 - 16u + g2) & 255u) << 20);
   uint32_t c_rgb = (s0 & 255u) | (s1 << 10) | (s2 << 20);
   bad = (isbr || islu) ? bad_ref : (isl2 && q < W);
-#ifndef NICE_PLACE_BRANCHY
   // the candidates opaque: otherwise the select chain compiles to a switch of
   // exec-masked branches on the prefix (about 35 scalar instructions and 8
   // branches per event, every prefix present in most waves)
@@ -1682,9 +1592,6 @@ __device__ __forceinline__ uint32_t place_record(uint32_t ev, uint32_t q, uint32
   uint32_t c_sd2 = c_sd, c_l22 = c_l2;
   asm volatile("" : "+v"(c_br), "+v"(c_sd2), "+v"(c_l22), "+v"(c_rgb));
   return (isbr || islu) ? c_br : issd ? c_sd2 : isl2 ? c_l22 : c_rgb;
-#else
-  return (isbr || islu) ? ((cls << 28) | (islu ? c_lu : 0u)) : issd ? c_sd : isl2 ? c_l2 : c_rgb;
-#endif
 }
 
 // SMALL_DIFF index -> record constant (code.rs:230-247): index = rd + 7 gd + 49 bd
@@ -1863,1646 +1770,5 @@ __global__ __launch_bounds__(64 * DEC_PLACE_WAVES) void dec_place(DecArgs a) {
   if (err) set_status(&a.status[f], NICE_E_FORMAT);
 }
 
-// ---------------------------------------------------------------------------
-// D5: reconstruction.
-// ---------------------------------------------------------------------------
-struct RecLds {
-  uint32_t y4tail[4];
-  int32_t ref_k[16], ref_d[16];
-  int32_t ref_off32[16];   // k*W + d per record class, clamped to [0, 4] (only 0..3 are special)
-  int32_t err;
-  uint32_t pad[3];
-};
-
-// Per-channel cyclic intervals [lo, lo+len] (mod 256) for the three channels
-// in the "spread" layout (fields at bits 0, 10, 20 with two guard bits), so one
-// 32-bit op acts on all channels.  An exact value is an interval with len 0;
-// unknown is lo 0, len 255.  Rows are stored spread as well.
-constexpr uint32_t SP_K = 0xFFu | (0xFFu << 10) | (0xFFu << 20);
-constexpr uint32_t SP_K9 = 0x1FFu | (0x1FFu << 10) | (0x1FFu << 20);
-constexpr uint32_t SP_1 = 1u | (1u << 10) | (1u << 20);
-struct IvS { uint32_t lo, len; };
-__device__ __forceinline__ uint32_t spread3(uint32_t v) {   // R | G<<8 | B<<16 -> spread
-  return (v & 0xFFu) | ((v & 0xFF00u) << 2) | ((v & 0xFF0000u) << 4);
-}
-// unspread3(v) | alpha by two byte permutes of v (R), v >> 2 (G), v >> 4 (B):
-// asel = 0x0D060100 (alpha byte 0xFF) or 0x0C060100 (0x00); 4 instructions
-// per pixel instead of 7
-__device__ __forceinline__ uint32_t unspread3_perm(uint32_t v, uint32_t asel) {
-  const uint32_t rg = __builtin_amdgcn_perm(v >> 2, v, 0x0C0C0500u);
-  return __builtin_amdgcn_perm(v >> 4, rg, asel);
-}
-__device__ __forceinline__ uint32_t unspread3(uint32_t v) {
-  return (v & 0xFFu) | ((v >> 2) & 0xFF00u) | ((v >> 4) & 0xFF0000u);
-}
-__device__ __forceinline__ IvS ivs_exact(uint32_t sp) { return IvS{sp, 0u}; }
-__device__ __forceinline__ IvS ivs_add(IvS a, uint32_t c) { return IvS{(a.lo + c) & SP_K, a.len}; }
-// floor((L + U) / 2) + c over an interval L: halves it unless it wraps past
-// 255, in which case the hull of both halves is [U/2, (255+U)/2] -- the
-// average of the whole range [0, 255], so a wrapping field is widened to that
-// before the one averaging (instead of averaging both forms and selecting).
-__device__ __forceinline__ IvS ivs_avg(IvS l, uint32_t u, uint32_t c) {
-  const uint32_t s = l.lo + l.len;
-  const uint32_t wm = ((s >> 8) & SP_1) * 0x3FFu;        // fields whose interval wraps
-  const uint32_t lo0 = l.lo & ~wm, s0 = (s & ~wm) | (SP_K & wm);
-  const uint32_t lo1 = ((lo0 + u) >> 1) & SP_K;
-  const uint32_t hi1 = ((s0 + u) >> 1) & SP_K9;
-  return IvS{(lo1 + c) & SP_K, hi1 - lo1};
-}
-
-// Row storage: R rows x W spread pixels (R = 4 for W >= 3, else 8) and the last
-// 3 pixels of row y-4 (offsets 3W+1, 3W+3).
-struct RowCtx {
-  uint32_t* ring;
-  const uint32_t* y4tail;
-  uint32_t W, y, rmask;
-  __device__ __forceinline__ uint32_t* row(uint32_t r) const { return ring + (size_t)(r & rmask) * W; }
-};
-
-// Pixels [x0, x_stop) of the current row from their records; r0..r2 are the
-// pixels before x0 (intervals).  Branch-free step: the averaging value and the
-// reference value are both formed and one is selected.  Every value is written
-// to the row (unknown ones are rewritten by the fix-up pass before anything
-// reads them: the only same-row reads are of pixels 0..2, which lane 0 -- exact
-// from the start -- writes at its steps 0..2, before the last segment reaches
-// its last three columns; the host keeps that segment >= 6 pixels long).
-// Returns the last segment-local index left unknown (-1: none).
-__device__ __forceinline__ int run_segment(const RowCtx& rc, const RecLds& L, const uint32_t* recs,
-                                           uint32_t x0, uint32_t x_stop, IvS r0, IvS r1, IvS r2) {
-  int last_unknown = -1;
-  const uint32_t y = rc.y;
-  const uint32_t W = rc.W;
-  uint32_t* row = rc.row(y);
-  const uint32_t* up = rc.row(y - 1);       // unused on row 0
-  const bool has_up = y > 0;
-  for (uint32_t x = x0; x < x_stop; ++x) {
-    const uint32_t r = recs[x];
-    const uint32_t u = up[x];
-    const bool ref = rec_cls(r) != 0;   // run pixels are class 1 (the pixel before) with c = 0
-    const uint32_t c = rec_c(r);
-    // reference value (kind REF): recent pixels or a pixel of the ring
-    const int id = (int)rec_cls(r);
-    const int off = (int)L.ref_off32[id];
-    int jx = (int)x - L.ref_d[id];
-    int jy = (int)y - L.ref_k[id];
-    if (W >= 4) {                 // one wrap at most (|d| <= 3)
-      const int wrapl = jx < 0, wrapr = jx >= (int)W;
-      jx += wrapl ? (int)W : (wrapr ? -(int)W : 0);
-      jy += wrapr - wrapl;
-    } else {                      // tiny widths: general linear index
-      const int64_t j = (int64_t)y * W + x - ((int64_t)L.ref_k[id] * W + L.ref_d[id]);
-      const int64_t jj = j < 0 ? 0 : j;
-      jy = (int)(jj / W);
-      jx = (int)(jj - (int64_t)jy * W);
-    }
-    jx = min(max(jx, 0), (int)W - 1);
-    const uint32_t far = (jy + 4 == (int)y && rc.rmask == 3u)
-                             ? rc.y4tail[max(jx - (int)(W - 3), 0)]
-                             : rc.ring[(size_t)((uint32_t)jy & rc.rmask) * W + (uint32_t)jx];
-    IvS src;
-    src.lo = off == 1 ? r0.lo : off == 2 ? r1.lo : off == 3 ? r2.lo : off == 0 ? 0u : far;
-    src.len = off == 1 ? r0.len : off == 2 ? r1.len : off == 3 ? r2.len : 0u;
-    src = ref ? src : r0;
-    const IvS va = ivs_avg(r0, u, c);
-    const IvS vr = ivs_add(src, c);
-    const bool avg = !ref && has_up;
-    const IvS v{avg ? va.lo : vr.lo, avg ? va.len : vr.len};
-    row[x] = v.lo;
-    last_unknown = v.len ? (int)(x - x0) : last_unknown;
-    r2 = r1; r1 = r0; r0 = v;
-  }
-  return last_unknown;
-}
-
-// The row ring lives in LDS when it fits (LDS_ROWS) -- the address space must
-// be static: a runtime LDS-or-global pointer compiles to flat_* accesses, and
-// every flat access waits for all outstanding global loads.
-template <bool LDS_ROWS>
-__device__ __forceinline__ void dec_reconstruct_body(const DecArgs& a) {
-  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-  RecLds& L = *reinterpret_cast<RecLds*>(smem);
-  const uint32_t W = a.W, H = a.H;
-  const uint32_t R = W >= 3 ? 4u : 8u;
-  const uint32_t kw = (W + 31) / 32;
-  static_assert(sizeof(RecLds) <= 512, "host LDS sizing assumes RecLds <= 512 B");
-  uint32_t* recbuf = reinterpret_cast<uint32_t*>(smem + 512) + ((kw + 3) & ~3u);   // row records
-  uint32_t* ring;
-  if constexpr (LDS_ROWS) ring = recbuf + ((W + 3) & ~3u);
-  else ring = a.rowbuf + (uint64_t)blockIdx.x * R * W;
-  const uint32_t f = blockIdx.x;
-  const int lane = threadIdx.x;
-  if (a.redo && a.hand_abort[f] != SPLIT_REDO) return;
-  if (a.status[f] != 0) return;
-  if (lane < 16) {
-    L.ref_k[lane] = cls_rows(lane);
-    L.ref_d[lane] = cls_px(lane);
-    const int64_t off = (int64_t)cls_rows(lane) * W + cls_px(lane);
-    L.ref_off32[lane] = (int32_t)(off < 0 ? 4 : off > 4 ? 4 : off);
-  }
-  if (lane == 0) L.err = 0;
-  __syncthreads();
-  const uint32_t S = a.seg, nseg = a.nseg;
-  const uint32_t* recs = a.recs + (uint64_t)f * a.rec_stride;
-  uint8_t* outp = a.px_out + (uint64_t)f * a.px_stride;
-  const uint32_t OC = a.out_channels;
-  const uint8_t alpha = (a.flags & NICE_DEC_ALPHA_FILL_FF) ? 255 : 0;
-  const bool active = (uint32_t)lane < nseg;
-  const uint32_t x0 = lane * S;
-  const uint32_t x1 = active ? ((uint32_t)lane == nseg - 1 ? W : x0 + S) : x0;
-  const uint32_t seglen = x1 - x0;
-
-  unsigned long long t_a = 0, t_b = 0, t_c = 0, t_d = 0;
-  for (uint32_t y = 0; y < H; ++y) {
-    const unsigned long long c0 = a.stats ? __builtin_amdgcn_s_memtime() : 0;
-    RowCtx rc{ring, L.y4tail, W, y, R - 1};
-    if (R == 4 && y >= 4 && lane < 3) L.y4tail[lane] = rc.row(y)[W - 3 + lane];
-    // this row's records, coalesced
-    const uint32_t* rrow = recs + (uint64_t)y * W;
-    for (uint32_t x = lane; x < W; x += 64) recbuf[x] = rec_canon(rrow[x], a.rec_tag);
-    __syncthreads();
-    auto linear_px = [&](int64_t j) -> uint32_t {
-      if (j < 0) return 0u;   // pixel 0's left neighbour is itself, not yet written (0)
-      const uint64_t jy = (uint64_t)j / W, jx = (uint64_t)j - jy * W;
-      return (R == 4 && jy + 4 == y) ? L.y4tail[jx - (W - 3)] : rc.row((uint32_t)jy)[jx];
-    };
-    IvS r0, r1, r2;
-    if (lane == 0) {
-      r0 = ivs_exact(linear_px((int64_t)y * W - 1));
-      r1 = ivs_exact(linear_px((int64_t)y * W - 2));
-      r2 = ivs_exact(linear_px((int64_t)y * W - 3));
-    } else {
-      r0 = IvS{0u, SP_K}; r1 = r0; r2 = r0;
-    }
-    const unsigned long long c1 = a.stats ? __builtin_amdgcn_s_memtime() : 0;
-    // speculative pass: lane 0 starts exact, the others from an unknown entry
-    int last_unknown = -1;
-    if (active) last_unknown = run_segment(rc, L, recbuf, x0, x1, r0, r1, r2);
-    // fix-up rounds: an unconverged segment is recomputed exactly as soon as the
-    // three pixels before it are exact (left segment converged before its last
-    // three pixels, or already fixed) -- normally all in one parallel round
-    unsigned long long fin = __ballot(!active || last_unknown < 0);
-    unsigned long long tail_ok = __ballot(!active || last_unknown < 0 ||
-                                          (seglen >= 3 && last_unknown < (int)seglen - 3));
-    if (a.stats && lane == 0) {
-      atomicAdd(&a.stats[0], 1ull);
-      atomicAdd(&a.stats[1], (unsigned long long)__popcll(~fin));
-      atomicAdd(&a.stats[2], (unsigned long long)__popcll(~tail_ok));
-    }
-    if (a.stats && active && last_unknown >= 0) atomicAdd(&a.stats[3], (unsigned long long)(last_unknown + 1));
-    __syncthreads();
-    const unsigned long long c2 = a.stats ? __builtin_amdgcn_s_memtime() : 0;
-    while (fin != ~0ull) {
-      const bool mine = !((fin >> lane) & 1ull);
-      const bool left_ok = lane == 0 || (((fin | tail_ok) >> (lane - 1)) & 1ull);
-      const bool ready = mine && left_ok;
-      if (ready) {
-        r0 = ivs_exact(linear_px((int64_t)y * W + x0 - 1));
-        r1 = ivs_exact(linear_px((int64_t)y * W + x0 - 2));
-        r2 = ivs_exact(linear_px((int64_t)y * W + x0 - 3));
-        const int lu = run_segment(rc, L, recbuf, x0, x0 + (uint32_t)last_unknown + 1, r0, r1, r2);
-        if (lu >= 0) atomicCAS(&L.err, 0, NICE_E_FORMAT);   // exact inputs give exact outputs
-        last_unknown = -1;
-      }
-      __syncthreads();
-      fin |= __ballot(ready);
-      tail_ok |= fin;
-      if (a.stats && lane == 0) atomicAdd(&a.stats[4], 1ull);
-    }
-    __syncthreads();
-    const unsigned long long c3 = a.stats ? __builtin_amdgcn_s_memtime() : 0;
-    if (L.err) break;
-    // emit the row in the caller's pixel format
-    uint8_t* orow = outp + (uint64_t)y * W * OC;
-    const uint32_t* row = rc.row(y);
-    if (OC == 4) {
-      uint32_t* o32 = reinterpret_cast<uint32_t*>(orow);
-      for (uint32_t x = lane; x < W; x += 64) o32[x] = unspread3(row[x]) | ((uint32_t)alpha << 24);
-    } else {
-      for (uint32_t x = lane; x < W; x += 64) {
-        const uint32_t v = unspread3(row[x]);
-        uint8_t* o = orow + (uint64_t)x * 3;
-        o[0] = (uint8_t)v; o[1] = (uint8_t)(v >> 8); o[2] = (uint8_t)(v >> 16);
-      }
-    }
-    __syncthreads();
-    if (a.stats) {
-      const unsigned long long c4 = __builtin_amdgcn_s_memtime();
-      t_a += c1 - c0; t_b += c2 - c1; t_c += c3 - c2; t_d += c4 - c3;
-    }
-  }
-  if (a.stats && lane == 0) {
-    atomicAdd(&a.stats[5], t_a); atomicAdd(&a.stats[6], t_b);
-    atomicAdd(&a.stats[7], t_c); atomicAdd(&a.stats[8], t_d);
-  }
-  if (lane == 0 && L.err) set_status(&a.status[f], L.err);
-}
-
-// ---------------------------------------------------------------------------
-// D5b: multi-wave reconstruction (64 <= W <= 16384).  One block per frame,
-// one lane per 16-pixel row segment (up to 1024 lanes).  A lane keeps its
-// segment of the row above and of the current row in registers (the segment
-// loop is unrolled), so the left-to-right recurrence touches no memory:
-//   pre-pass  records (prefetched one row ahead) -> per-pixel kind and
-//             constant; references into rows above read a ring of the last
-//             four rows (LDS when it fits, else global)
-//   spec      from the exact entry (lane 0) or an unknown one (others), as
-//             per-channel cyclic intervals that collapse within a few pixels
-//   fix-up    rounds across the block: a lane whose left neighbour's last
-//             three pixels are exact recomputes its unknown prefix exactly;
-//             the others refine theirs from the neighbour's current intervals
-//             (sound, so anything that collapses is final)
-//   emit      pixels to the ring and the caller's raster
-// ---------------------------------------------------------------------------
-// (ROWS_SEG, ROWS_RING and the kernels' LDS layouts: nice_geom.h)
-
-// Per-pixel word: spread constant c in the field bits, the kind as one-hot
-// flags in the guard bits -- W_L1/W_L2/W_L3: c plus the pixel 1..3 back;
-// W_AVG: c plus floor((left + up) / 2); W_CUR: c plus one of pixels 0..2 of the
-// current row (index in bits 8..9), unknown until lane 0 has them; none: the
-// constant itself (a reference into a row above, already added).
-constexpr uint32_t W_L1 = 1u << 28, W_AVG = 1u << 31, W_CUR = 1u << 18;   // W_L2, W_L3: bits 29, 30
-// Kind bits >> 28 per record class, 4 bits per class: class 0 is the average
-// (on row 0: the pixel to the left), classes 1-3 the pixel 1-3 back, classes
-// 4-13 a pixel of a row above (no bits; W_CUR is added per pixel).
-constexpr unsigned long long ROWS_KIND = (W_AVG >> 28) | ((unsigned long long)(W_L1 >> 28) << 4) |
-                                         ((unsigned long long)((W_L1 << 1) >> 28) << 8) |
-                                         ((unsigned long long)((W_L1 << 2) >> 28) << 12);
-constexpr unsigned long long ROWS_KIND_Y0 = (ROWS_KIND & ~15ull) | (W_L1 >> 28);
-static_assert((W_AVG >> 28) == 8u && (W_L1 >> 28) == 1u, "kind bits 28..31");
-__device__ __forceinline__ uint32_t wmask(uint32_t w, int bit) {
-  return (uint32_t)__builtin_amdgcn_sbfe((int)w, bit, 1);   // 0 or ~0
-}
-// One pixel: kinds are selected with masks (no control flow, no SGPR masks).
-// The constant is the word itself: its kind bits (18, 28..31) only reach a
-// field's guard bits or bits >= 28 of the sums, which the masks after every
-// add clear (no carry reaches a lower field: value bits <= 255 + 255 + 512).
-// CUR = false: the caller knows no word holds W_CUR (waves without the row's
-// last columns), two instructions fewer.
-template <bool CUR = true>
-__device__ __forceinline__ IvS rows_step(IvS l1, IvS l2, IvS l3, uint32_t u, uint32_t wp) {
-  const uint32_t c = wp;
-  const IvS va = ivs_avg(l1, u, c);
-  const uint32_t m1 = wmask(wp, 28), m2 = wmask(wp, 29), m3 = wmask(wp, 30);
-  const uint32_t ma = wmask(wp, 31);
-  const uint32_t slo = (l1.lo & m1) | (l2.lo & m2) | (l3.lo & m3);
-  const uint32_t slen = (l1.len & m1) | (l2.len & m2) | (l3.len & m3) | (CUR ? SP_K & wmask(wp, 18) : 0u);
-  const uint32_t rlo = (slo + c) & SP_K;
-  return IvS{(va.lo & ma) | (rlo & ~ma), (va.len & ma) | (slen & ~ma)};
-}
-
-// rows_chain when every input is exact (r0..r2 and the kept pixels): plain
-// arithmetic, no intervals.  Only after the W_CUR words are resolved.
-__device__ __forceinline__ uint32_t rows_step_exact(uint32_t l1, uint32_t l2, uint32_t l3, uint32_t u,
-                                                    uint32_t wp) {
-  // (l1 + u) >> 1 leaves the next field's lowest bit in each guard bit 9:
-  // with c (the word: no W_CUR bit once resolved) a field sums to <= 1022, so
-  // one mask at the end clears both
-  const uint32_t c = wp;
-  // kinds as sign-extended bit masks: and / and-or / bit-insert selects, the
-  // constant added once after the average-or-copy select (instead of compare
-  // and select chains: one 4K frame reconstruct 9.02 -> 8.72 ms, 64 x 1080p
-  // 4.10 -> 3.95, profiles/r05zr_ab_flow_steps.log)
-  const uint32_t sel = (l1 & wmask(wp, 28)) | (l2 & wmask(wp, 29)) | (l3 & wmask(wp, 30));
-  const uint32_t ma = (uint32_t)((int32_t)wp >> 31);
-  const uint32_t x = (((l1 + u) >> 1) & ma) | (sel & ~ma);
-  return (x + c) & SP_K;
-}
-
-// Speculative pass over the whole segment; returns -1 when every pixel is
-// exact, S - 4 when the last three are, else S - 1 (a bound on the last unknown).
-// (Switching a wave to the plain step once all its lanes are exact -- one
-// vote per pixel -- was 5 % slower: each vote's branch waits on the VALU.)
-// A partial last segment's padding pixels are run records (copies of the pixel
-// before, interval width included), so counting them leaves "every pixel
-// exact" unchanged and spares 16 loop-invariant lane masks (SGPR spills).
-template <int S>
-__device__ __forceinline__ int rows_spec(IvS (&v)[S], IvS r0, IvS r1, IvS r2, const uint32_t (&w)[S],
-                                         const uint32_t (&prev)[S]) {
-#pragma unroll
-  for (int p = 0; p < S; ++p) {
-    const IvS l1 = p >= 1 ? v[p - 1] : r0;
-    const IvS l2 = p >= 2 ? v[p - 2] : (p == 1 ? r0 : r1);
-    const IvS l3 = p >= 3 ? v[p - 3] : (p == 2 ? r0 : (p == 1 ? r1 : r2));
-    v[p] = rows_step(l1, l2, l3, prev[p], w[p]);
-  }
-  // a coarse last unknown index from two OR trees instead of a compare and a
-  // select per pixel: its users only ask "any unknown" and "last three exact",
-  // and the fix-up chain recomputing exact pixels too is harmless (512-frame
-  // reconstruct 20.03 -> 19.63 ms)
-  uint32_t head = 0, tail = v[S - 1].len | v[S - 2].len | v[S - 3].len;
-#pragma unroll
-  for (int p = 0; p < S - 3; ++p) head |= v[p].len;
-  return tail ? S - 1 : head ? S - 4 : -1;
-}
-
-// Recomputes pixels 0..lu (lanes with `go`), keeping the others (already
-// exact); returns the new last unknown index.  Stops once no lane of the wave
-// has work left.
-template <int S>
-__device__ __forceinline__ int rows_chain(IvS (&v)[S], IvS r0, IvS r1, IvS r2, const uint32_t (&w)[S],
-                                          const uint32_t (&prev)[S], int lu, bool go) {
-  int nlu = -1;
-  const int upto = go ? lu : -1;
-#pragma unroll
-  for (int p = 0; p < S; ++p) {
-    if (!__any(p <= upto)) break;
-    const IvS l1 = p >= 1 ? v[p - 1] : r0;
-    const IvS l2 = p >= 2 ? v[p - 2] : (p == 1 ? r0 : r1);
-    const IvS l3 = p >= 3 ? v[p - 3] : (p == 2 ? r0 : (p == 1 ? r1 : r2));
-    const IvS n = rows_step(l1, l2, l3, prev[p], w[p]);
-    const bool upd = p <= upto;
-    v[p].lo = upd ? n.lo : v[p].lo;
-    v[p].len = upd ? n.len : v[p].len;
-    nlu = (upd && n.len) ? p : nlu;
-  }
-  return go ? nlu : lu;
-}
-
-template <int S>
-__device__ __forceinline__ int rows_chain_exact(IvS (&v)[S], IvS r0, IvS r1, IvS r2, const uint32_t (&w)[S],
-                                                const uint32_t (&prev)[S], int lu, bool go) {
-  const int upto = go ? lu : -1;
-  // all S steps, predicated: a vote per pixel to stop early (its branch waits
-  // on the VALU) made a single 4K frame 4 % slower, same at 512 frames (one
-  // vote per call to skip waves with nothing to recompute, and kind masks
-  // instead of the select chain, were no faster either)
-#pragma unroll
-  for (int p = 0; p < S; ++p) {
-    const uint32_t l1 = p >= 1 ? v[p - 1].lo : r0.lo;
-    const uint32_t l2 = p >= 2 ? v[p - 2].lo : (p == 1 ? r0.lo : r1.lo);
-    const uint32_t l3 = p >= 3 ? v[p - 3].lo : (p == 2 ? r0.lo : (p == 1 ? r1.lo : r2.lo));
-    const uint32_t n = rows_step_exact(l1, l2, l3, prev[p], w[p]);
-    const bool upd = p <= upto;
-    v[p].lo = upd ? n : v[p].lo;
-    v[p].len = upd ? 0u : v[p].len;
-  }
-  return go ? -1 : lu;
-}
-
-// Block barrier; with the ring in LDS only LDS traffic is ordered, so global
-// stores (the raster) and the record prefetch stay in flight across it.
-template <bool LDS_RING>
-__device__ __forceinline__ void rows_barrier() {
-  if constexpr (LDS_RING) {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-  } else {
-    __syncthreads();
-  }
-}
-
-template <int MAXT, bool LDS_RING, int S = ROWS_SEG>
-__device__ __forceinline__ void dec_rows_body(const DecArgs& a) {
-  // diagnostics counters (NICE_DEC_STATS=1) only in -DNICE_ROWS_STATS builds:
-  // the runtime checks alone held SGPRs and branches in the row loop
-#ifdef NICE_ROWS_STATS
-  unsigned long long* const stats = a.stats;
-#else
-  constexpr unsigned long long* stats = nullptr;
-#endif
-  extern __shared__ __attribute__((aligned(16))) uint32_t sm[];
-  // per record class: rows back (bits 0-1), pixels back + 3 (bits 2-4), kind
-  // bits (28-31); entries 16.. for row 0.  One LDS read per pixel instead of
-  // three shifts of packed 64-bit constants.
-  __shared__ uint32_t clsw[32];
-  if (threadIdx.x < 32) {
-    const uint32_t c = threadIdx.x & 15u;
-    const unsigned long long kinds = threadIdx.x >= 16 ? ROWS_KIND_Y0 : ROWS_KIND;
-    clsw[threadIdx.x] = ((CLS_ROWS_PACK >> (2 * c)) & 3u) | (uint32_t)((CLS_PX_PACK >> (3 * c)) & 7u) << 2 |
-                        ((uint32_t)(kinds >> (4u * c)) & 15u) << 28;
-  }
-  const uint32_t nthr = blockDim.x;
-  const uint32_t W = a.W, H = a.H;
-  const RowsLds lds = rows_lds(nthr);
-  uint32_t* tails = sm + lds.tails;   // nthr x {lo, len} x 3 (pixels S-1, S-2, S-3)
-  uint32_t* flags = sm + lds.flags;   // nthr: last three pixels exact
-  uint32_t* head3 = sm + lds.head3;   // pixels 0..2 of the current row
-  uint32_t* pend = sm + lds.pend;     // 2 round flags
-  int* err = reinterpret_cast<int*>(sm + lds.err);
-  const uint32_t f = blockIdx.x;
-  // ring rows padded one word per 16 pixels: lane i's segment starts at bank
-  // 17i mod 32, so the lanes' accesses to their segments are conflict free
-  const uint32_t RS = rows_ring_stride(W);
-  uint32_t* ring = (LDS_RING ? (sm + lds.ring) : (a.rowbuf + (uint64_t)f * ROWS_RING * RS)) + ROWS_RB;
-  // per-row class table (S == 16), double-buffered by row parity: x = kind bits
-  // | pixels back + 3, y = ring offset of the referenced row's pixel 0 plus 3
-  // minus pixels back, so a reference's word is 17 * lane + p + y (+ a +-1
-  // padding correction for the first and last three pixels of a segment)
-  __shared__ uint2 rtab[2][16];
-  auto build_tab = [&](uint32_t yy) {
-    if (threadIdx.x < 16) {
-      const uint32_t c = threadIdx.x;
-      const unsigned long long kinds = yy == 0 ? ROWS_KIND_Y0 : ROWS_KIND;
-      const uint32_t rows = (CLS_ROWS_PACK >> (2 * c)) & 3u, dxp3 = (uint32_t)(CLS_PX_PACK >> (3 * c)) & 7u;
-      rtab[yy & 1u][c] = make_uint2((((uint32_t)(kinds >> (4u * c)) & 15u) << 28) | dxp3,
-                                    ((yy - rows) & (ROWS_RING - 1)) * RS + 3u - dxp3);
-    }
-  };
-  if (S == 16) build_tab(0);
-  if (a.redo && a.hand_abort[f] != SPLIT_REDO) return;   // block-uniform
-  if (a.status[f] != 0) return;
-  const uint32_t lane = threadIdx.x;
-  const uint32_t nseg = (W + S - 1) / S;
-  const bool active = lane < nseg;
-  const uint32_t x0 = lane * S;
-  const int nvalid = active ? (int)min((uint32_t)S, W - x0) : 0;
-  const uint32_t* recs = a.recs + (uint64_t)f * a.rec_stride;
-  uint8_t* outp = a.px_out + (uint64_t)f * a.px_stride;
-  const uint32_t OC = a.out_channels;
-  const uint32_t alpha = (a.flags & NICE_DEC_ALPHA_FILL_FF) ? 0xFF000000u : 0u;
-  const uint32_t asel = alpha ? 0x0D060100u : 0x0C060100u;   // unspread3_perm
-  const bool vec_rec = (W & 3u) == 0 && nvalid == S;
-  const bool vec_out = (OC == 4 && (W & 3u) == 0 && nvalid == S) ||
-                       (OC == 3 && S % 16 == 0 && (W & 15u) == 0 && nvalid == S);
-  if (lane == 0) *err = 0;
-  uint32_t prev[S], rn[S];
-#pragma unroll
-  for (int p = 0; p < S; ++p) prev[p] = 0;
-  auto load_recs = [&](uint32_t y) {
-    const uint32_t* rrow = recs + (uint64_t)y * W + x0;
-    if (vec_rec) {
-#pragma unroll
-      for (int q = 0; q < S / 4; ++q) {
-        const uint4 t = reinterpret_cast<const uint4*>(rrow)[q];
-        rn[4 * q] = t.x; rn[4 * q + 1] = t.y; rn[4 * q + 2] = t.z; rn[4 * q + 3] = t.w;
-      }
-    } else if (nvalid > 0) {   // a partial last segment
-#pragma unroll
-      for (int p = 0; p < S; ++p) rn[p] = p < nvalid ? rrow[p] : REC_RUN;
-    } else {                   // idle lane: no loads (its wave would run the masked path every row)
-#pragma unroll
-      for (int p = 0; p < S; ++p) rn[p] = REC_RUN;
-    }
-  };
-  if (H > 0) load_recs(0);
-  __syncthreads();
-  unsigned long long t_a = 0, t_b = 0, t_c = 0, t_d = 0, n_fix = 0;
-  for (uint32_t y = 0; y < H; ++y) {
-    const unsigned long long c0 = stats ? __builtin_amdgcn_s_memtime() : 0;
-    // ---- pre-pass: records -> per-pixel words
-    const uint32_t* const cwt = clsw + (y == 0 ? 16 : 0);
-    uint32_t w[S];
-#ifdef NICE_AB_PRE2   // A/B probe: the pre-pass twice (its cost)
-    for (int rep = 0; rep < 2; ++rep) {
-      uint32_t z = 0;
-      asm volatile("" : "+v"(z));
-#else
-    {
-      constexpr uint32_t z = 0;
-#endif
-    if constexpr (S == 16) {
-      // table form: every lane, no wrap logic (ring halos); only the last
-      // lane's references to the current row (W_CUR) are patched below
-      const uint2* tb = rtab[y & 1u];
-      const uint32_t lb = 17u * lane;
-#pragma unroll
-      for (int p = 0; p < S; ++p) {
-        const uint32_t r = rec_canon(rn[p] + z, a.rec_tag);
-        const uint32_t cls = rec_cls(r);                     // 0..13
-        const uint2 e = tb[cls];
-        uint32_t ad = lb + e.y;
-        if (p < 3 || p > S - 4) ad += (uint32_t)((int)(p + 3u - (e.x & 7u)) >> 4);   // padding word crossed
-        const uint32_t o = ring[ad + p];
-        const uint32_t c = rec_c(r);
-        // (a VALU mask from a table bit instead of the compare: 4 % slower)
-        w[p] = (e.x & 0xF0000000u) | (((cls >= 4u ? o : 0u) + c) & SP_K);
-      }
-      // references past the row end into row y itself (pixels 0..2): only
-      // columns W-3 .. W-1 have them -- the last segment, and the one before
-      // it when the last holds fewer than three pixels (W % 16 in {1, 2}).
-      // Branch-free (per-pixel branches held exec masks in SGPRs, which
-      // spilled), and only the wave holding those lanes runs it.
-      if (x0 + S + 2u >= W) {
-#pragma unroll
-        for (int p = 0; p < S; ++p) {
-          const uint32_t r = rec_canon(rn[p], a.rec_tag);   // padding: a run record (class 1)
-          const uint32_t cls = rec_cls(r);
-          const uint32_t tx = x0 + p + 3u - ((uint32_t)(CLS_PX_PACK >> (3u * cls)) & 7u);
-          const bool cur = cls >= 4u && ((CLS_ROWS_PACK >> (2u * cls)) & 3u) == 1u && tx >= W;
-          w[p] = cur ? (W_CUR | rec_c(r) | ((tx - W) << 8)) : w[p];
-        }
-      }
-    } else {
-#pragma unroll
-    for (int p = 0; p < S; ++p) {
-      const uint32_t x = x0 + p;
-      const uint32_t r = rec_canon(rn[p] + z, a.rec_tag);
-      const uint32_t cls = rec_cls(r);                       // 0..13
-      const uint32_t cw = cwt[cls];                          // rows | px + 3 << 2 | kind bits
-      const uint32_t rows = cw & 3u;
-      const int dx = (int)((cw >> 2) & 7u) - 3;
-      int tx = (int)x - dx;
-      const int wl = tx < 0, wr = tx >= (int)W;
-      tx += wl ? (int)W : (wr ? -(int)W : 0);
-      const uint32_t back = rows + wl - wr;                  // rows above (0: current row)
-      const bool up = cls >= 4;
-      const bool cur = up && back == 0;
-      // unconditional LDS read (a harmless in-range address for other classes)
-      const uint32_t txc = (uint32_t)min(max(tx, 0), (int)W - 1);
-      const uint32_t o = ring[__umul24((y - back) & (ROWS_RING - 1), RS) + txc + (txc >> 4)];
-      const uint32_t c = rec_c(r);
-      // kind bits from the class (branch-free: the ternary chain compiled to two
-      // nested exec-masked branches per pixel)
-      const uint32_t kb = (cw & 0xF0000000u) | (cur ? W_CUR : 0u);
-      w[p] = kb | ((up && !cur) ? ((o + c) & SP_K) : c) | (cur ? ((uint32_t)tx << 8) : 0u);
-    }
-    }
-    }
-    // ---- entry: lane 0 exact (previous row's last pixels; 0 before pixel 0)
-    IvS r0{0u, SP_K}, r1{0u, SP_K}, r2{0u, SP_K};
-    if (lane == 0) {
-      if (y == 0) {
-        r0 = r1 = r2 = ivs_exact(0u);
-      } else {
-        const uint32_t* pr = ring + (size_t)((y - 1) & (ROWS_RING - 1)) * RS;
-        r0 = ivs_exact(pr[(W - 1) + ((W - 1) >> 4)]);
-        r1 = ivs_exact(pr[(W - 2) + ((W - 2) >> 4)]);
-        r2 = ivs_exact(pr[(W - 3) + ((W - 3) >> 4)]);
-      }
-    }
-    if (y + 1 < H) load_recs(y + 1);   // in flight during this row
-    const unsigned long long c1 = stats ? __builtin_amdgcn_s_memtime() : 0;
-    // ---- speculative pass
-    IvS v[S];
-    int lu = rows_spec<S>(v, r0, r1, r2, w, prev);
-#ifdef NICE_AB_SPEC2   // A/B probe: the speculative pass twice (its cost)
-    {
-      IvS v2[S];
-      const int lu2 = rows_spec<S>(v2, IvS{v[S - 1].lo & 1u, r0.len}, r1, r2, w, prev);
-      lu = lu2 < -1 ? lu2 : lu;
-#pragma unroll
-      for (int p = 0; p < S; ++p) v[p].lo |= v2[p].len & 0x80000000u;
-    }
-#endif
-    if (active) {
-      uint32_t* t = tails + lane * 6;
-      t[0] = v[S - 1].lo; t[1] = v[S - 1].len;
-      t[2] = v[S - 2].lo; t[3] = v[S - 2].len;
-      t[4] = v[S - 3].lo; t[5] = v[S - 3].len;
-      flags[lane] = (lu < S - 3) ? 1u : 0u;
-    }
-    if (lane == 0) { head3[0] = v[0].lo; head3[1] = v[1].lo; head3[2] = v[2].lo; pend[0] = 0; pend[1] = 0; }
-    bool fin = !active || lu < 0;
-    if (stats && active && lu >= 0) {
-      atomicAdd(&stats[1], 1ull);
-      atomicAdd(&stats[3], (unsigned long long)(lu + 1));
-      if (lu >= S - 3) atomicAdd(&stats[2], 1ull);
-      // unknown tails: every tail pixel a full-width interval (a copy chain
-      // from the unknown entry or a current-row reference) or some narrowed one
-      const uint32_t tl0 = v[S - 1].len, tl1 = v[S - 2].len, tl2 = v[S - 3].len;
-      if (tl0 | tl1 | tl2) {
-        const bool copies = (tl0 == 0u || tl0 == SP_K) && (tl1 == 0u || tl1 == SP_K) && (tl2 == 0u || tl2 == SP_K);
-        atomicAdd(&stats[copies ? 24 : 25], 1ull);
-      }
-    }
-    rows_barrier<LDS_RING>();
-    const unsigned long long c2 = stats ? __builtin_amdgcn_s_memtime() : 0;
-    const unsigned long long nfix0 = n_fix;
-#ifdef NICE_AB_ROUND   // A/B probe: one more (empty) fix-up round per row
-    if (!fin) atomicOr(&pend[1], 0u);
-    rows_barrier<LDS_RING>();
-    if (pend[1] == 7u) lu = S;
-    rows_barrier<LDS_RING>();
-#endif
-    // ---- fix-up rounds
-    bool cur_done = false;
-    for (uint32_t rd = 0;; ++rd) {
-      if (!fin) atomicOr(&pend[rd & 1u], 1u);
-      rows_barrier<LDS_RING>();
-      if (pend[rd & 1u] == 0) break;
-      ++n_fix;
-      if (lane == 0) pend[(rd + 1) & 1u] = 0;
-      if (!cur_done) {   // pixels 0..2 of the row are exact now (lane 0)
-        if (x0 + S + 2u >= W) {   // the lanes that can hold W_CUR words (above)
-          const uint32_t h0 = head3[0], h1 = head3[1], h2 = head3[2];
-#pragma unroll
-          for (int p = 0; p < S; ++p) {
-            const uint32_t k = (w[p] >> 8) & 3u;
-            const uint32_t hv = k == 0u ? h0 : k == 1u ? h1 : h2;
-            w[p] = (w[p] & W_CUR) ? ((hv + (w[p] & SP_K)) & SP_K) : w[p];
-          }
-        }
-        cur_done = true;
-      }
-      bool exact_in = false;
-      if (!fin && lane > 0) {
-        const uint32_t* t = tails + (lane - 1) * 6;
-        r0 = IvS{t[0], t[1]}; r1 = IvS{t[2], t[3]}; r2 = IvS{t[4], t[5]};
-        exact_in = flags[lane - 1] != 0;
-      }
-      rows_barrier<LDS_RING>();
-      // only lanes whose left tail is exact recompute, with plain arithmetic:
-      // refining from an inexact neighbour (interval chain) rarely collapses
-      // anything in one round and forced its whole wave onto the interval
-      // chain; the leftmost unfinished lane always has an exact left tail
-      const bool go = !fin && exact_in;
-#ifndef NICE_ROWS_HOIST
-      // the words as opaque per round: otherwise the compiler hoists the select
-      // masks of all 16 pixels out of the round loop, and their SGPR pairs
-      // spill to VGPR lanes (a writelane per mask per row, a readlane per use)
-#pragma unroll
-      for (int p = 0; p < S; ++p) asm volatile("" : "+v"(w[p]));
-#endif
-      lu = rows_chain_exact<S>(v, r0, r1, r2, w, prev, lu, go);
-      if (go) {
-        if (lu >= 0) atomicCAS(err, 0, NICE_E_FORMAT);   // exact inputs give exact outputs
-        uint32_t* t = tails + lane * 6;
-        t[0] = v[S - 1].lo; t[1] = v[S - 1].len;
-        t[2] = v[S - 2].lo; t[3] = v[S - 2].len;
-        t[4] = v[S - 3].lo; t[5] = v[S - 3].len;
-        flags[lane] = 1u;
-        fin = true;
-      }
-    }
-    if (stats && lane == 0) {
-      const unsigned long long r = n_fix - nfix0;
-      atomicAdd(&stats[9 + (r >= 6 ? 6 : r)], 1ull);
-    }
-    if (*err) break;
-    const unsigned long long c3 = stats ? __builtin_amdgcn_s_memtime() : 0;
-    // ---- emit: ring row y (its slot held row y-4, no longer referenced) and the raster
-    if (active) {
-      uint32_t* rr = ring + (size_t)(y & (ROWS_RING - 1)) * RS + x0 + (x0 >> 4);   // x0 = 16 * lane
-      const uint64_t pix = (uint64_t)y * W + x0;
-#pragma unroll
-      for (int p = 0; p < S; ++p) rr[p] = v[p].lo;   // padding pixels land in the row's spare words
-      if (lane == 0 && y > 0) {   // row y-1's right halo: this row's first three pixels
-        uint32_t* h = ring + (size_t)((y - 1) & (ROWS_RING - 1)) * RS;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) h[(W + k) + ((W + k) >> 4)] = v[k].lo;
-      }
-      // row y+1's left halo: this row's last three pixels -- from the last
-      // segment and, when it holds fewer than three (W % 16 in {1, 2}), the one
-      // before it (round 5 width sweep: W = 66, a row starting with a W+3
-      // reference read a stale halo word)
-      if (x0 + S + 2u >= W) {
-        uint32_t* h = ring + (size_t)((y + 1) & (ROWS_RING - 1)) * RS;
-#pragma unroll
-        for (int p = 0; p < S; ++p)
-          if (p < nvalid && x0 + p + 3u >= W) h[(int)(x0 + p - W) - 1] = v[p].lo;
-      }
-      if (vec_out && OC == 4) {
-        uint4* o = reinterpret_cast<uint4*>(outp + pix * 4);
-#pragma unroll
-        for (int q = 0; q < S / 4; ++q)
-          o[q] = make_uint4(unspread3_perm(v[4 * q].lo, asel), unspread3_perm(v[4 * q + 1].lo, asel),
-                            unspread3_perm(v[4 * q + 2].lo, asel), unspread3_perm(v[4 * q + 3].lo, asel));
-      } else if (vec_out) {
-        if constexpr (S % 16 == 0) {
-          uint32_t b[3 * S / 4];
-#pragma unroll
-          for (int q = 0; q < S / 4; ++q) {
-            const uint32_t u0 = unspread3_perm(v[4 * q].lo, 0x0C060100u), u1 = unspread3_perm(v[4 * q + 1].lo, 0x0C060100u);
-            const uint32_t u2 = unspread3_perm(v[4 * q + 2].lo, 0x0C060100u), u3 = unspread3_perm(v[4 * q + 3].lo, 0x0C060100u);
-            b[3 * q] = __builtin_amdgcn_perm(u1, u0, 0x04020100u);       // R0 G0 B0 R1
-            b[3 * q + 1] = __builtin_amdgcn_perm(u2, u1, 0x05040201u);   // G1 B1 R2 G2
-            b[3 * q + 2] = __builtin_amdgcn_perm(u3, u2, 0x06050402u);   // B2 R3 G3 B3
-          }
-          uint4* o = reinterpret_cast<uint4*>(outp + pix * 3);
-#pragma unroll
-          for (int q = 0; q < 3 * S / 16; ++q) o[q] = make_uint4(b[4 * q], b[4 * q + 1], b[4 * q + 2], b[4 * q + 3]);
-        }
-      } else if (OC == 4) {
-        uint32_t* o32 = reinterpret_cast<uint32_t*>(outp + pix * 4);
-#pragma unroll
-        for (int p = 0; p < S; ++p)
-          if (p < nvalid) o32[p] = unspread3(v[p].lo) | alpha;
-      } else {
-        uint8_t* o8 = outp + pix * 3;
-#pragma unroll
-        for (int p = 0; p < S; ++p) {
-          if (p < nvalid) {
-            const uint32_t u = unspread3(v[p].lo);
-            o8[3 * p] = (uint8_t)u; o8[3 * p + 1] = (uint8_t)(u >> 8); o8[3 * p + 2] = (uint8_t)(u >> 16);
-          }
-        }
-      }
-    }
-#pragma unroll
-    for (int p = 0; p < S; ++p) { prev[p] = v[p].lo; }
-    if (S == 16) build_tab(y + 1);   // the last readers of that buffer were row y-1's
-    rows_barrier<LDS_RING>();
-    if (stats) {
-      const unsigned long long c4 = __builtin_amdgcn_s_memtime();
-      t_a += c1 - c0; t_b += c2 - c1; t_c += c3 - c2; t_d += c4 - c3;
-    }
-  }
-  if (stats && lane == 0) {
-    atomicAdd(&stats[0], (unsigned long long)H);
-    atomicAdd(&stats[4], n_fix);
-    atomicAdd(&stats[5], t_a); atomicAdd(&stats[6], t_b);
-    atomicAdd(&stats[7], t_c); atomicAdd(&stats[8], t_d);
-  }
-  if (lane == 0 && *err) set_status(&a.status[f], *err);
-}
-
-// Ring in LDS (4 rows fit next to the block's tails) or in global memory.
-__global__ __launch_bounds__(ROWS_THREADS) void dec_rows(DecArgs a) { dec_rows_body<ROWS_THREADS, true>(a); }
-__global__ __launch_bounds__(ROWS_WIDE_THREADS) void dec_rows_wide(DecArgs a) { dec_rows_body<ROWS_WIDE_THREADS, false>(a); }
-// 8-pixel segments (W <= 4096: up to 512 lanes): twice the lanes per frame,
-// for batches too small to fill the CUs (single-frame latency)
-__global__ __launch_bounds__(ROWS_THREADS) void dec_rows8(DecArgs a) { dec_rows_body<ROWS_THREADS, true, 8>(a); }
-
-// ---------------------------------------------------------------------------
-// D5d: dataflow row reconstruction for small batches (round 5; 64 <= W <=
-// 4096, one frame per block, frames <= CUs).  dec_rows keeps every wave of a
-// block on one row: a block barrier after the speculative pass, two per fix-up
-// round, one after the emit, and the record pre-pass and the raster stores on
-// the row's critical path.  At one frame per CU (single frames, config 3,
-// small RGB batches) that path sets the decode time: 2160 rows of ~6.8 us for
-// 4K.  Here the block's waves form K groups of WPR = ceil(segments / 64)
-// waves; group g reconstructs rows g, g + K, ..., so rows overlap, and the
-// waves synchronise only through LDS stamps (row + 1):
-//   fin[slot][w]  wave w's segments of the row are final in the ring;
-//   tst[slot][w]  the last three pixels of wave w's last segment are exact
-//                 (tail[slot][w]): the next wave's first lane can fix up;
-//   hst[slot]     the row's first three pixels (W_CUR references of the
-//                 row's last columns, code.rs:141-145: offsets W-1, W-3 reach
-//                 into the current row).
-// Wave w of row y waits for row y-1's waves w-1..w+1 (the references reach
-// +-3 pixels, rows 1..3 back: rows y-2, y-3 are final by induction), wave 0
-// for all of row y-1 (its entry is the row's last pixels, code.rs:412-413),
-// the last wave also for row y-1's wave 0 (right halos).  Then: pre-pass ring
-// reads (the record decode and addresses are done before the wait), the
-// speculative pass, and fix-up rounds inside the wave (lane shuffles, no
-// barriers; the first lane takes the left wave's published tail), the ring
-// row and halos, the stamp, and only then the raster stores and the next
-// rows' record loads -- off the critical path.  A ring of 8 rows (K + 3 <= 8)
-// in LDS.  Every dependency points to an earlier (row, wave) and all waves
-// are resident, so the earliest unfinished one always progresses; every wait
-// is bounded (0.2 s, then the frame fails with NICE_E_HIP and the other waves
-// stop).
-// ---------------------------------------------------------------------------
-// (FLOW_THREADS, FLOW_SLOTS, FLOW_MAXW and struct FlowCtl: nice_geom.h)
-constexpr unsigned long long FLOW_TIMEOUT = 20000000ull;   // s_memrealtime ticks (100 MHz): 0.2 s
-// a timed-out wait (the workgroup preempted or time-sliced for longer than
-// that) does not fail the frame: it is marked for the barrier kernel
-// (dec_rows, launched after this one in redo mode) -- slower,
-// never wrong
-constexpr int FLOW_REDO = 1;
-static_assert(sizeof(FlowPair) == sizeof(uint2) && alignof(FlowPair) == alignof(uint2), "FlowCtl::rtab");
-__device__ __forceinline__ uint32_t flow_peek(const uint32_t* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-// LDS-only release (the raster stores and record loads stay in flight)
-__device__ __forceinline__ void flow_publish(uint32_t* p, uint32_t v) {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-__device__ __forceinline__ void flow_acquire() { __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local"); }
-// the wave waits until stamps[i] >= want for every bit i of mask (lanes 0..3
-// read one stamp each); false when the frame aborted or the wait timed out
-__device__ __forceinline__ bool flow_wait(FlowCtl& C, const uint32_t* stamps, uint32_t mask, uint32_t want) {
-  const uint32_t lane = threadIdx.x & 63u;
-  const bool mine = lane < FLOW_MAXW && ((mask >> lane) & 1u);
-  unsigned long long t0 = 0;
-  for (uint32_t n = 0;; ++n) {
-    const uint32_t v = mine ? flow_peek(stamps + lane) : want;
-    if (__ballot(v < want) == 0ull) break;
-    if ((n & 31u) == 0u) {
-      if (flow_peek(&C.abort)) return false;
-      const unsigned long long t = __builtin_amdgcn_s_memrealtime();
-      if (n == 0) t0 = t;
-      else if (t - t0 > FLOW_TIMEOUT) {
-        atomicOr(&C.abort, 1u);
-        atomicCAS(&C.err, 0, FLOW_REDO);
-        return false;
-      }
-    }
-    __builtin_amdgcn_s_sleep(1);
-  }
-  flow_acquire();
-  return true;
-}
-// lane l gets lane l-1's value (lane 0: 0) by a DPP wave shift: one VALU move,
-// no LDS round trip (ds_bpermute) on the hand-off path (one 4K frame 10.27 ->
-// 10.21 ms, 64 x 1080p 4.79 -> 4.74, profiles/r05zl_ab_flow_dpp.log)
-__device__ __forceinline__ uint32_t shfl_up1(uint32_t v) {
-  return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x138 /* wave_shr:1 */, 0xF, 0xF, false);
-}
-// The speculative pass; reports which parts of the segment stayed unknown
-// (from OR trees over the interval widths instead of a compare and select per
-// pixel): any pixel, any of pixels 8..15 (the fix-up chain's second half),
-// any of the last three (the tail the next lane or wave starts from).  (A vote
-// after pixel 7 switching the wave to the exact step when every lane's last
-// three pixels were exact was neutral: 18.73 vs 18.64 ms at 512 frames,
-// profiles/r05w_ab_flow_spec.log.)
-struct SpecUnk { uint32_t any, hi, tail; };
-template <int S, bool CUR>
-__device__ __forceinline__ SpecUnk rows_spec_unk(IvS (&v)[S], IvS r0, IvS r1, IvS r2, const uint32_t (&w)[S],
-                                                 const uint32_t (&prev)[S]) {
-  static_assert(S == 16, "halves of eight pixels");
-#pragma unroll
-  for (int p = 0; p < S; ++p) {
-    const IvS l1 = p >= 1 ? v[p - 1] : r0;
-    const IvS l2 = p >= 2 ? v[p - 2] : (p == 1 ? r0 : r1);
-    const IvS l3 = p >= 3 ? v[p - 3] : (p == 2 ? r0 : (p == 1 ? r1 : r2));
-    v[p] = rows_step<CUR>(l1, l2, l3, prev[p], w[p]);
-  }
-  const uint32_t tail = v[13].len | v[14].len | v[15].len;
-  const uint32_t hi = tail | v[8].len | v[9].len | v[10].len | v[11].len | v[12].len;
-  const uint32_t lo = v[0].len | v[1].len | v[2].len | v[3].len | v[4].len | v[5].len | v[6].len | v[7].len;
-  return SpecUnk{lo | hi, hi, tail};
-}
-// Exact recompute of pixels 0..7 and, when some lane with `hi` goes, 8..15,
-// of the lanes with `go` (their entry is exact); the second half
-// only when some lane of the wave still has unknown pixels there (one vote per
-// round: 512 x 4K reconstruct -1 %, 1024 x 1080p -2 %, profiles/r05v_ab_chunks.log;
-// votes every four pixels cost more than they saved at one frame per CU).
-template <int S>
-__device__ __forceinline__ void rows_chain_upto(IvS (&v)[S], IvS r0, IvS r1, IvS r2, const uint32_t (&w)[S],
-                                                const uint32_t (&prev)[S], bool go, bool hi) {
-  auto step = [&](int p) {
-    const uint32_t l1 = p >= 1 ? v[p - 1].lo : r0.lo;
-    const uint32_t l2 = p >= 2 ? v[p - 2].lo : (p == 1 ? r0.lo : r1.lo);
-    const uint32_t l3 = p >= 3 ? v[p - 3].lo : (p == 2 ? r0.lo : (p == 1 ? r1.lo : r2.lo));
-    const uint32_t n = rows_step_exact(l1, l2, l3, prev[p], w[p]);
-    // a lane with an exact entry recomputes every pixel of the half (the ones
-    // past its last unknown come out equal): one select on a lane mask per
-    // pixel instead of a compare and a select (with the caller's asm pin of
-    // the words, which cost a copy of each per round, removed: 512 x 4K
-    // reconstruct 17.53 -> 16.86 ms, one 4K frame 9.56 -> 9.08,
-    // profiles/r05zq_ab_flow_chain.log)
-    v[p].lo = go ? n : v[p].lo;
-  };
-#pragma unroll
-  for (int p = 0; p < 8; ++p) step(p);
-  if (__ballot(go && hi) != 0ull) {
-#pragma unroll
-    for (int p = 8; p < 16; ++p) step(p);
-  }
-}
-__global__ __launch_bounds__(FLOW_THREADS) void dec_rows_flow(DecArgs a) {
-  constexpr int S = ROWS_SEG;
-  extern __shared__ __attribute__((aligned(16))) uint32_t sm[];
-  FlowCtl& C = *reinterpret_cast<FlowCtl*>(sm);
-  constexpr uint32_t CTL_WORDS = sizeof(FlowCtl) / 4;
-  constexpr uint32_t ZERO_IDX = offsetof(FlowCtl, zero) / 4;
-  const uint32_t W = a.W, H = a.H, f = blockIdx.x;
-  const uint32_t RS = rows_ring_stride(W);
-  const uint32_t RB = CTL_WORDS + ROWS_RB;   // sm index of ring slot 0, pixel 0
-  const uint32_t RM = a.flow_ring - 1u;      // ring rows - 1 (4 or 8 rows)
-  uint32_t* const ring = sm + RB;
-  for (uint32_t i = threadIdx.x; i < CTL_WORDS; i += blockDim.x) sm[i] = 0u;
-  __syncthreads();
-  if (a.status[f] != 0) return;   // block-uniform
-  const uint32_t nseg = (W + S - 1) / S, WPR = (nseg + 63) / 64, K = a.flow_k;
-  const uint32_t wid = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-  if (wid >= K * WPR) return;   // no barrier below this point
-  // tests (NICE_OPT_TEST_FLOW_ABSENT): the block's last wave never starts, as
-  // if it were not resident, so the others' waits time out into the fallback
-  if (a.test_absent_strip && wid == K * WPR - 1) return;
-  const uint32_t g = wid / WPR, w = wid - g * WPR, lastw = WPR - 1;
-  const uint32_t seg = w * 64u + lane;
-  const bool active = seg < nseg;
-  const uint32_t x0 = seg * S;
-  const int nvalid = active ? (int)min((uint32_t)S, W - x0) : 0;
-  const uint32_t* recs = a.recs + (uint64_t)f * a.rec_stride;
-  uint8_t* outp = a.px_out + (uint64_t)f * a.px_stride;
-  const uint32_t OC = a.out_channels;
-  const uint32_t alpha = (a.flags & NICE_DEC_ALPHA_FILL_FF) ? 0xFF000000u : 0u;
-  const uint32_t asel = alpha ? 0x0D060100u : 0x0C060100u;   // unspread3_perm
-  const bool vec_rec = (W & 3u) == 0 && nvalid == S;
-  const bool vec_out = (OC == 4 && (W & 3u) == 0 && nvalid == S) ||
-                       (OC == 3 && (W & 15u) == 0 && nvalid == S);
-  const uint32_t full = (1u << WPR) - 1u;
-  const uint32_t depmask = w == 0 ? full : ((((7u << w) >> 1) & full) | (w == lastw ? 1u : 0u));
-  const bool curlane = active && x0 + S + 2u >= W;   // words that can reference row y itself (W_CUR)
-  const bool wave_cur = __any(curlane);
-  uint2* const rtab = reinterpret_cast<uint2*>(C.rtab[wid]);
-  const uint32_t lb = 17u * seg;
-  uint32_t rn[S];
-  auto load_recs = [&](uint32_t y) {
-    const uint32_t* rrow = recs + (uint64_t)y * W + x0;
-    if (vec_rec) {
-#pragma unroll
-      for (int q = 0; q < S / 4; ++q) {
-        const uint4 t = reinterpret_cast<const uint4*>(rrow)[q];
-        rn[4 * q] = t.x; rn[4 * q + 1] = t.y; rn[4 * q + 2] = t.z; rn[4 * q + 3] = t.w;
-      }
-    } else if (nvalid > 0) {
-#pragma unroll
-      for (int p = 0; p < S; ++p) rn[p] = p < nvalid ? rrow[p] : REC_RUN;
-    } else {
-#pragma unroll
-      for (int p = 0; p < S; ++p) rn[p] = REC_RUN;
-    }
-  };
-  if (g < H) load_recs(g);
-  bool ok = true;
-#ifdef NICE_FLOW_STATS   // cycle split per wave position (NICE_DEC_STATS=1): stats[64 + 8 w + k]
-  unsigned long long ts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#define FLOW_T(k) { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); ts[k] += t_ - tlast; tlast = t_; }
-  unsigned long long tlast = __builtin_amdgcn_s_memtime();
-#else
-#define FLOW_T(k)
-#endif
-  for (uint32_t y = g; y < H && ok; y += K) {
-    const uint32_t s = y & (FLOW_SLOTS - 1u);                              // stamps
-    const uint32_t rs = y & RM, rsp = (y - 1u) & RM;   // ring rows
-    // ---- pre-pass, part 1 (no pixel values): the row's class table, each
-    // record's constant and kind bits, and the ring index of its reference
-    if (lane < 16) {
-      const uint32_t c = lane;
-      const unsigned long long kinds = y == 0 ? ROWS_KIND_Y0 : ROWS_KIND;
-      const uint32_t rows = (CLS_ROWS_PACK >> (2 * c)) & 3u, dxp3 = (uint32_t)(CLS_PX_PACK >> (3 * c)) & 7u;
-      rtab[c] = make_uint2((((uint32_t)(kinds >> (4u * c)) & 15u) << 28) | dxp3,
-                           RB + ((y - rows) & RM) * RS + 3u - dxp3);
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
-    uint32_t wk[S], ad[S];
-#pragma unroll
-    for (int p = 0; p < S; ++p) {
-      const uint32_t r = rec_canon(rn[p], a.rec_tag);
-      const uint32_t cls = rec_cls(r);   // 0..13
-      const uint2 e = rtab[cls];
-      uint32_t idx = lb + e.y + (uint32_t)p;
-      if (p < 3 || p > S - 4) idx += (uint32_t)((int)(p + 3u - (e.x & 7u)) >> 4);   // padding word crossed
-      ad[p] = cls >= 4u ? idx : ZERO_IDX;
-      // kind bits | the constant (already spread by the writers): one bit-field
-      // insert (e.x holds only kind bits 28..31 and dxp3 in bits 0..2, which
-      // the constant's mask covers)
-      uint32_t kw;
-      asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(kw) : "s"(REC_K), "v"(r), "v"(e.x));
-      wk[p] = kw;
-    }
-    // references past the row end into row y itself (pixels 0..2): only the
-    // wave holding the row's last columns (a wave-uniform branch: as a lane
-    // branch the compiler if-converted it into every wave's pre-pass once the
-    // record constant no longer needed spreading here, +2 % reconstruct)
-    if (wave_cur) {
-#pragma unroll
-      for (int p = 0; p < S; ++p) {
-        const uint32_t r = rec_canon(rn[p], a.rec_tag);
-        const uint32_t cls = rec_cls(r);
-        const uint32_t tx = x0 + p + 3u - ((uint32_t)(CLS_PX_PACK >> (3u * cls)) & 7u);
-        const bool cur = curlane && cls >= 4u && ((CLS_ROWS_PACK >> (2u * cls)) & 3u) == 1u && tx >= W;
-        wk[p] = cur ? (W_CUR | rec_c(r) | ((tx - W) << 8)) : wk[p];
-        ad[p] = cur ? ZERO_IDX : ad[p];
-      }
-    }
-    FLOW_T(0)
-    // ---- wait for the rows above
-    if (y > 0 && !flow_wait(C, C.fin[(y - 1u) & (FLOW_SLOTS - 1u)], depmask, y)) { ok = false; break; }
-    // wave priorities (round 6): the row's pass once the rows above are in
-    // before the waves still decoding records or storing the raster, and the
-    // fix-up chain -- the row's serial path -- before both (512 x 4K
-    // reconstruct 15.54 -> 14.48 ms, one 4K frame 8.43 -> 7.92;
-    // profiles/r06ze_ab_flow_prio.log, r06zf_ab_flow_prio2.log)
-    __builtin_amdgcn_s_setprio(1);
-    FLOW_T(1)
-    // ---- pre-pass, part 2: reference values, the row above, the entry
-    uint32_t wv[S], prev[S];
-#pragma unroll
-    for (int p = 0; p < S; ++p) {
-      const uint32_t o = sm[ad[p]];
-      wv[p] = (wk[p] & ~SP_K) | ((o + wk[p]) & SP_K);
-    }
-    uint32_t* const pr = ring + rsp * RS;
-#pragma unroll
-    for (int p = 0; p < S; ++p) prev[p] = y > 0 ? pr[lb + p] : 0u;
-    IvS r0{0u, SP_K}, r1{0u, SP_K}, r2{0u, SP_K};
-    if (seg == 0) {
-      if (y == 0) {
-        r0 = r1 = r2 = ivs_exact(0u);
-      } else {
-        r0 = ivs_exact(pr[(W - 1) + ((W - 1) >> 4)]);
-        r1 = ivs_exact(pr[(W - 2) + ((W - 2) >> 4)]);
-        r2 = ivs_exact(pr[(W - 3) + ((W - 3) >> 4)]);
-      }
-    }
-    FLOW_T(2)
-    // ---- speculative pass
-    IvS v[S];
-    // (a wave without the row's last columns skips the W_CUR width term:
-    // 512 x 4K reconstruct -1 %, profiles/r05zt_ab_flow_curspec.log)
-    const SpecUnk su = wave_cur ? rows_spec_unk<S, true>(v, r0, r1, r2, wv, prev)
-                                : rows_spec_unk<S, false>(v, r0, r1, r2, wv, prev);
-    bool fin = !active || su.any == 0u;
-    bool tex = !active || su.tail == 0u;
-    const bool unk_hi = su.hi != 0u;
-    if (w == 0 && lane == 0) {   // the row's first three pixels (lane 0: exact entry)
-      C.head[s][0] = v[0].lo; C.head[s][1] = v[1].lo; C.head[s][2] = v[2].lo;
-      flow_publish(&C.hst[s], y + 1u);
-    }
-    bool tpub = w == lastw;   // the last wave's tail feeds no wave
-    auto pub_tail = [&]() {
-      if (!tpub && __builtin_amdgcn_readlane((int)tex, 63)) {
-        if (lane == 63) {
-          C.tail[s][w][0] = v[S - 1].lo; C.tail[s][w][1] = v[S - 2].lo; C.tail[s][w][2] = v[S - 3].lo;
-          flow_publish(&C.tst[s][w], y + 1u);
-        }
-        tpub = true;
-      }
-    };
-    pub_tail();
-    FLOW_T(3)
-    // ---- fix-up rounds inside the wave
-    __builtin_amdgcn_s_setprio(2);
-    bool cur_done = !wave_cur;
-    unsigned long long t0 = 0;
-    for (uint32_t n = 0;; ++n) {
-      if (__ballot(!fin) == 0ull) break;
-      if (!cur_done && flow_peek(&C.hst[s]) >= y + 1u) {
-        flow_acquire();
-        const uint32_t h0 = C.head[s][0], h1 = C.head[s][1], h2 = C.head[s][2];
-        if (curlane) {
-#pragma unroll
-          for (int p = 0; p < S; ++p) {
-            const uint32_t k = (wv[p] >> 8) & 3u;
-            const uint32_t hv = k == 0u ? h0 : k == 1u ? h1 : h2;
-            wv[p] = (wv[p] & W_CUR) ? ((hv + (wv[p] & SP_K)) & SP_K) : wv[p];
-          }
-        }
-        cur_done = true;
-      }
-      IvS l0{shfl_up1(v[S - 1].lo), 0u}, l1{shfl_up1(v[S - 2].lo), 0u}, l2{shfl_up1(v[S - 3].lo), 0u};
-      bool lex = shfl_up1(tex ? 1u : 0u) != 0u;
-      if (lane == 0) {
-        lex = false;
-        if (w > 0 && flow_peek(&C.tst[s][w - 1]) >= y + 1u) {
-          flow_acquire();
-          l0.lo = C.tail[s][w - 1][0]; l1.lo = C.tail[s][w - 1][1]; l2.lo = C.tail[s][w - 1][2];
-          lex = true;
-        }
-      }
-      const bool go = !fin && lex && (cur_done || !curlane);
-      if (__ballot(go) != 0ull) {
-        rows_chain_upto<S>(v, l0, l1, l2, wv, prev, go, unk_hi);
-        if (go) {
-          fin = true;
-          tex = true;
-        }
-        pub_tail();
-#ifdef NICE_FLOW_STATS
-        ts[6] += 1;
-#endif
-      } else {
-        // nothing to do until the left wave's tail or the row head arrive
-        if ((n & 31u) == 0u) {
-          if (flow_peek(&C.abort)) { ok = false; break; }
-          const unsigned long long t = __builtin_amdgcn_s_memrealtime();
-          if (t0 == 0) t0 = t;
-          else if (t - t0 > FLOW_TIMEOUT) {
-            atomicOr(&C.abort, 1u);
-            atomicCAS(&C.err, 0, FLOW_REDO);
-            ok = false;
-            break;
-          }
-        }
-        __builtin_amdgcn_s_sleep(1);
-      }
-    }
-    FLOW_T(4)
-    if (!ok) break;
-    if (C.err) { atomicOr(&C.abort, 1u); ok = false; break; }
-    // ---- the ring row, its halos, the stamp
-    if (active) {
-      uint32_t* rr = ring + rs * RS + lb;
-#pragma unroll
-      for (int p = 0; p < S; ++p) rr[p] = v[p].lo;   // padding pixels land in the row's spare words
-      if (seg == 0 && y > 0) {   // row y-1's right halo: this row's first three pixels
-#pragma unroll
-        for (int k = 0; k < 3; ++k) pr[(W + k) + ((W + k) >> 4)] = v[k].lo;
-      }
-    }
-    if (wave_cur) {   // row y+1's left halo (words -4..-2): this row's columns W-3..W-1, copied
-      // from the ring words just written by the wave holding each of them
-      // (a 4-row ring puts it over row y-3's left halo, which row y's first
-      // wave reads in its pre-pass: wait for that wave's first pixels)
-      if (RM < 7u && !flow_wait(C, &C.hst[s], 1u, y + 1u)) { ok = false; break; }
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
-      const uint32_t col = W - 3u + lane;
-      if (lane < 3u && (col / S) / 64u == w)
-        ring[((y + 1u) & RM) * RS + lane - 4] = ring[rs * RS + col + (col >> 4)];
-    }
-    if (lane == 0) flow_publish(&C.fin[s][w], y + 1u);
-    __builtin_amdgcn_s_setprio(0);
-    FLOW_T(5)
-    // ---- off the critical path: the next row's records, the raster
-    if (y + K < H) load_recs(y + K);
-    if (active) {
-      const uint64_t pix = (uint64_t)y * W + x0;
-      if (vec_out && OC == 4) {
-        uint4* o = reinterpret_cast<uint4*>(outp + pix * 4);
-#pragma unroll
-        for (int q = 0; q < S / 4; ++q)
-          o[q] = make_uint4(unspread3_perm(v[4 * q].lo, asel), unspread3_perm(v[4 * q + 1].lo, asel),
-                            unspread3_perm(v[4 * q + 2].lo, asel), unspread3_perm(v[4 * q + 3].lo, asel));
-      } else if (vec_out) {
-        uint32_t b[3 * S / 4];
-#pragma unroll
-        for (int q = 0; q < S / 4; ++q) {
-          const uint32_t u0 = unspread3_perm(v[4 * q].lo, 0x0C060100u), u1 = unspread3_perm(v[4 * q + 1].lo, 0x0C060100u);
-          const uint32_t u2 = unspread3_perm(v[4 * q + 2].lo, 0x0C060100u), u3 = unspread3_perm(v[4 * q + 3].lo, 0x0C060100u);
-          b[3 * q] = __builtin_amdgcn_perm(u1, u0, 0x04020100u);       // R0 G0 B0 R1
-          b[3 * q + 1] = __builtin_amdgcn_perm(u2, u1, 0x05040201u);   // G1 B1 R2 G2
-          b[3 * q + 2] = __builtin_amdgcn_perm(u3, u2, 0x06050402u);   // B2 R3 G3 B3
-        }
-        uint4* o = reinterpret_cast<uint4*>(outp + pix * 3);
-#pragma unroll
-        for (int q = 0; q < 3 * S / 16; ++q) o[q] = make_uint4(b[4 * q], b[4 * q + 1], b[4 * q + 2], b[4 * q + 3]);
-      } else if (OC == 4) {
-        uint32_t* o32 = reinterpret_cast<uint32_t*>(outp + pix * 4);
-#pragma unroll
-        for (int p = 0; p < S; ++p)
-          if (p < nvalid) o32[p] = unspread3(v[p].lo) | alpha;
-      } else {
-        uint8_t* o8 = outp + pix * 3;
-#pragma unroll
-        for (int p = 0; p < S; ++p) {
-          if (p < nvalid) {
-            const uint32_t u = unspread3(v[p].lo);
-            o8[3 * p] = (uint8_t)u; o8[3 * p + 1] = (uint8_t)(u >> 8); o8[3 * p + 2] = (uint8_t)(u >> 16);
-          }
-        }
-      }
-    }
-  }
-  if (lane == 0) {
-    const int e = __hip_atomic_load(&C.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    if (e == FLOW_REDO && a.hand_abort) atomicCAS(&a.hand_abort[f], 0u, SPLIT_REDO);
-    else if (e) set_status(&a.status[f], e == FLOW_REDO ? NICE_E_HIP : e);
-  }
-#ifdef NICE_FLOW_STATS
-  if (lane == 0 && a.stats) {
-    // ts[7]: rows processed; k = 0 record decode, 1 wait, 2 ring reads, 3 spec, 4 fix-up, 5 ring row + stamp, 6 fix-up rounds with work
-    ts[7] = (H > g ? (H - g + K - 1) / K : 0);
-    for (int k = 0; k < 8; ++k) atomicAdd(&a.stats[64 + 8 * w + k], ts[k]);
-  }
-#endif
-#undef FLOW_T
-}
-
-// ---------------------------------------------------------------------------
-// D5c: strip-split reconstruction for wide frames: a frame's row segments are
-// cut into k strips of <= 256 lanes, one workgroup each (one per CU), all rows
-// in order.  In raster order the strip-rows ("units" (y, j)) form one chain:
-// a unit's left neighbour is (y, j-1), or (y-1, k-1) for j = 0 (the wrap of
-// code.rs:412-413), its right neighbour (y, j+1), or (y+1, 0).  Each block
-// keeps a 4-row ring of its columns plus three halo columns on each side in
-// LDS; ring row r's left halo is the last three pixels of r's left neighbour
-// unit, its right halo the first three of r's right neighbour unit -- so every
-// reference (rows 1..3 back, +-3 pixels, code.rs:141-145) is one ring read
-// with no wrap logic, and lane 0's entry (the three pixels before the strip)
-// is ring row y's left halo.  Units publish their first and last three pixels
-// as soon as they are exact (after the speculative pass, usually without
-// their entry) as 8-byte {row + 1, value} granules (agent-scope relaxed
-// atomics: sc1 stores / loads); a block waits for nothing before its
-// speculative pass except the halos of rows y-2 and y-3 (published long
-// before); halo words of row y-1 not yet published and the entry are unknown
-// intervals in the speculative pass, resolved in the fix-up rounds, which poll
-// for them.  Every dependency points to a unit earlier in raster order, so
-// with every block resident (the host launches at most one block per CU for
-// half the CUs) the earliest unfinished unit always progresses.  Polls give up
-// after SPLIT_TIMEOUT (a frame-wide abort flag stops the other strips early
-// on an error).
-// ---------------------------------------------------------------------------
-// (SPLIT_THREADS, SPLIT_GRAN, split_ring_stride and the LDS layout: nice_geom.h)
-// s_memrealtime ticks (100 MHz): 0.2 s.  A wait this long means a strip's
-// neighbour is not resident (other kernels hold the CUs): the frame is handed
-// to the fallback launch (SPLIT_REDO), not failed
-constexpr unsigned long long SPLIT_TIMEOUT = 20000000ull;
-constexpr int SPLIT_QUIET = -1000, SPLIT_TIMED_OUT = -1001;   // block-local err codes
-__device__ __forceinline__ uint32_t sr_idx(uint32_t lc3) { return lc3 + (lc3 >> 4); }
-
-__device__ __forceinline__ void hand_put(unsigned long long* p, uint32_t row, uint32_t v) {
-  __hip_atomic_store(p, ((unsigned long long)(row + 1u) << 32) | v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ unsigned long long hand_get(const unsigned long long* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-struct SplitGeo {
-  uint32_t f, j, k, W, H, sw, RS;
-  unsigned long long* hand;   // frame f's granules
-  // granule i of unit (y, jj)
-  __device__ __forceinline__ unsigned long long* g(uint32_t y, uint32_t jj, uint32_t i) const {
-    return hand + ((uint64_t)y * k + jj) * SPLIT_GRAN + i;
-  }
-  // source granule of halo pixel i (0..2) of ring row r (>= -1: ring row -1's
-  // right halo is row 0's first pixels when j = k-1 -- pixel W-3 of row 0
-  // may reference pixel 0 through offset W-3), side 0 (left) / 1 (right);
-  // false when the source lies outside the image (never referenced)
-  __device__ __forceinline__ bool src(int r, uint32_t side, uint32_t i, unsigned long long*& p,
-                                      uint32_t& srow) const {
-    if (side == 0) {
-      if (j > 0) {
-        if (r < 0) return false;
-        p = g((uint32_t)r, j - 1, 4 + i); srow = (uint32_t)r; return true;
-      }
-      if (r < 1) return false;
-      p = g((uint32_t)r - 1, k - 1, 4 + i); srow = (uint32_t)r - 1; return true;
-    }
-    if (j + 1 < k) {
-      if (r < 0) return false;
-      p = g((uint32_t)r, j + 1, i); srow = (uint32_t)r; return true;
-    }
-    if (r < -1 || r + 1 >= (int)H) return false;
-    p = g((uint32_t)(r + 1), 0, i); srow = (uint32_t)(r + 1); return true;
-  }
-};
-
-// A wave-0 poll in two halves, so the granule loads' latency overlaps other
-// work.  The halo items of row y: t = 0..5 ring rows y-3, y-3, y-2, y-2, y-1,
-// y-1 (left, right), t = 6 row y's left halo (the entry); lanes 3t..3t+2 take
-// item t.  issue() loads the granules of the items in `mask` whose hv word
-// does not say present; commit() copies every item whose three tags match
-// into the ring and sets its hv word.  hv[slot * 2 + side]: the ring row
-// (>= -1) whose halo the slot holds, + 2 (0: none).
-struct HaloPoll {
-  unsigned long long v;
-  int r;
-  uint32_t side, i, srow;   // side 2: no item on this lane
-  bool ex;
-  __device__ __forceinline__ void issue(const SplitGeo& G, const uint32_t* hv, uint32_t lane, uint32_t y,
-                                        uint32_t mask) {
-    side = 2u;
-    ex = false;
-    v = 0;
-    const uint32_t t = lane / 3u;
-    i = lane - 3u * t;
-    if (t >= 7u || !((mask >> t) & 1u)) return;
-    const int rr = t < 6u ? (int)y - 3 + (int)(t >> 1) : (int)y;
-    const uint32_t sd = t < 6u ? (t & 1u) : 0u;
-    if (rr < -1 || hv[((uint32_t)rr & 3u) * 2u + sd] == (uint32_t)(rr + 2)) return;
-    r = rr;
-    side = sd;
-    unsigned long long* p = nullptr;
-    ex = G.src(rr, sd, i, p, srow);
-    if (ex) v = hand_get(p);
-  }
-  __device__ __forceinline__ void commit(const SplitGeo& G, uint32_t* ring, uint32_t* hv, uint32_t lane) {
-    const bool ok = side < 2u && (!ex || (uint32_t)(v >> 32) == srow + 1u);
-    if (ok) ring[((uint32_t)r & 3u) * G.RS + sr_idx(side ? G.sw + 3u + i : i)] = (uint32_t)v;
-    const unsigned long long m = __ballot(ok);
-    if (ok && i == 0u && ((m >> lane) & 7ull) == 7ull) hv[((uint32_t)r & 3u) * 2u + side] = (uint32_t)(r + 2);
-    side = 2u;
-  }
-};
-// present bits (t = 0..6) of row y's halo items
-__device__ __forceinline__ uint32_t halo_have(const uint32_t* hv, uint32_t y) {
-  uint32_t m = 0;
-#pragma unroll
-  for (uint32_t t = 0; t < 7u; ++t) {
-    const int rr = t < 6u ? (int)y - 3 + (int)(t >> 1) : (int)y;
-    const uint32_t sd = t < 6u ? (t & 1u) : 0u;
-    if (rr < -1 || hv[((uint32_t)rr & 3u) * 2u + sd] == (uint32_t)(rr + 2)) m |= 1u << t;
-  }
-  return m;
-}
-
-__global__ __launch_bounds__(SPLIT_THREADS) void dec_rows_split(DecArgs a) {
-  constexpr int S = ROWS_SEG;
-  extern __shared__ __attribute__((aligned(16))) uint32_t sm[];
-  __shared__ uint32_t clsw[32];
-  __shared__ uint32_t hv[8];     // ring slot halo state (row + 1 per slot and side)
-  __shared__ uint32_t pend[2];
-  __shared__ int err;
-  const uint32_t k = a.strips;
-  const uint32_t f = a.split_f0 + blockIdx.x / k, j = blockIdx.x % k;
-  if (a.test_absent_strip && j == k - 1) return;   // block-uniform (tests only)
-  const uint32_t W = a.W, H = a.H;
-  const uint32_t nseg = (W + S - 1) / S;
-  const uint32_t sps = (nseg + k - 1) / k;
-  const uint32_t s0 = j * sps, s1 = min(nseg, s0 + sps);
-  const uint32_t c0 = s0 * S, sw = min(W, s1 * S) - c0;
-  const uint32_t lane = threadIdx.x;
-  const uint32_t nl = s1 - s0;
-  const bool active = lane < nl;
-  const uint32_t xl0 = lane * S;
-  const int nvalid = active ? (int)min((uint32_t)S, sw - xl0) : 0;
-  const SplitGeo G{f, j, k, W, H, sw, split_ring_stride(sw), a.hand + (uint64_t)f * H * k * SPLIT_GRAN};
-  const uint32_t RS = G.RS;
-  uint32_t* tails = sm;                              // SPLIT_THREADS x {lo, len} x 3
-  uint32_t* flags = sm + SPLIT_FLAGS;                // SPLIT_THREADS
-  uint32_t* ring = sm + SPLIT_RING;                  // 4 x RS
-  if (threadIdx.x < 32) {
-    const uint32_t c = threadIdx.x & 15u;
-    const unsigned long long kinds = threadIdx.x >= 16 ? ROWS_KIND_Y0 : ROWS_KIND;
-    clsw[threadIdx.x] = ((CLS_ROWS_PACK >> (2 * c)) & 3u) | (uint32_t)((CLS_PX_PACK >> (3 * c)) & 7u) << 2 |
-                        ((uint32_t)(kinds >> (4u * c)) & 15u) << 28;
-  }
-  if (threadIdx.x < 8) hv[threadIdx.x] = 0;
-  if (lane == 0) err = 0;
-  if (a.status[f] != 0) return;   // block-uniform
-  uint32_t* abort_f = a.hand_abort + f;
-  const uint32_t* recs = a.recs + (uint64_t)f * a.rec_stride + c0;
-  uint8_t* outp = a.px_out + (uint64_t)f * a.px_stride;
-  const uint32_t OC = a.out_channels;
-  const uint32_t alpha = (a.flags & NICE_DEC_ALPHA_FILL_FF) ? 0xFF000000u : 0u;
-  const uint32_t asel = alpha ? 0x0D060100u : 0x0C060100u;   // unspread3_perm
-  const bool vec_rec = ((W | c0) & 3u) == 0 && nvalid == S;
-  const bool vec_out = (OC == 4 && ((W | c0) & 3u) == 0 && nvalid == S) ||
-                       (OC == 3 && ((W | c0) & 15u) == 0 && nvalid == S);
-  uint32_t prev[S], rn[S];
-#pragma unroll
-  for (int p = 0; p < S; ++p) prev[p] = 0;
-  auto load_recs = [&](uint32_t y) {
-    const uint32_t* rrow = recs + (uint64_t)y * W + xl0;
-    if (vec_rec) {
-#pragma unroll
-      for (int q = 0; q < S / 4; ++q) {
-        const uint4 t = reinterpret_cast<const uint4*>(rrow)[q];
-        rn[4 * q] = t.x; rn[4 * q + 1] = t.y; rn[4 * q + 2] = t.z; rn[4 * q + 3] = t.w;
-      }
-    } else if (nvalid > 0) {
-#pragma unroll
-      for (int p = 0; p < S; ++p) rn[p] = p < nvalid ? rrow[p] : REC_RUN;
-    } else {
-#pragma unroll
-      for (int p = 0; p < S; ++p) rn[p] = REC_RUN;
-    }
-  };
-  if (H > 0) load_recs(0);
-  __syncthreads();
-  unsigned long long t_row = 0;   // when this row's waits began
-  // wave 0: gives up (error) on a timeout or another strip's abort
-  auto give_up = [&]() -> bool {
-    if (__hip_atomic_load(abort_f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) {
-      if (lane == 0) atomicCAS(&err, 0, SPLIT_QUIET);   // another strip failed or timed out: exit quietly
-      return true;
-    }
-    if (__builtin_amdgcn_s_memrealtime() - t_row > SPLIT_TIMEOUT) {
-      if (lane == 0) atomicCAS(&err, 0, SPLIT_TIMED_OUT);
-      return true;
-    }
-    return false;
-  };
-  HaloPoll HP;
-  bool pending_poll = false;   // wave 0: HP holds issued loads
-  // timing counters (NICE_DEC_STATS=1) only in -DNICE_ROWS_STATS builds
-#ifdef NICE_ROWS_STATS
-  unsigned long long* const stats = a.stats;
-#else
-  constexpr unsigned long long* stats = nullptr;
-#endif
-  unsigned long long c_entry = 0, c_right = 0;
-  unsigned long long c_wait = 0, c_spec = 0, c_fix = 0, c_emit = 0, n_rounds = 0, n_polls = 0, n_noentry = 0;
-  uint32_t y = 0;
-  for (; y < H; ++y) {
-    const unsigned long long cc0 = stats ? __builtin_amdgcn_s_memtime() : 0;
-    // ---- halos: rows y-2 and y-3 (wait), row y-1 and the entry (try)
-    t_row = __builtin_amdgcn_s_memrealtime();
-    if (lane == 0) {   // slot y & 3 held row y-4: free it for row y
-      hv[(y & 3u) * 2u] = 0u;
-      hv[(y & 3u) * 2u + 1u] = 0u;
-    }
-    if (lane < 64) {
-      // the loads issued at the end of the previous row, then rows y-2 and
-      // y-3 (items 0..3) until present
-      if (pending_poll) HP.commit(G, ring, hv, lane);
-      pending_poll = false;
-      while (true) {
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
-        const uint32_t miss = ~halo_have(hv, y) & 15u;
-        if (!miss) break;
-        if (give_up()) break;
-        HP.issue(G, hv, lane, y, miss);
-        HP.commit(G, ring, hv, lane);
-        if (stats) ++n_polls;
-        __builtin_amdgcn_s_sleep(1);
-      }
-    }
-    __syncthreads();
-    if (err) break;
-    const uint32_t ym1 = (y - 1u) & 3u;
-    bool hl1 = hv[ym1 * 2u] == y + 1u;               // row y-1's halos present (row -1 at y = 0)
-    bool hr1 = hv[ym1 * 2u + 1u] == y + 1u;
-    bool eok = hv[(y & 3u) * 2u] == y + 2u;          // the entry (row y's left halo)
-    const unsigned long long cc1 = stats ? __builtin_amdgcn_s_memtime() : 0;
-    if (stats && !eok) ++n_noentry;
-    // ---- pre-pass: records -> per-pixel words; a reference into a halo of
-    // row y-1 not yet present is marked W_CUR (unknown) with its halo slot
-    // (index in bits 8..9, side in bit 19) and resolved in the fix-up rounds
-    const uint32_t* const cwt = clsw + (y == 0 ? 16 : 0);
-    uint32_t w[S];
-    bool npend = false;
-#pragma unroll
-    for (int p = 0; p < S; ++p) {
-      const uint32_t r = rec_canon(rn[p], a.rec_tag);
-      const uint32_t cls = rec_cls(r);
-      const uint32_t cw = cwt[cls];
-      const uint32_t rows = cw & 3u;
-      const uint32_t lc3 = xl0 + (uint32_t)p + 6u - ((cw >> 2) & 7u);   // local column + 3 - pixels back
-      const bool up = cls >= 4;
-      const bool pl = up && rows == 1u && lc3 < 3u && !hl1;
-      const bool pr = up && rows == 1u && lc3 >= sw + 3u && !hr1;
-      const uint32_t lcc = min(lc3, sw + 5u);
-      const uint32_t o = ring[__umul24((y - rows) & 3u, RS) + sr_idx(lcc)];
-      const uint32_t c = rec_c(r);
-      const bool cur = pl || pr;
-      const uint32_t hslot = pl ? lc3 : (lc3 - sw - 3u);
-      const uint32_t kb = (cw & 0xF0000000u) | (cur ? W_CUR : 0u);
-      w[p] = kb | ((up && !cur) ? ((o + c) & SP_K) : c) | (cur ? ((hslot << 8) | (pr ? (1u << 19) : 0u)) : 0u);
-      npend = npend || cur;
-    }
-    // ---- entry: exact when present (strip 0 of row 0: zeros), else unknown
-    IvS r0{0u, SP_K}, r1{0u, SP_K}, r2{0u, SP_K};
-    if (lane == 0) {
-      if (y == 0 && j == 0) {
-        r0 = r1 = r2 = ivs_exact(0u);
-      } else if (eok) {
-        const uint32_t* hr = ring + (y & 3u) * RS;
-        r0 = ivs_exact(hr[sr_idx(2)]); r1 = ivs_exact(hr[sr_idx(1)]); r2 = ivs_exact(hr[sr_idx(0)]);
-      }
-    }
-    if (y + 1 < H) load_recs(y + 1);
-    // ---- speculative pass
-    IvS v[S];
-    int lu = rows_spec<S>(v, r0, r1, r2, w, prev);
-    if (active) {
-      uint32_t* t = tails + lane * 6;
-      t[0] = v[S - 1].lo; t[1] = v[S - 1].len;
-      t[2] = v[S - 2].lo; t[3] = v[S - 2].len;
-      t[4] = v[S - 3].lo; t[5] = v[S - 3].len;
-      flags[lane] = (lu < S - 3) ? 1u : 0u;
-    }
-    if (lane == 0) { pend[0] = 0; pend[1] = 0; }
-    bool fin = !active || lu < 0;
-    // the unit's first / last three pixels, published once exact
-    uint32_t pub = 0;
-    const bool pub_lane = active && (lane == 0 || xl0 + S + 3u > sw);
-    auto publish = [&]() {
-      if (!pub_lane) return;
-#pragma unroll
-      for (int p = 0; p < S; ++p) {
-        const uint32_t x = xl0 + (uint32_t)p;
-        const uint32_t il = x + 3u - sw;   // 0..2 for the last three pixels
-        if (x < 3u && !((pub >> x) & 1u) && v[p].len == 0u) {
-          hand_put(G.g(y, j, x), y, v[p].lo);
-          pub |= 1u << x;
-        }
-        if (x < sw && il < 3u && !((pub >> (4u + il)) & 1u) && v[p].len == 0u) {
-          hand_put(G.g(y, j, 4u + il), y, v[p].lo);
-          pub |= 16u << il;
-        }
-      }
-    };
-    publish();
-    rows_barrier<true>();
-    const unsigned long long cc2 = stats ? __builtin_amdgcn_s_memtime() : 0;
-    // ---- fix-up rounds (polling for the entry and row y-1's missing halos)
-    for (uint32_t rd = 0;; ++rd) {
-      if (stats) ++n_rounds;
-      if (!fin) atomicOr(&pend[rd & 1u], 1u);
-      if (lane < 64) {
-        // commit the loads issued last round, issue the still missing items
-        // (row y-1's halos, the entry); their latency overlaps this round
-        if (pending_poll) HP.commit(G, ring, hv, lane);
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
-        const uint32_t miss = ~halo_have(hv, y) & 0x70u;
-        pending_poll = miss != 0u;
-        if (pending_poll) {
-          HP.issue(G, hv, lane, y, miss);
-          if (stats) ++n_polls;
-          if (rd > 1u) __builtin_amdgcn_s_sleep(1);
-        }
-      }
-      if (lane < 64 && (rd & 63u) == 63u) (void)give_up();   // bounds every wait (and any logic error)
-      rows_barrier<true>();
-      if (pend[rd & 1u] == 0 || err) break;
-      if (lane == 0) pend[(rd + 1) & 1u] = 0;
-      const bool nhl = hl1 || hv[ym1 * 2u] == y + 1u, nhr = hr1 || hv[ym1 * 2u + 1u] == y + 1u;
-      bool resolved = false;
-      if (npend && ((nhl && !hl1) || (nhr && !hr1))) {
-        resolved = true;
-        // halo words now present: resolve them (their chains are unknown from
-        // there on and get recomputed below)
-        const uint32_t* hrow = ring + ym1 * RS;
-        bool still = false;
-#pragma unroll
-        for (int p = 0; p < S; ++p) {
-          if (w[p] & W_CUR) {
-            const uint32_t sd = (w[p] >> 19) & 1u, hs = (w[p] >> 8) & 3u;
-            if (sd ? nhr : nhl)
-              w[p] = (hrow[sr_idx(sd ? sw + 3u + hs : hs)] + (w[p] & SP_K)) & SP_K;
-            else
-              still = true;
-          }
-        }
-        npend = still;
-        if (!fin) { /* recompute below */ }
-      }
-      hl1 = nhl;
-      hr1 = nhr;
-      const bool neok = eok || hv[(y & 3u) * 2u] == y + 2u;
-      if (stats && neok && !eok) c_entry += __builtin_amdgcn_s_memtime() - cc2;
-      if (stats && nhr && !hr1) c_right += __builtin_amdgcn_s_memtime() - cc2;
-      eok = neok;
-      bool exact_in = false;
-      bool go = !fin;
-      if (!fin) {
-        if (lane > 0) {
-          const uint32_t* t = tails + (lane - 1) * 6;
-          r0 = IvS{t[0], t[1]}; r1 = IvS{t[2], t[3]}; r2 = IvS{t[4], t[5]};
-          exact_in = flags[lane - 1] != 0;
-        } else if (eok) {
-          const uint32_t* hr = ring + (y & 3u) * RS;
-          r0 = ivs_exact(hr[sr_idx(2)]); r1 = ivs_exact(hr[sr_idx(1)]); r2 = ivs_exact(hr[sr_idx(0)]);
-          exact_in = true;
-        }
-        exact_in = exact_in && !npend;
-        // as in dec_rows: only exact left tails (or entries) are used
-        go = exact_in;
-      }
-      (void)resolved;
-      rows_barrier<true>();
-      lu = rows_chain_exact<S>(v, r0, r1, r2, w, prev, lu, go);
-      if (go) {
-        if (lu >= 0) atomicCAS(&err, 0, NICE_E_FORMAT);
-        uint32_t* t = tails + lane * 6;
-        t[0] = v[S - 1].lo; t[1] = v[S - 1].len;
-        t[2] = v[S - 2].lo; t[3] = v[S - 2].len;
-        t[4] = v[S - 3].lo; t[5] = v[S - 3].len;
-        flags[lane] = 1u;
-        fin = true;
-      }
-      publish();
-    }
-    if (err) break;
-    // prefetch the next row's halo items (committed at its start)
-    if (lane < 64 && y + 1 < H) {
-      if (pending_poll) HP.commit(G, ring, hv, lane);
-      HP.issue(G, hv, lane, y + 1, 0x7Fu);
-      pending_poll = true;
-    }
-    const unsigned long long cc3 = stats ? __builtin_amdgcn_s_memtime() : 0;
-    // ---- emit: ring row y (local columns) and the raster
-    if (active) {
-      uint32_t* rr = ring + (y & 3u) * RS;
-      const uint64_t pix = (uint64_t)y * W + c0 + xl0;
-#pragma unroll
-      for (int p = 0; p < S; ++p) rr[sr_idx(xl0 + (uint32_t)p + 3u)] = v[p].lo;   // padding: spare words
-      if (vec_out && OC == 4) {
-        uint4* o = reinterpret_cast<uint4*>(outp + pix * 4);
-#pragma unroll
-        for (int q = 0; q < S / 4; ++q)
-          o[q] = make_uint4(unspread3_perm(v[4 * q].lo, asel), unspread3_perm(v[4 * q + 1].lo, asel),
-                            unspread3_perm(v[4 * q + 2].lo, asel), unspread3_perm(v[4 * q + 3].lo, asel));
-      } else if (vec_out) {
-        uint32_t b[3 * S / 4];
-#pragma unroll
-        for (int q = 0; q < S / 4; ++q) {
-          const uint32_t u0 = unspread3_perm(v[4 * q].lo, 0x0C060100u), u1 = unspread3_perm(v[4 * q + 1].lo, 0x0C060100u);
-          const uint32_t u2 = unspread3_perm(v[4 * q + 2].lo, 0x0C060100u), u3 = unspread3_perm(v[4 * q + 3].lo, 0x0C060100u);
-          b[3 * q] = __builtin_amdgcn_perm(u1, u0, 0x04020100u);       // R0 G0 B0 R1
-          b[3 * q + 1] = __builtin_amdgcn_perm(u2, u1, 0x05040201u);   // G1 B1 R2 G2
-          b[3 * q + 2] = __builtin_amdgcn_perm(u3, u2, 0x06050402u);   // B2 R3 G3 B3
-        }
-        uint4* o = reinterpret_cast<uint4*>(outp + pix * 3);
-#pragma unroll
-        for (int q = 0; q < 3 * S / 16; ++q) o[q] = make_uint4(b[4 * q], b[4 * q + 1], b[4 * q + 2], b[4 * q + 3]);
-      } else if (OC == 4) {
-        uint32_t* o32 = reinterpret_cast<uint32_t*>(outp + pix * 4);
-#pragma unroll
-        for (int p = 0; p < S; ++p)
-          if (p < nvalid) o32[p] = unspread3(v[p].lo) | alpha;
-      } else {
-        uint8_t* o8 = outp + pix * 3;
-#pragma unroll
-        for (int p = 0; p < S; ++p) {
-          if (p < nvalid) {
-            const uint32_t u = unspread3(v[p].lo);
-            o8[3 * p] = (uint8_t)u; o8[3 * p + 1] = (uint8_t)(u >> 8); o8[3 * p + 2] = (uint8_t)(u >> 16);
-          }
-        }
-      }
-    }
-#pragma unroll
-    for (int p = 0; p < S; ++p) prev[p] = v[p].lo;
-    rows_barrier<true>();
-    if (stats) {
-      const unsigned long long cc4 = __builtin_amdgcn_s_memtime();
-      c_wait += cc1 - cc0; c_spec += cc2 - cc1; c_fix += cc3 - cc2; c_emit += cc4 - cc3;
-    }
-  }
-  if (stats && lane == 0) {
-    atomicAdd(&stats[0], (unsigned long long)y); atomicAdd(&stats[4], n_rounds);
-    atomicAdd(&stats[5], c_wait); atomicAdd(&stats[6], c_spec); atomicAdd(&stats[7], c_fix);
-    atomicAdd(&stats[8], c_emit); atomicAdd(&stats[1], n_noentry); atomicAdd(&stats[2], n_polls);
-    atomicAdd(&stats[3], c_entry); atomicAdd(&stats[9], c_right);
-  }
-  if (lane == 0 && err) {
-    if (err == SPLIT_TIMED_OUT) {
-      // not co-resident: the fallback launch reconstructs the frame (a real
-      // error of another strip sets the status, which the fallback respects)
-      atomicCAS(abort_f, 0u, SPLIT_REDO);
-    } else if (err != SPLIT_QUIET) {
-      __hip_atomic_store(abort_f, SPLIT_ABORT_ERR, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      set_status(&a.status[f], err);
-    }
-  }
-}
-
-__global__ __launch_bounds__(64) void dec_reconstruct(DecArgs a) {
-  if (a.rows_in_lds) dec_reconstruct_body<true>(a);
-  else dec_reconstruct_body<false>(a);
-}
 
 }  // namespace nice

@@ -1,6 +1,8 @@
 """The row kernels' spread-form arithmetic after round 5's instruction cuts
-(ivs_avg, rows_step, rows_step_exact in nice_decode.hip) equals the forms it
-replaced: tools/rows_arith_check.cpp, compiled here with g++ (CPU only)."""
+(ivs_avg, rows_step, rows_step_exact: csrc/nice_rows.hpp, the header the row
+kernels of nice_rows.hip compile) equals the forms it replaced:
+tools/rows_arith_check.cpp, which includes that header by its path and is
+compiled here with g++ (CPU only)."""
 import os
 import shutil
 import subprocess

@@ -1,5 +1,5 @@
 """Host model of the row reconstructor's LDS ring addressing (dec_rows_body,
-csrc/nice_decode.hip): the table-form pre-pass reads a reference of record
+csrc/nice_rows.hip): the table-form pre-pass reads a reference of record
 class c at word 4 + slot(y - rows_c) * RS + 17 * lane + d + (d >> 4),
 d = p - px_c, with no wrap logic, because every emitted row also writes two
 halos -- lane 0 its first three pixels past the end of the row above, the last

@@ -7,7 +7,8 @@ R=$(git rev-parse --show-toplevel)
 T=$(mktemp -d /tmp/var_XXXX)
 cd "$R/fast-losless-image-compression-format_amd"
 pids=""
-for f in nice_encode nice_decode nice_capi nice_pipe nice_image; do
+for src in csrc/*.hip; do   # every HIP source, as build_ab.sh
+  f=$(basename "$src" .hip)
   /opt/rocm/bin/hipcc -O3 -std=c++17 --offload-arch=gfx950 -fPIC -Wno-unused-function $FLAGS \
     -c csrc/$f.hip -o $T/$f.o &
   pids="$pids $!"

@@ -1,22 +1,21 @@
-// Host check of the row kernels' spread-form arithmetic (nice_decode.hip,
-// round 5): the shipped forms of the interval average (ivs_avg), the
-// speculative step (rows_step) and the exact step (rows_step_exact) against
-// the straightforward forms they replaced.  The shipped forms are restated
-// here line for line; the check is what DESIGN.md's "instruction cuts" table
-// cites.  Usage: rows_arith_check [random_cases]   (exit 0: all equal)
+// Host check of the row kernels' spread-form arithmetic (round 5): the shipped
+// interval average (ivs_avg), speculative step (rows_step) and exact step
+// (rows_step_exact) -- the functions of csrc/nice_rows.hpp themselves, which
+// the kernels of nice_rows.hip compile too -- against the straightforward
+// forms they replaced.  The check is what DESIGN.md's "instruction cuts" table
+// cites.  The header is included by its path from this file, so a plain
+// "g++ tools/rows_arith_check.cpp" builds the check.
+// Usage: rows_arith_check [random_cases]   (exit 0: all equal)
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 
-namespace {
-constexpr uint32_t SP_K = 0xFFu | (0xFFu << 10) | (0xFFu << 20);
-constexpr uint32_t SP_K9 = 0x1FFu | (0x1FFu << 10) | (0x1FFu << 20);
-constexpr uint32_t SP_1 = 1u | (1u << 10) | (1u << 20);
-constexpr uint32_t W_L1 = 1u << 28, W_AVG = 1u << 31, W_CUR = 1u << 18;
-struct IvS { uint32_t lo, len; };
-uint32_t wmask(uint32_t w, int bit) { return (uint32_t)(-(int32_t)((w >> bit) & 1u)); }
+#include "../fast-losless-image-compression-format_amd/csrc/nice_rows.hpp"
 
-// --- the forms before round 5's cuts
+using namespace nice;
+
+namespace {
+// --- the forms before round 5's cuts (wmask: the header's host form)
 IvS avg_old(IvS l, uint32_t u, uint32_t c) {
   const uint32_t s = l.lo + l.len;
   const uint32_t wm = ((s >> 8) & SP_1) * 0x3FFu;
@@ -42,32 +41,6 @@ uint32_t exact_old(uint32_t l1, uint32_t l2, uint32_t l3, uint32_t u, uint32_t w
   return (wp & W_AVG) ? va : ((sel + c) & SP_K);
 }
 
-// --- the shipped forms (nice_decode.hip: ivs_avg, rows_step<CUR>, rows_step_exact)
-IvS avg_new(IvS l, uint32_t u, uint32_t c) {
-  const uint32_t s = l.lo + l.len;
-  const uint32_t wm = ((s >> 8) & SP_1) * 0x3FFu;
-  const uint32_t lo0 = l.lo & ~wm, s0 = (s & ~wm) | (SP_K & wm);
-  const uint32_t lo1 = ((lo0 + u) >> 1) & SP_K, hi1 = ((s0 + u) >> 1) & SP_K9;
-  return IvS{(lo1 + c) & SP_K, hi1 - lo1};
-}
-template <bool CUR>
-IvS step_new(IvS l1, IvS l2, IvS l3, uint32_t u, uint32_t wp) {
-  const uint32_t c = wp;
-  const IvS va = avg_new(l1, u, c);
-  const uint32_t m1 = wmask(wp, 28), m2 = wmask(wp, 29), m3 = wmask(wp, 30), ma = wmask(wp, 31);
-  const uint32_t slo = (l1.lo & m1) | (l2.lo & m2) | (l3.lo & m3);
-  const uint32_t slen = (l1.len & m1) | (l2.len & m2) | (l3.len & m3) | (CUR ? SP_K & wmask(wp, 18) : 0u);
-  const uint32_t rlo = (slo + c) & SP_K;
-  return IvS{(va.lo & ma) | (rlo & ~ma), (va.len & ma) | (slen & ~ma)};
-}
-uint32_t exact_new(uint32_t l1, uint32_t l2, uint32_t l3, uint32_t u, uint32_t wp) {
-  const uint32_t c = wp;
-  const uint32_t sel = (l1 & wmask(wp, 28)) | (l2 & wmask(wp, 29)) | (l3 & wmask(wp, 30));
-  const uint32_t ma = (uint32_t)((int32_t)wp >> 31);
-  const uint32_t x = (((l1 + u) >> 1) & ma) | (sel & ~ma);
-  return (x + c) & SP_K;
-}
-
 uint32_t rs = 2463534242u;
 uint32_t rnd() { rs ^= rs << 13; rs ^= rs >> 17; rs ^= rs << 5; return rs; }
 }  // namespace
@@ -84,7 +57,7 @@ int main(int argc, char** argv) {
         L = (L & ~(0xFFu << 10 * f)) | (lo << 10 * f);
         N = (N & ~(0xFFu << 10 * f)) | (len << 10 * f);
         U = (U & ~(0xFFu << 10 * f)) | (u << 10 * f);
-        const IvS a = avg_old({L, N}, U, C), b = avg_new({L, N}, U, C);
+        const IvS a = avg_old({L, N}, U, C), b = ivs_avg({L, N}, U, C);
         bad_avg += (a.lo != b.lo || a.len != b.len);
       }
   // the steps over random words of every kind (W_CUR: the width must agree;
@@ -94,13 +67,13 @@ int main(int argc, char** argv) {
     const uint32_t k = kinds[rnd() % 6u];
     const uint32_t wp = k | (rnd() & SP_K);
     const uint32_t l1 = rnd() & SP_K, l2 = rnd() & SP_K, l3 = rnd() & SP_K, u = rnd() & SP_K;
-    if (k != W_CUR) bad_exact += exact_old(l1, l2, l3, u, wp) != exact_new(l1, l2, l3, u, wp);
+    if (k != W_CUR) bad_exact += exact_old(l1, l2, l3, u, wp) != rows_step_exact(l1, l2, l3, u, wp);
     IvS a{l1, rnd() & SP_K}, b{l2, rnd() & SP_K}, c{l3, rnd() & SP_K};
     if (rnd() & 1u) a.len = 0;
-    const IvS p = step_new<true>(a, b, c, u, wp), q = step_old(a, b, c, u, wp);
+    const IvS p = rows_step<true>(a, b, c, u, wp), q = step_old(a, b, c, u, wp);
     bad_step += (p.len != q.len || (k != W_CUR && p.lo != q.lo));
     if (k != W_CUR) {   // waves without W_CUR words take the CUR = false step
-      const IvS r = step_new<false>(a, b, c, u, wp);
+      const IvS r = rows_step<false>(a, b, c, u, wp);
       bad_step += (r.len != q.len || r.lo != q.lo);
     }
   }
