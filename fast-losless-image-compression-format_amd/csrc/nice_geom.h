@@ -20,7 +20,7 @@ constexpr uint32_t LDS_BUDGET = 160 * 1024, LDS_OPT_IN = 64 * 1024;
 // a launch's dynamic LDS fits beside up to 1 KB of static LDS (class tables, flags)
 NICE_HD constexpr bool lds_fits(size_t dynamic_bytes) { return dynamic_bytes + 1024 <= LDS_BUDGET; }
 
-// ---- encoder classify kernels (nice_encode.hip) -----------------------------
+// ---- encoder classify kernels (nice_classify.hip) ---------------------------
 constexpr int ENC_TILE = 1024;     // pixels per encoder tile (raster-contiguous)
 constexpr int ENC_THREADS = 256;   // enc_classify / _tiny (window kernels), enc_tilebits, enc_pack_long
 constexpr int CLS_THREADS = 512;   // block size of every ring / pair / slide / strip / twin classify kernel

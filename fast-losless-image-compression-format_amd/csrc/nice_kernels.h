@@ -76,6 +76,7 @@ struct EncArgs {
   uint2* over_list;          // n_frames * ceil((tile_hi - tile_lo) / PACK_SUB)
 };
 
+// the classify family and enc_rundigits: nice_classify.hip; from enc_group_reduce on: nice_encode.hip
 __global__ void enc_classify(EncArgs a);        // W >= 3
 __global__ void enc_classify_tiny(EncArgs a);   // W < 3
 __global__ void enc_classify_ring(EncArgs a);    // RGBA, 16K-pixel ring (W <= CLS_RING_MAX_W)

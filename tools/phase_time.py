@@ -35,6 +35,11 @@ torch.cuda.synchronize()
 assert int(status.abs().sum()) == 0
 if not os.environ.get("NICE_PT_NOCHECK") and not ENC_ONLY:   # (timing-only experiment builds)
     assert torch.equal(dec.reshape(F, -1), px.reshape(F, -1)), "decoded frames differ from the input"
+import hashlib  # noqa: E402
+h = hashlib.sha256()   # (A/B builds via NICE_LIB_PATH must agree)
+for i in range(min(F, 16)):
+    h.update(st[i, :int(ln[i])].cpu().numpy().tobytes())
+print(f"[{os.environ.get('NICE_LIB_PATH', 'in-tree')}] {F} x {W} x {H} x {C}: digest={h.hexdigest()[:16]}")
 for what, fn in [("encode", lambda: nice.encode_batch(px, W, H, C, st, ln)),
                  ("decode", lambda: nice.decode_batch(st, ln, W, H, C, dec, status))][:1 if ENC_ONLY else 2]:
     torch.cuda.synchronize()
