@@ -27,7 +27,7 @@ __all__ = [
     "Image", "encode", "decode", "encode_bytes", "decode_bytes", "encode_bound",
     "encode_batch", "decode_batch", "Context", "Pipeline", "NiceError", "lib", "LIB_PATH",
     "packed_bound", "pack_streams", "encode_batch_packed", "decode_batch_packed", "save_packed", "load_packed",
-    "TiledImage", "tile_grid", "tile_select", "tiled_bound", "encode_tiled", "decode_tiled", "save_tiled",
+    "TiledImage", "TiledAlpha", "tiled_alpha_bound", "tile_grid", "tile_select", "tiled_bound", "encode_tiled", "decode_tiled", "save_tiled",
     "load_tiled", "DEFAULT_TILE",
     "DEC_STRICT_REFERENCE", "DEC_ALPHA_FILL_FF", "DEC_TOLERANT_HEADER",
 ]
@@ -57,6 +57,8 @@ EXPORTS = [
     "nice_packed_bound", "nice_pack_streams_dev", "nice_encode_batch_packed_dev", "nice_decode_packed_dev",
     "nice_tile_grid", "nice_tiled_bound", "nice_tile_select", "nice_tiles_split_dev", "nice_tiles_merge_dev",
     "nice_encode_tiled_dev", "nice_decode_tiled_dev",
+    "nice_tile_alpha_width", "nice_tiled_alpha_bound", "nice_tiles_alpha_range_dev", "nice_encode_tiled_alpha_dev",
+    "nice_decode_tiled_alpha_dev",
 ]
 
 
@@ -126,6 +128,16 @@ def lib():
     L.nice_decode_tiled_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, u8p, u64, ctypes.c_void_p, ctypes.c_void_p,
                                         ctypes.c_void_p, u32, u32, u32, u32, u32, u32, u32, u32, u8, u8p, u64, u32,
                                         u8p]
+    L.nice_tile_alpha_width.restype = u32
+    L.nice_tile_alpha_width.argtypes = [u32]
+    L.nice_tiled_alpha_bound.restype = u64
+    L.nice_tiled_alpha_bound.argtypes = [u32, u32, u32, u32]
+    L.nice_tiles_alpha_range_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, u8p, u64, u32, u32, u32, u32, u8p, u8p]
+    L.nice_encode_tiled_alpha_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, u8p, u64, u32, u32, u32, u32, u8p, u64,
+                                              u8p, u8p, u8p, u8p, u8p]
+    L.nice_decode_tiled_alpha_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, u8p, u64, ctypes.c_void_p,
+                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, u32, u32, u32, u32, u32,
+                                              u32, u32, u32, u8p, u64, u8p]
     L.nice_pipe_create.argtypes = [ctypes.c_int, u32, u32, ctypes.c_uint8, u32, u32,
                                    ctypes.POINTER(ctypes.c_void_p)]
     L.nice_pipe_destroy.argtypes = [ctypes.c_void_p]
@@ -492,11 +504,31 @@ DEFAULT_TILE = (1024, 512)
 
 
 @dataclass
+class TiledAlpha:
+    """The alpha batch of a tiled RGBA image (include/nice.h, "tiled images:
+    alpha"): ``packed`` (uint8 tensor, where the colour ``packed`` lives) holds
+    tile t's alpha at ``off[t] : off[t] + stream_len[t]``; ``kind[t]`` is 0 for
+    a NICE stream of the plane's triplet image, 1 for the raw plane and 2 for a
+    constant plane of ``value[t]`` (nothing stored).  ``off`` (n + 1, int64),
+    ``stream_len`` (n, int64), ``kind`` and ``value`` (n, uint8) are CPU tensors."""
+    packed: object
+    off: object
+    stream_len: object
+    kind: object
+    value: object
+
+    @property
+    def nbytes(self) -> int:
+        return int(self.off[-1])
+
+
+@dataclass
 class TiledImage:
     """A tiled image: ``packed`` (uint8 tensor) holds tile t at
     ``off[t] : off[t] + stream_len[t]``; ``kind[t]`` is 0 for a NICE stream of
     the padded tile and 1 for raw RGB.  ``off`` (n + 1, int64), ``stream_len``
-    (n, int64) and ``kind`` (n, uint8) are CPU tensors."""
+    (n, int64) and ``kind`` (n, uint8) are CPU tensors.  ``alpha``: the alpha
+    batch (``TiledAlpha``) of an image encoded with ``alpha=True``, else None."""
     width: int
     height: int
     channels: int
@@ -506,6 +538,7 @@ class TiledImage:
     off: object
     stream_len: object
     kind: object
+    alpha: "TiledAlpha | None" = None
 
     @property
     def nx(self) -> int:
@@ -558,8 +591,36 @@ def _rows_view(t, what):
     return t.stride(0) if t.shape[0] > 1 else t.shape[1] * c
 
 
+def tiled_alpha_bound(width: int, height: int, tile_w: int, tile_h: int) -> int:
+    """Worst-case packed size of the tiled image's alpha batch (0: bad geometry)."""
+    return int(lib().nice_tiled_alpha_bound(width, height, tile_w, tile_h))
+
+
+def _encode_tiled_alpha(torch, img, pitch, tw, th, n, stream, ctx) -> TiledAlpha:
+    h, w, _ = img.shape
+    dev = img.device
+    packed = torch.empty(tiled_alpha_bound(w, h, tw, th), dtype=torch.uint8, device=dev)
+    off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    lens = torch.empty(n, dtype=torch.int64, device=dev)
+    kind = torch.empty(n, dtype=torch.uint8, device=dev)
+    val = torch.empty(n, dtype=torch.uint8, device=dev)
+    status = torch.full((1,), 99, dtype=torch.int32, device=dev)
+    rc = lib().nice_encode_tiled_alpha_dev(
+        (ctx or _ctx(dev.index or 0)).ptr, _stream_of(torch, stream, dev), ctypes.c_void_p(img.data_ptr()), pitch,
+        w, h, tw, th, ctypes.c_void_p(packed.data_ptr()), packed.numel(), ctypes.c_void_p(off.data_ptr()),
+        ctypes.c_void_p(lens.data_ptr()), ctypes.c_void_p(kind.data_ptr()), ctypes.c_void_p(val.data_ptr()),
+        ctypes.c_void_p(status.data_ptr()))
+    _check(rc, "nice_encode_tiled_alpha_dev")
+    if stream is not None:
+        stream.synchronize()
+    _check(int(status.cpu()[0]), "nice_encode_tiled_alpha_dev")
+    off_h = off.cpu()
+    # (a copy: the alpha of a mostly opaque image is far smaller than its bound)
+    return TiledAlpha(packed[:int(off_h[n])].clone(), off_h, lens.cpu(), kind.cpu(), val.cpu())
+
+
 def encode_tiled(img, tile=None, channels_out: int | None = None, stream=None, ctx: "_Ctx | None" = None,
-                 packed=None) -> TiledImage:
+                 packed=None, alpha: bool = False) -> TiledImage:
     """Encode ``img`` (uint8 cuda tensor [H, W, C], C 3 or 4, rows may be
     strided: ``stride(1) == C``, ``stride(2) == 1``) as tiles of ``tile`` =
     (tile_w, tile_h) pixels (default ``DEFAULT_TILE``).  Every tile is verified
@@ -567,12 +628,16 @@ def encode_tiled(img, tile=None, channels_out: int | None = None, stream=None, c
     ``decode_tiled`` returns the input's RGB for every input (alpha is not
     coded).  ``packed`` (optional uint8 cuda buffer, 16-byte aligned) receives
     the tiles; too small a buffer raises NiceError(E_CAPACITY).  The result's
-    ``packed`` is trimmed to ``off[n]``.  Waits for the device (the tables come
-    back to the host)."""
+    ``packed`` is trimmed to ``off[n]``.  ``alpha=True`` (a 4-channel image;
+    3 channels raise NiceError(E_ARG)) also stores byte +3 of every pixel, as
+    the result's ``alpha`` batch: ``decode_tiled`` then returns all four
+    channels.  Waits for the device (the tables come back to the host)."""
     import torch
     tw, th = DEFAULT_TILE if tile is None else tile
     pitch = _rows_view(img, "encode_tiled: img")
     h, w, c = img.shape
+    if alpha and c != 4:
+        raise NiceError(E_ARG, "encode_tiled: alpha=True needs a 4-channel image")
     nx, ny = tile_grid(w, h, tw, th)
     n = nx * ny
     dev = img.device
@@ -592,7 +657,10 @@ def encode_tiled(img, tile=None, channels_out: int | None = None, stream=None, c
         stream.synchronize()
     _check(int(status.cpu()[0]), "nice_encode_tiled_dev")
     off_h = off.cpu()
-    return TiledImage(w, h, c, tw, th, packed[:int(off_h[n])], off_h, lens.cpu(), kind.cpu())
+    timg = TiledImage(w, h, c, tw, th, packed[:int(off_h[n])], off_h, lens.cpu(), kind.cpu())
+    if alpha:
+        timg.alpha = _encode_tiled_alpha(torch, img, pitch, tw, th, n, stream, ctx)
+    return timg
 
 
 def decode_tiled(timg: TiledImage, roi=None, out=None, out_channels: int | None = None,
@@ -603,8 +671,12 @@ def decode_tiled(timg: TiledImage, roi=None, out=None, out_channels: int | None 
     the tiles the rectangle touches are decoded.  ``out`` may be a row-strided
     view of a larger tensor.  If any tile fails, its pixels of the window are
     left as they were, the other tiles are written, and NiceError is raised
-    with ``.statuses`` (one per selected tile, row-major) and ``.out``.  Waits
-    for the device (the statuses come back)."""
+    with ``.statuses`` (one per selected tile, row-major) and ``.out``.  Where
+    ``timg.alpha`` is set and the output has 4 channels, a second pass writes
+    the stored alpha into byte +3 (``flags``' DEC_ALPHA_FILL_FF is then
+    irrelevant); its statuses are the error's ``.alpha_statuses`` (None without
+    that pass), and a failed alpha tile keeps what the colour pass wrote there.
+    Waits for the device (the statuses come back)."""
     import torch
     x0, y0, rw, rh = (0, 0, timg.width, timg.height) if roi is None else roi
     tw, th = timg.tile_w, timg.tile_h
@@ -637,13 +709,35 @@ def decode_tiled(timg: TiledImage, roi=None, out=None, out_channels: int | None 
         ctypes.c_void_p(kind.data_ptr()), timg.width, timg.height, tw, th, x0, y0, rw, rh, out.shape[2],
         ctypes.c_void_p(out.data_ptr()), pitch, flags, ctypes.c_void_p(status.data_ptr()))
     _check(rc, "nice_decode_tiled_dev")
+    al = timg.alpha if out.shape[2] == 4 else None
+    if al is not None:   # the stored alpha over byte +3 of what the colour pass wrote
+        if not al.packed.is_cuda or al.packed.device != dev:
+            raise NiceError(E_ARG, "decode_tiled: timg.alpha.packed must be on the GPU, with timg.packed")
+        aoff = al.off.to("cpu", torch.int64).contiguous()
+        alens = al.stream_len.to("cpu", torch.int64).contiguous()
+        akind = al.kind.to("cpu", torch.uint8).contiguous()
+        aval = al.value.to("cpu", torch.uint8).contiguous()
+        if (aoff.numel() < n + 1 or alens.numel() != n or akind.numel() != n or aval.numel() != n
+                or int(aoff[n]) > al.packed.numel()):
+            raise NiceError(E_ARG, "decode_tiled: alpha tables do not match the grid")
+        astatus = torch.full((m,), 99, dtype=torch.int32, device=dev)
+        rc = lib().nice_decode_tiled_alpha_dev(
+            (ctx or _ctx(dev.index or 0)).ptr, _stream_of(torch, stream, dev),
+            ctypes.c_void_p(al.packed.data_ptr() if int(aoff[n]) else None), int(aoff[n]),
+            ctypes.c_void_p(aoff.data_ptr()), ctypes.c_void_p(alens.data_ptr()), ctypes.c_void_p(akind.data_ptr()),
+            ctypes.c_void_p(aval.data_ptr()), timg.width, timg.height, tw, th, x0, y0, rw, rh,
+            ctypes.c_void_p(out.data_ptr()), pitch, ctypes.c_void_p(astatus.data_ptr()))
+        _check(rc, "nice_decode_tiled_alpha_dev")
     if stream is not None:
         stream.synchronize()
     st = status.cpu().tolist()
-    bad = [s for s in st if s != OK]
+    ast = astatus.cpu().tolist() if al is not None else None
+    bad = [s for s in st + (ast or []) if s != OK]
     if bad:
-        err = NiceError(bad[0], f"nice_decode_tiled_dev: {len(bad)} of {m} tiles failed")
+        what = "nice_decode_tiled_dev" if al is None else "nice_decode_tiled_dev + nice_decode_tiled_alpha_dev"
+        err = NiceError(bad[0], f"{what}: {len(bad)} of {m if al is None else 2 * m} tiles failed")
         err.statuses = st
+        err.alpha_statuses = ast
         err.out = out
         raise err
     return out
@@ -655,8 +749,16 @@ def decode_tiled(timg: TiledImage, roi=None, out=None, out_channels: int | None 
 #                      channels, tile_w, tile_h, nx, ny, u32 reserved (0), u64 packed size
 #   n x u64 lengths, (n + 1) x u64 offsets, n x u8 kinds zero-padded to a
 #   multiple of 8 bytes, then the packed bytes
+# An image with an alpha batch is version 2: the reserved word is a flags word
+# (bit 0: alpha present), and after the colour packed bytes come
+#   u64 alpha packed size, n x u64 alpha lengths, (n + 1) x u64 alpha offsets,
+#   n x u8 alpha kinds and n x u8 alpha values, each zero-padded to a multiple
+#   of 8 bytes, then the alpha packed bytes
+# An image without one is written as version 1, as before.
 _TILE_MAGIC = b"NICETILE"
 _TILE_VERSION = 1
+_TILE_VERSION_ALPHA = 2
+_TILE_FLAG_ALPHA = 1
 _TILE_HEADER = "<8sIIIIIIIIIQ"
 
 
@@ -674,13 +776,33 @@ def save_tiled(path, timg: TiledImage) -> None:
     if size < 0 or size > timg.packed.numel():
         raise NiceError(E_ARG, "save_tiled: off[n] exceeds the packed buffer")
     blob = timg.packed.detach().reshape(-1)[:size].cpu().numpy()
+    al = timg.alpha
+    if al is not None:
+        alens = np.asarray(al.stream_len.detach().cpu().numpy(), dtype=np.int64).reshape(-1)
+        aoffs = np.asarray(al.off.detach().cpu().numpy(), dtype=np.int64).reshape(-1)
+        akinds = np.asarray(al.kind.detach().cpu().numpy(), dtype=np.uint8).reshape(-1)
+        avals = np.asarray(al.value.detach().cpu().numpy(), dtype=np.uint8).reshape(-1)
+        if alens.size != n or aoffs.size != n + 1 or akinds.size != n or avals.size != n:
+            raise NiceError(E_ARG, f"save_tiled: alpha tables do not match the {timg.nx} x {timg.ny} grid")
+        asize = int(aoffs[n])
+        if asize < 0 or asize > al.packed.numel():
+            raise NiceError(E_ARG, "save_tiled: alpha off[n] exceeds the alpha packed buffer")
+        ablob = al.packed.detach().reshape(-1)[:asize].cpu().numpy()
     with open(path, "wb") as fh:
-        fh.write(struct.pack(_TILE_HEADER, _TILE_MAGIC, _TILE_VERSION, timg.width, timg.height, timg.channels,
-                             timg.tile_w, timg.tile_h, timg.nx, timg.ny, 0, size))
+        fh.write(struct.pack(_TILE_HEADER, _TILE_MAGIC, _TILE_VERSION if al is None else _TILE_VERSION_ALPHA,
+                             timg.width, timg.height, timg.channels, timg.tile_w, timg.tile_h, timg.nx, timg.ny,
+                             0 if al is None else _TILE_FLAG_ALPHA, size))
         fh.write(lens.astype("<u8").tobytes())
         fh.write(offs.astype("<u8").tobytes())
         fh.write(kinds.tobytes() + bytes(-n % 8))
         fh.write(blob.tobytes())
+        if al is not None:
+            fh.write(struct.pack("<Q", asize))
+            fh.write(alens.astype("<u8").tobytes())
+            fh.write(aoffs.astype("<u8").tobytes())
+            fh.write(akinds.tobytes() + bytes(-n % 8))
+            fh.write(avals.tobytes() + bytes(-n % 8))
+            fh.write(ablob.tobytes())
 
 
 def load_tiled(path, device=None) -> TiledImage:
@@ -704,9 +826,13 @@ def load_tiled(path, device=None) -> TiledImage:
         magic, version, w, h, c, tw, th, nx, ny, reserved, size = struct.unpack(_TILE_HEADER, head)
         if magic != _TILE_MAGIC:
             raise bad("wrong magic")
-        if version != _TILE_VERSION:
+        if version not in (_TILE_VERSION, _TILE_VERSION_ALPHA):
             raise bad(f"version {version}")
-        if c not in (3, 4) or w == 0 or h == 0 or w * h > 1 << 30 or reserved != 0:
+        # version 1: a reserved zero; version 2: the flags, alpha (bit 0) the only one and always set
+        has_alpha = version == _TILE_VERSION_ALPHA
+        if reserved != (_TILE_FLAG_ALPHA if has_alpha else 0):
+            raise bad("flags")
+        if c not in (3, 4) or w == 0 or h == 0 or w * h > 1 << 30 or (has_alpha and c != 4):
             raise bad("image size or channels")
         if not (2 <= tw <= 8192 and 2 <= th <= 8192):
             raise bad("tile size")
@@ -718,7 +844,8 @@ def load_tiled(path, device=None) -> TiledImage:
         if size % 16 or size >= 1 << 62:
             raise bad("packed size")
         kpad = n + (-n % 8)
-        if fsize != hsz + 8 * n + 8 * (n + 1) + kpad + size:
+        colour_end = hsz + 8 * n + 8 * (n + 1) + kpad + size
+        if (fsize < colour_end + 8) if has_alpha else (fsize != colour_end):
             raise bad("file size does not match the header")
         lens = np.frombuffer(fh.read(8 * n), "<u8")
         offs = np.frombuffer(fh.read(8 * (n + 1)), "<u8")
@@ -738,11 +865,43 @@ def load_tiled(path, device=None) -> TiledImage:
         blob = np.frombuffer(fh.read(size), np.uint8)
         if blob.size != size:
             raise bad("truncated")
+        alpha = None
+        if has_alpha:   # validated as strictly as the colour tables
+            (asize,) = struct.unpack("<Q", fh.read(8))
+            if asize % 16 or asize >= 1 << 62:
+                raise bad("alpha packed size")
+            if fsize != colour_end + 8 + 8 * n + 8 * (n + 1) + 2 * kpad + asize:
+                raise bad("file size does not match the alpha tables")
+            alens = np.frombuffer(fh.read(8 * n), "<u8")
+            aoffs = np.frombuffer(fh.read(8 * (n + 1)), "<u8")
+            akinds = np.frombuffer(fh.read(kpad), np.uint8)
+            avals = np.frombuffer(fh.read(kpad), np.uint8)
+            if aoffs[0] != 0 or aoffs[n] != asize or (aoffs % 16).any():
+                raise bad("alpha offsets not 16-byte aligned from 0 to the alpha packed size")
+            if (aoffs[1:] < aoffs[:-1]).any():
+                raise bad("alpha offsets not monotone")
+            if (alens > aoffs[1:] - aoffs[:-1]).any():
+                raise bad("an alpha tile overlaps the next")
+            if akinds[n:].any() or avals[n:].any() or (akinds[:n] > 2).any():
+                raise bad("alpha tile kinds")
+            if (alens[akinds[:n] == 1] != tw * th).any():
+                raise bad("raw alpha tile length")
+            if (alens[akinds[:n] == 2] != 0).any():
+                raise bad("constant alpha tile with a length")
+            if avals[:n][akinds[:n] != 2].any():
+                raise bad("alpha value of a tile that is not constant")
+            ablob = np.frombuffer(fh.read(asize), np.uint8)
+            if ablob.size != asize:
+                raise bad("truncated")
+            apacked = torch.from_numpy(ablob.copy())
+            alpha = TiledAlpha(apacked if device is None else apacked.to(device),
+                               torch.from_numpy(aoffs.astype(np.int64)), torch.from_numpy(alens.astype(np.int64)),
+                               torch.from_numpy(akinds[:n].copy()), torch.from_numpy(avals[:n].copy()))
     packed = torch.from_numpy(blob.copy())
     if device is not None:
         packed = packed.to(device)
     return TiledImage(w, h, c, tw, th, packed, torch.from_numpy(offs.astype(np.int64)),
-                      torch.from_numpy(lens.astype(np.int64)), torch.from_numpy(kinds[:n].copy()))
+                      torch.from_numpy(lens.astype(np.int64)), torch.from_numpy(kinds[:n].copy()), alpha)
 
 
 def checksum64(buf) -> int:

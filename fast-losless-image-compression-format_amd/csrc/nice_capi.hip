@@ -1121,6 +1121,197 @@ int nice_decode_tiled_dev(nice_ctx* ctx, void* stream, const uint8_t* d_packed, 
   return NICE_OK;
 }
 
+// ---- tiled images: the alpha batch ------------------------------------------
+uint32_t nice_tile_alpha_width(uint32_t tile_w) { return (uint32_t)(((uint64_t)tile_w + 2) / 3); }
+
+// a slot of the alpha encode's strided scratch: the stream or the raw plane
+static uint64_t alpha_slot_bytes(uint32_t tile_w, uint32_t tile_h) {
+  return std::max<uint64_t>(packed_slot_bytes(nice_tile_alpha_width(tile_w), tile_h),
+                            align_up((size_t)tile_w * tile_h, 256));
+}
+
+uint64_t nice_tiled_alpha_bound(uint32_t w, uint32_t h, uint32_t tile_w, uint32_t tile_h) {
+  uint32_t nx, ny;
+  if (nice_tile_grid(w, h, tile_w, tile_h, &nx, &ny)) return 0;
+  const uint64_t per = std::max<uint64_t>(nice_encode_bound(nice_tile_alpha_width(tile_w), tile_h),
+                                          (uint64_t)tile_w * tile_h);
+  return (uint64_t)nx * ny * align_up(per, 16);
+}
+
+int nice_tiles_alpha_range_dev(nice_ctx* ctx, void* stream, const uint8_t* d_img, uint64_t row_pitch, uint32_t w,
+                               uint32_t h, uint32_t tile_w, uint32_t tile_h, uint32_t* d_lo, uint32_t* d_hi) {
+  if (!ctx || !d_img || !d_lo || !d_hi) return NICE_E_ARG;
+  uint32_t nx, ny;
+  int rc = nice_tile_grid(w, h, tile_w, tile_h, &nx, &ny);
+  if (rc) return rc;
+  if (row_pitch < 4ull * w) return NICE_E_ARG;
+  NICE_HIP(hipSetDevice(ctx->device));
+  return nice::alpha_range_launch(stream, d_img, row_pitch, w, h, tile_w, tile_h, nx, ny, d_lo, d_hi);
+}
+
+int nice_encode_tiled_alpha_dev(nice_ctx* ctx, void* stream, const uint8_t* d_img, uint64_t row_pitch, uint32_t w,
+                                uint32_t h, uint32_t tile_w, uint32_t tile_h, uint8_t* d_apacked, uint64_t apacked_cap,
+                                uint64_t* d_aoff, uint64_t* d_alen, uint8_t* d_akind, uint8_t* d_aval,
+                                int32_t* d_status) {
+  if (!ctx || !d_img || !d_aoff || !d_alen || !d_akind || !d_aval || !d_status) return NICE_E_ARG;
+  if ((!d_apacked && apacked_cap) || ((uintptr_t)d_apacked & 15)) return NICE_E_ARG;
+  uint32_t nx, ny;
+  int rc = nice_tile_grid(w, h, tile_w, tile_h, &nx, &ny);
+  if (rc) return rc;
+  if (row_pitch < 4ull * w) return NICE_E_ARG;
+  NICE_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = (hipStream_t)stream;
+  const uint32_t n = nx * ny;
+  const uint32_t aw = nice_tile_alpha_width(tile_w);
+  // small tables, sized for every tile coded: the stream lengths, the ranges,
+  // the list of coded tiles, their decode statuses and verdicts
+  const size_t o_mlen = 0, o_lo = o_mlen + 8ull * n, o_hi = o_lo + 4ull * n, o_list = o_hi + 4ull * n,
+               o_st = o_list + 4ull * n, o_vk = o_st + 4ull * n;
+  if ((rc = ctx->tile_tab.grow(align_up(o_vk + n, 16)))) return rc;
+  uint8_t* dt = (uint8_t*)ctx->tile_tab.ptr;
+  // first wait: the ranges say which tiles are coded at all
+  if ((rc = nice::alpha_range_launch(stream, d_img, row_pitch, w, h, tile_w, tile_h, nx, ny, (uint32_t*)(dt + o_lo),
+                                     (uint32_t*)(dt + o_hi))))
+    return rc;
+  std::vector<uint32_t> range(2ull * n), list;
+  NICE_HIP(hipMemcpyAsync(range.data(), dt + o_lo, 8ull * n, hipMemcpyDeviceToHost, st));
+  NICE_HIP(hipStreamSynchronize(st));
+  std::vector<uint8_t> kind(n), val(n);
+  for (uint32_t t = 0; t < n; ++t) {
+    const bool flat = range[t] == range[n + t];
+    kind[t] = flat ? 2 : 0;
+    val[t] = flat ? (uint8_t)range[t] : 0;
+    if (!flat) list.push_back(t);
+  }
+  const uint32_t m = (uint32_t)list.size();
+  NICE_HIP(hipMemcpyAsync(d_akind, kind.data(), n, hipMemcpyHostToDevice, st));
+  NICE_HIP(hipMemcpyAsync(d_aval, val.data(), n, hipMemcpyHostToDevice, st));
+  NICE_HIP(hipMemsetAsync(d_alen, 0, 8ull * n, st));
+  const uint64_t slot = alpha_slot_bytes(tile_w, tile_h);
+  if (m) {
+    const uint64_t trip_stride = align_up((size_t)aw * 3 * tile_h, 16);
+    if ((rc = ctx->tiles.grow((size_t)m * trip_stride))) return rc;
+    if ((rc = ctx->tile_dec.grow((size_t)m * trip_stride))) return rc;
+    if ((rc = ctx->pack.grow((size_t)m * slot))) return rc;
+    uint8_t* trip = (uint8_t*)ctx->tiles.ptr;
+    uint8_t* back = (uint8_t*)ctx->tile_dec.ptr;
+    uint8_t* slots = (uint8_t*)ctx->pack.ptr;
+    uint32_t* d_list = (uint32_t*)(dt + o_list);
+    uint64_t* mlen = (uint64_t*)(dt + o_mlen);
+    int32_t* dec_status = (int32_t*)(dt + o_st);
+    uint8_t* vk = dt + o_vk;
+    NICE_HIP(hipMemcpyAsync(d_list, list.data(), 4ull * m, hipMemcpyHostToDevice, st));
+    if ((rc = nice::alpha_gather_launch(stream, d_img, row_pitch, w, h, tile_w, tile_h, nx, d_list, m, trip,
+                                        trip_stride)))
+      return rc;
+    if ((rc = nice_encode_batch_dev(ctx, stream, trip, trip_stride, m, aw, tile_h, 3, 3, slots, slot, mlen))) return rc;
+    // second wait: the stream lengths size the verify decode, as in nice_encode_tiled_dev
+    if ((rc = nice::decode_batch_impl(ctx, stream, slots, slot, mlen, nullptr, m, aw, tile_h, 3, back, trip_stride,
+                                      NICE_DEC_TOLERANT_HEADER, dec_status)))
+      return rc;
+    if ((rc = nice::tiles_compare_launch(stream, trip, trip_stride, back, trip_stride, 3, m, aw * tile_h, dec_status,
+                                         vk)))
+      return rc;
+    if ((rc = nice::alpha_store_launch(stream, trip, trip_stride, tile_w, tile_h, d_list, m, vk, mlen, slots, slot,
+                                       d_akind, d_alen)))
+      return rc;
+  }
+  if ((rc = nice::pack_offsets_launch(stream, slot, d_alen, n, apacked_cap, d_aoff, d_status))) return rc;
+  return m ? nice::alpha_pack_launch(stream, (const uint8_t*)ctx->pack.ptr, slot, (const uint64_t*)(dt + o_mlen),
+                                     (const uint32_t*)(dt + o_list), m, d_aoff, d_apacked, apacked_cap)
+           : NICE_OK;
+}
+
+int nice_decode_tiled_alpha_dev(nice_ctx* ctx, void* stream, const uint8_t* d_apacked, uint64_t apacked_bytes,
+                                const uint64_t* h_aoff, const uint64_t* h_alen, const uint8_t* h_akind,
+                                const uint8_t* h_aval, uint32_t w, uint32_t h, uint32_t tile_w, uint32_t tile_h,
+                                uint32_t x0, uint32_t y0, uint32_t rw, uint32_t rh, uint8_t* d_out, uint64_t out_pitch,
+                                int32_t* d_status) {
+  if (!ctx || !h_aoff || !h_alen || !h_akind || !h_aval || !d_out || !d_status) return NICE_E_ARG;
+  if ((!d_apacked && apacked_bytes) || ((uintptr_t)d_apacked & 15)) return NICE_E_ARG;
+  uint32_t nx, ny, tx0, ty0, tx1, ty1;
+  int rc = nice_tile_select(w, h, tile_w, tile_h, x0, y0, rw, rh, &tx0, &ty0, &tx1, &ty1);
+  if (rc) return rc;
+  (void)nice_tile_grid(w, h, tile_w, tile_h, &nx, &ny);
+  if (out_pitch < 4ull * rw) return NICE_E_ARG;
+  NICE_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = (hipStream_t)stream;
+  const uint32_t m = (tx1 - tx0) * (ty1 - ty0);
+  const uint64_t npx = (uint64_t)tile_w * tile_h;
+  const uint32_t aw = nice_tile_alpha_width(tile_w);
+  // the selected tiles: the coded ones to decode, and every tile to merge with
+  // its source; a tile refused here keeps its status and is not touched
+  std::vector<uint64_t> c_off, c_len, s_src;
+  std::vector<uint32_t> c_pos, s_idx;
+  std::vector<uint8_t> s_kind;
+  std::vector<int32_t> init(m, NICE_OK);
+  uint32_t p = 0;
+  for (uint32_t ty = ty0; ty < ty1; ++ty) {
+    for (uint32_t tx = tx0; tx < tx1; ++tx, ++p) {
+      const uint32_t t = ty * nx + tx;
+      const uint64_t off = h_aoff[t], len = h_alen[t];
+      const uint8_t k = h_akind[t];
+      uint64_t src;
+      if (k > 2) {
+        init[p] = NICE_E_FORMAT;
+        continue;
+      } else if ((off & 15) || off > apacked_bytes || len > apacked_bytes - off) {
+        init[p] = NICE_E_ARG;
+        continue;
+      } else if (k == 2 ? len != 0 : k == 1 ? len != npx : len == 0) {   // (no stream is empty)
+        init[p] = NICE_E_FORMAT;
+        continue;
+      } else if (k == 2) {
+        src = h_aval[t];
+      } else if (k == 1) {
+        src = off;
+      } else {
+        src = c_off.size();
+        c_off.push_back(off);
+        c_len.push_back(len);
+        c_pos.push_back(p);
+      }
+      s_src.push_back(src);
+      s_idx.push_back(t);
+      s_kind.push_back(k);
+    }
+  }
+  const uint32_t nc = (uint32_t)c_off.size(), ns = (uint32_t)s_idx.size();
+  // one upload: u64 {coded offsets, coded lengths, sources}, u32 {coded
+  // positions, tile indices}, u8 kinds; then the coded statuses
+  const size_t o_coff = 0, o_clen = o_coff + 8ull * nc, o_src = o_clen + 8ull * nc, o_cpos = o_src + 8ull * ns,
+               o_idx = o_cpos + 4ull * nc, o_kind = o_idx + 4ull * ns, o_cst = align_up(o_kind + ns, 16),
+               tab_bytes = o_cst + 4ull * nc;
+  std::vector<uint8_t> tab(o_cst);
+  if (nc) {
+    memcpy(&tab[o_coff], c_off.data(), 8ull * nc);
+    memcpy(&tab[o_clen], c_len.data(), 8ull * nc);
+    memcpy(&tab[o_cpos], c_pos.data(), 4ull * nc);
+  }
+  if (ns) {
+    memcpy(&tab[o_src], s_src.data(), 8ull * ns);
+    memcpy(&tab[o_idx], s_idx.data(), 4ull * ns);
+    memcpy(&tab[o_kind], s_kind.data(), ns);
+  }
+  if ((rc = ctx->tile_tab.grow(std::max<size_t>(tab_bytes, 16)))) return rc;
+  uint8_t* dt = (uint8_t*)ctx->tile_tab.ptr;
+  if (o_cst) NICE_HIP(hipMemcpyAsync(dt, tab.data(), o_cst, hipMemcpyHostToDevice, st));
+  NICE_HIP(hipMemcpyAsync(d_status, init.data(), 4ull * m, hipMemcpyHostToDevice, st));
+  const uint64_t stride = align_up((size_t)aw * 3 * tile_h, 16);
+  int32_t* cst = (int32_t*)(dt + o_cst);
+  if (nc) {
+    if ((rc = ctx->tile_dec.grow((size_t)nc * stride))) return rc;
+    if ((rc = nice::decode_batch_impl(ctx, stream, d_apacked, 0, (const uint64_t*)(dt + o_clen), c_len.data(), nc, aw,
+                                      tile_h, 3, (uint8_t*)ctx->tile_dec.ptr, stride, NICE_DEC_TOLERANT_HEADER, cst,
+                                      (const uint64_t*)(dt + o_coff), apacked_bytes)))
+      return rc;
+    if ((rc = nice::tiles_scatter_status_launch(stream, cst, (const uint32_t*)(dt + o_cpos), nc, d_status))) return rc;
+  }
+  return nice::alpha_merge_launch(stream, (const uint8_t*)ctx->tile_dec.ptr, stride, cst, d_apacked,
+                                  (const uint64_t*)(dt + o_src), dt + o_kind, (const uint32_t*)(dt + o_idx), ns, w, h,
+                                  tile_w, tile_h, nx, x0, y0, rw, rh, d_out, out_pitch);
+}
+
 // ---- one image sharded over ranks ------------------------
 int nice_band_classify(nice_ctx* ctx, void* stream, const uint8_t* d_px, uint64_t px0, uint64_t px_count,
                        uint32_t w, uint32_t h, uint8_t channels, uint8_t channels_out, uint32_t tile_lo,

@@ -26,6 +26,10 @@ int pack_streams_launch(void* stream, int cus, const uint8_t* d_streams, uint64_
                         const uint64_t* d_stream_len, uint32_t n_frames, uint8_t* d_packed, uint64_t packed_cap,
                         uint64_t* d_off, int32_t* d_status);
 
+// The first of the two alone: d_off (n_frames + 1) and *d_status from the lengths.
+int pack_offsets_launch(void* stream, uint64_t stream_stride, const uint64_t* d_stream_len, uint32_t n_frames,
+                        uint64_t packed_cap, uint64_t* d_off, int32_t* d_status);
+
 // ---- tiled images (nice_tiles.hip) -----------------------------------------
 // Arguments are checked by the callers (nice_capi.hip); every launch is
 // asynchronous on `stream`.  NICE_E_ARG: the grid would not fit a launch.
@@ -51,6 +55,33 @@ int tiles_store_raw_launch(void* stream, const uint8_t* d_tiles, uint64_t tile_s
                            uint64_t* d_len);
 // d_out[d_pos[i]] = d_st[i]
 int tiles_scatter_status_launch(void* stream, const int32_t* d_st, const uint32_t* d_pos, uint32_t n, int32_t* d_out);
+
+// ---- the alpha batch of a tiled image (nice_tiles.hip) -----------------------
+// aw3 = 3 * ceil(tile_w / 3): bytes per row of a tile's triplet image.
+// d_lo[t], d_hi[t] = min, max of byte +3 over tile t of an RGBA image (both preset by the call).
+int alpha_range_launch(void* stream, const uint8_t* d_img, uint64_t row_pitch, uint32_t w, uint32_t h, uint32_t tile_w,
+                       uint32_t tile_h, uint32_t nx, uint32_t ny, uint32_t* d_lo, uint32_t* d_hi);
+// The triplet image of tile d_list[i] dense at d_trip + i * trip_stride, i < m.
+int alpha_gather_launch(void* stream, const uint8_t* d_img, uint64_t row_pitch, uint32_t w, uint32_t h, uint32_t tile_w,
+                        uint32_t tile_h, uint32_t nx, const uint32_t* d_list, uint32_t m, uint8_t* d_trip,
+                        uint64_t trip_stride);
+// Stream i is stored raw where d_vk[i] != 0 (the verify compare) or
+// d_mlen[i] >= tile_w * tile_h: d_vk[i] becomes that verdict, slot i the plane,
+// d_mlen[i] the stored length; d_akind / d_alen of tile d_list[i] are written,
+// and the slot's bytes from the length to the next multiple of 16 zeroed.
+int alpha_store_launch(void* stream, const uint8_t* d_trip, uint64_t trip_stride, uint32_t tile_w, uint32_t tile_h,
+                       const uint32_t* d_list, uint32_t m, uint8_t* d_vk, uint64_t* d_mlen, uint8_t* d_slots,
+                       uint64_t slot_stride, uint8_t* d_akind, uint64_t* d_alen);
+// Slot i (16-byte aligned, zero pad bytes) to d_packed + d_off[d_list[i]]; nothing at or past packed_cap.
+int alpha_pack_launch(void* stream, const uint8_t* d_slots, uint64_t slot_stride, const uint64_t* d_mlen,
+                      const uint32_t* d_list, uint32_t m, const uint64_t* d_off, uint8_t* d_packed, uint64_t packed_cap);
+// Byte +3 of the window's RGBA pixels.  Slot i holds tile d_tile_idx[i] of
+// d_kind[i]: 0 the decoded triplet image d_src[i] (skipped where its
+// d_dec_status is nonzero), 1 the plane at d_packed + d_src[i], 2 the constant d_src[i].
+int alpha_merge_launch(void* stream, const uint8_t* d_dec, uint64_t dec_stride, const int32_t* d_dec_status,
+                       const uint8_t* d_packed, const uint64_t* d_src, const uint8_t* d_kind, const uint32_t* d_tile_idx,
+                       uint32_t n_slots, uint32_t w, uint32_t h, uint32_t tile_w, uint32_t tile_h, uint32_t nx,
+                       uint32_t x0, uint32_t y0, uint32_t rw, uint32_t rh, uint8_t* d_out, uint64_t out_pitch);
 
 // nice_ctx_reserve; with_packed: also the strided scratch of
 // nice_encode_batch_packed_dev (n_frames stream slots).

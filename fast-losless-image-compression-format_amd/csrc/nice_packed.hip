@@ -174,12 +174,20 @@ __global__ __launch_bounds__(PK_COPY_THREADS) void pack_copy(const uint8_t* __re
   }
 }
 
+int pack_offsets_launch(void* stream, uint64_t stream_stride, const uint64_t* d_stream_len, uint32_t n_frames,
+                        uint64_t packed_cap, uint64_t* d_off, int32_t* d_status) {
+  hipLaunchKernelGGL(pack_scan, dim3(1), dim3(PK_SCAN_THREADS), 0, (hipStream_t)stream,
+                     (const unsigned long long*)d_stream_len, stream_stride, n_frames, (unsigned long long*)d_off,
+                     (unsigned long long)packed_cap, d_status);
+  return hipGetLastError() == hipSuccess ? NICE_OK : NICE_E_HIP;
+}
+
 int pack_streams_launch(void* stream, int cus, const uint8_t* d_streams, uint64_t stream_stride,
                         const uint64_t* d_stream_len, uint32_t n_frames, uint8_t* d_packed, uint64_t packed_cap,
                         uint64_t* d_off, int32_t* d_status) {
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(pack_scan, dim3(1), dim3(PK_SCAN_THREADS), 0, st, (const unsigned long long*)d_stream_len,
-                     stream_stride, n_frames, (unsigned long long*)d_off, (unsigned long long)packed_cap, d_status);
+  if (pack_offsets_launch(stream, stream_stride, d_stream_len, n_frames, packed_cap, d_off, d_status) != NICE_OK)
+    return NICE_E_HIP;
   if (n_frames && packed_cap >= 16) {
     const uint32_t blocks = (uint32_t)std::max(cus, 1) * PK_COPY_BLOCKS_PER_CU;
     hipLaunchKernelGGL(pack_copy, dim3(blocks), dim3(PK_COPY_THREADS), 0, st, d_streams, stream_stride,

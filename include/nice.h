@@ -191,7 +191,8 @@ int nice_decode_packed_dev(nice_ctx* ctx, void* stream, const uint8_t* d_packed,
  * 1024-pixel encoder tiles of one tile must stay below 2^32 (the batch
  * encoder's work counter).  Anything else is NICE_E_ARG.
  * As everywhere in this codec only bytes +0..+2 of a pixel are coded: the
- * tiled path does not preserve alpha either.
+ * colour batch does not preserve alpha either.  Byte +3 of an RGBA image is
+ * kept by a second packed batch beside it ("alpha", below).
  *
  * Layout.  The n tiles are a packed batch (above): d_packed, off[n + 1],
  * len[n], plus kind[n] (u8).  kind 0: an ordinary NICE stream, byte for byte
@@ -272,6 +273,73 @@ int nice_decode_tiled_dev(nice_ctx* ctx, void* stream, const uint8_t* d_packed, 
                           const uint64_t* h_off, const uint64_t* h_len, const uint8_t* h_kind, uint32_t w, uint32_t h,
                           uint32_t tile_w, uint32_t tile_h, uint32_t x0, uint32_t y0, uint32_t rw, uint32_t rh,
                           uint8_t out_channels, uint8_t* d_out, uint64_t out_pitch, uint32_t flags, int32_t* d_status);
+
+/* ---- tiled images: alpha ----
+ * Byte +3 of an RGBA image, as a packed batch of its own over the same grid
+ * (nx, ny, clamp padding): d_apacked, aoff[n + 1], alen[n] exactly as a packed
+ * batch is defined above, plus akind[n] and aval[n] (u8).  The colour batch
+ * and every call above are untouched.  Tile t's alpha plane A[y][x] is
+ * tile_w x tile_h bytes, byte +3 of the padded tile, stored as one of
+ *   kind 2, constant: every byte of the plane equals aval[t]; alen[t] = 0.
+ *           Every tile of an opaque image is this kind.
+ *   kind 0, coded: an ordinary NICE stream of the plane's triplet image,
+ *           aw = ceil(tile_w / 3) wide, tile_h high, 3 channels, whose pixel
+ *           (x', y) is (A[y][min(3x', tile_w - 1)], A[y][min(3x' + 1, tile_w - 1)],
+ *           A[y][min(3x' + 2, tile_w - 1)]): byte for byte what nice_encode
+ *           gives for that image with channels = channels_out = 3.
+ *   kind 1, raw: the plane, tile_w * tile_h bytes in row-major order, where
+ *           the verify decode (tolerant header) of the coded stream fails or
+ *           differs, or the stream is not shorter than the plane
+ *           (alen >= tile_w * tile_h; noise does this).
+ * aval[t] is 0 unless the kind is 2. */
+/* aw = ceil(tile_w / 3). */
+uint32_t nice_tile_alpha_width(uint32_t tile_w);
+/* n * align16(max(nice_encode_bound(aw, tile_h), tile_w * tile_h)): always
+ * enough for d_apacked.  0 for a bad geometry. */
+uint64_t nice_tiled_alpha_bound(uint32_t w, uint32_t h, uint32_t tile_w, uint32_t tile_h);
+/* The range pass alone: d_lo[t], d_hi[t] (n u32 each, device memory) = the
+ * smallest and the largest byte +3 of tile t of a 4-channel image (padding
+ * included: it repeats pixels of the same tile).  Asynchronous. */
+int nice_tiles_alpha_range_dev(nice_ctx* ctx, void* stream, const uint8_t* d_img, uint64_t row_pitch, uint32_t w,
+                               uint32_t h, uint32_t tile_w, uint32_t tile_h, uint32_t* d_lo, uint32_t* d_hi);
+/* Encodes the alpha batch of a 4-channel image (d_img, row_pitch >= 4 * w,
+ * any alignment), read in place with the clamp padding.  d_apacked: 16-byte
+ * aligned, apacked_cap bytes.  d_aoff (n + 1 u64) and *d_status are written as
+ * by nice_encode_batch_packed_dev (NICE_E_CAPACITY: d_aoff[n] is the size
+ * needed and no byte at or past apacked_cap is written); d_alen (n u64),
+ * d_akind and d_aval (n u8); all device memory.
+ * The call waits for the device at most twice: for the per-tile alpha ranges
+ * (16 bytes per lane where d_img and row_pitch are 16-byte aligned, else
+ * dwords or bytes), which decide which tiles are coded at all, and, only if
+ * some tile is not constant, for the stream lengths that size the verify
+ * decode.  Only the non-constant tiles are gathered, encoded and verified: an
+ * opaque image costs the range pass and launches no encode and no decode.
+ * Scratch is the context's, shared with nice_encode_tiled_dev. */
+int nice_encode_tiled_alpha_dev(nice_ctx* ctx, void* stream, const uint8_t* d_img, uint64_t row_pitch, uint32_t w,
+                                uint32_t h, uint32_t tile_w, uint32_t tile_h, uint8_t* d_apacked, uint64_t apacked_cap,
+                                uint64_t* d_aoff /* n + 1 */, uint64_t* d_alen /* n */, uint8_t* d_akind /* n */,
+                                uint8_t* d_aval /* n */, int32_t* d_status /* 1 */);
+/* Writes byte +3, and only byte +3, of the 4-byte pixels of the window
+ * [x0, x0 + rw) x [y0, y0 + rh) at d_out (out_pitch >= 4 * rw): run
+ * nice_decode_tiled_dev with out_channels = 4 first, on the same stream, then
+ * this.  h_aoff (n entries needed), h_alen, h_akind, h_aval: the tables of all
+ * n tiles in host memory; only the tiles the rectangle touches are read
+ * (d_apacked may be null when apacked_bytes is 0).  Nothing outside the window
+ * is written.  Where tile_w % 4 == 0, x0 % 4 == 0 and d_out and out_pitch are
+ * 16-byte aligned a lane rewrites the alpha of four pixels as one 16-byte
+ * read-modify-write; everything else stores bytes.
+ * d_status: one entry per selected tile, in the order of nice_decode_tiled_dev.
+ * A tile whose status is not NICE_OK leaves its alpha bytes as they were; the
+ * others are written.  Per tile: a kind above 2 is NICE_E_FORMAT; an offset
+ * that is not a multiple of 16 or off + len > apacked_bytes NICE_E_ARG; a raw
+ * length other than tile_w * tile_h, a constant tile with a nonzero length or
+ * an empty stream NICE_E_FORMAT; a coded tile reports its decode status.
+ * The call uploads the gathered tables and otherwise only enqueues work. */
+int nice_decode_tiled_alpha_dev(nice_ctx* ctx, void* stream, const uint8_t* d_apacked, uint64_t apacked_bytes,
+                                const uint64_t* h_aoff, const uint64_t* h_alen, const uint8_t* h_akind,
+                                const uint8_t* h_aval, uint32_t w, uint32_t h, uint32_t tile_w, uint32_t tile_h,
+                                uint32_t x0, uint32_t y0, uint32_t rw, uint32_t rh, uint8_t* d_out, uint64_t out_pitch,
+                                int32_t* d_status);
 
 /* ---- one image sharded over ranks (config 4) ----
  * The image's raster is cut into bands of whole encoder tiles (1024 pixels in
