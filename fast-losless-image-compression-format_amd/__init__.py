@@ -29,6 +29,8 @@ __all__ = [
     "packed_bound", "pack_streams", "encode_batch_packed", "decode_batch_packed", "save_packed", "load_packed",
     "TiledImage", "TiledAlpha", "tiled_alpha_bound", "tile_grid", "tile_select", "tiled_bound", "encode_tiled", "decode_tiled", "save_tiled",
     "load_tiled", "DEFAULT_TILE",
+    "ImageSet", "set_grid", "set_select", "set_bound", "encode_set", "decode_set", "save_set", "load_set",
+    "DEFAULT_SET_TILE",
     "DEC_STRICT_REFERENCE", "DEC_ALPHA_FILL_FF", "DEC_TOLERANT_HEADER",
 ]
 
@@ -59,6 +61,8 @@ EXPORTS = [
     "nice_encode_tiled_dev", "nice_decode_tiled_dev",
     "nice_tile_alpha_width", "nice_tiled_alpha_bound", "nice_tiles_alpha_range_dev", "nice_encode_tiled_alpha_dev",
     "nice_decode_tiled_alpha_dev",
+    "nice_set_grid", "nice_set_bound", "nice_set_select", "nice_set_split_dev", "nice_set_merge_dev",
+    "nice_encode_set_dev", "nice_decode_set_dev",
 ]
 
 
@@ -138,6 +142,17 @@ def lib():
     L.nice_decode_tiled_alpha_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, u8p, u64, ctypes.c_void_p,
                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, u32, u32, u32, u32, u32,
                                               u32, u32, u32, u8p, u64, u8p]
+    vp = ctypes.c_void_p
+    L.nice_set_grid.argtypes = [vp, vp, u32, u32, u32, vp]
+    L.nice_set_bound.restype = u64
+    L.nice_set_bound.argtypes = [vp, vp, u32, u32, u32]
+    L.nice_set_select.argtypes = [vp, vp, u32, u32, u32, vp, u32, vp]
+    L.nice_set_split_dev.argtypes = [vp, vp, vp, vp, vp, vp, u32, u8, u32, u32, u8p, u64]
+    L.nice_set_merge_dev.argtypes = [vp, vp, u8p, u64, vp, vp, vp, vp, u32, u8, vp, vp, u32, u32, u32, vp, vp, vp, u32,
+                                     u8, u8]
+    L.nice_encode_set_dev.argtypes = [vp, vp, vp, vp, vp, vp, u32, u8, u8, u32, u32, u8p, u64, u8p, u8p, u8p, u8p]
+    L.nice_decode_set_dev.argtypes = [vp, vp, u8p, u64, vp, vp, vp, vp, vp, u32, u32, u32, vp, vp, vp, u32, u8, u32,
+                                      u8p]
     L.nice_pipe_create.argtypes = [ctypes.c_int, u32, u32, ctypes.c_uint8, u32, u32,
                                    ctypes.POINTER(ctypes.c_void_p)]
     L.nice_pipe_destroy.argtypes = [ctypes.c_void_p]
@@ -902,6 +917,326 @@ def load_tiled(path, device=None) -> TiledImage:
         packed = packed.to(device)
     return TiledImage(w, h, c, tw, th, packed, torch.from_numpy(offs.astype(np.int64)),
                       torch.from_numpy(lens.astype(np.int64)), torch.from_numpy(kinds[:n].copy()), alpha)
+
+
+# ---- image sets (include/nice.h, "image sets") --------------------------------
+# Many images of different sizes as one packed batch of equally sized tiles:
+# one batch encode, one batch decode, whatever the number of images or windows.
+# 256 x 256: of 256 x 256, 512 x 512 and 1024 x 512 the fastest to decode and encode and the smallest
+# container on 256 images of 256..1536 pixels a side (tools/bench_sets.py; DESIGN.md, "Image sets").
+DEFAULT_SET_TILE = (256, 256)
+
+
+@dataclass
+class ImageSet:
+    """A set of K images: image i is ``widths[i]`` x ``heights[i]``, its tiles
+    are ``first[i] : first[i + 1]`` of the n tiles in ``packed`` (uint8 tensor),
+    tile t at ``off[t] : off[t] + stream_len[t]``; ``kind[t]`` is 0 for a NICE
+    stream of the padded tile and 1 for raw RGB.  ``widths``, ``heights`` and
+    ``first`` (K + 1) are lists; ``off`` (n + 1, int64), ``stream_len`` (n,
+    int64) and ``kind`` (n, uint8) are CPU tensors.  Alpha is not stored."""
+    widths: list
+    heights: list
+    channels: int
+    tile_w: int
+    tile_h: int
+    first: list
+    packed: object
+    off: object
+    stream_len: object
+    kind: object
+
+    @property
+    def nbytes(self) -> int:
+        """Bytes of the packed tiles (the container adds its tables)."""
+        return int(self.off[-1])
+
+    def __len__(self) -> int:
+        return len(self.widths)
+
+
+def _u32_array(vals):
+    vals = [int(v) for v in vals]
+    _u32_args(*vals)
+    return (ctypes.c_uint32 * max(len(vals), 1))(*vals)
+
+
+def set_grid(widths, heights, tile_w: int, tile_h: int):
+    """``first`` (K + 1 ints): the scan of the images' tile counts, ``first[K]``
+    the set's n; NiceError(E_ARG) for an empty set or one outside the limits."""
+    k = len(widths)
+    if len(heights) != k:
+        raise NiceError(E_ARG, "set_grid: widths and heights differ in length")
+    _u32_args(tile_w, tile_h)
+    first = (ctypes.c_uint32 * (k + 1))()
+    _check(lib().nice_set_grid(_u32_array(widths), _u32_array(heights), k, tile_w, tile_h, first), "nice_set_grid")
+    return list(first)
+
+
+def set_bound(widths, heights, tile_w: int, tile_h: int) -> int:
+    """Worst-case packed size of the set (0: bad set)."""
+    if len(heights) != len(widths):
+        return 0
+    return int(lib().nice_set_bound(_u32_array(widths), _u32_array(heights), len(widths), tile_w, tile_h))
+
+
+def _win_array(windows):
+    flat = []
+    for wdw in windows:
+        if len(wdw) != 5:
+            raise NiceError(E_ARG, "a window is (image, x, y, w, h)")
+        flat += list(wdw)
+    return _u32_array(flat)
+
+
+def set_select(widths, heights, tile_w: int, tile_h: int, windows):
+    """``slot_first`` (M + 1 ints) for ``windows`` = [(image, x, y, w, h), ...]:
+    window j's slots, the tiles it touches inside its image in row-major order,
+    are ``slot_first[j] : slot_first[j + 1]``.  NiceError(E_ARG) for an image
+    index past the set, an empty window or one that leaves its image."""
+    k, m = len(widths), len(windows)
+    if len(heights) != k:
+        raise NiceError(E_ARG, "set_select: widths and heights differ in length")
+    _u32_args(tile_w, tile_h)
+    sf = (ctypes.c_uint32 * (m + 1))()
+    _check(lib().nice_set_select(_u32_array(widths), _u32_array(heights), k, tile_w, tile_h, _win_array(windows), m,
+                                 sf), "nice_set_select")
+    return list(sf)
+
+
+def encode_set(images, tile=None, channels_out: int | None = None, stream=None, ctx: "_Ctx | None" = None,
+               packed=None) -> ImageSet:
+    """Encode ``images`` (a list of uint8 cuda tensors [H, W, C] of any sizes,
+    one C of 3 or 4 and one device; rows may be strided as for
+    ``encode_tiled``) as one set with tiles of ``tile`` = (tile_w, tile_h)
+    pixels (default ``DEFAULT_SET_TILE``): one batch encode and verify over the
+    tiles of all images.  Tile ``first[i] + t`` equals tile t of
+    ``encode_tiled(images[i], tile)``.  ``packed`` (optional uint8 cuda buffer,
+    16-byte aligned) receives the tiles; too small a buffer raises
+    NiceError(E_CAPACITY).  Waits for the device (the tables come back)."""
+    import torch
+    tw, th = DEFAULT_SET_TILE if tile is None else tile
+    images = list(images)
+    if not images:
+        raise NiceError(E_ARG, "encode_set: no images")
+    pitches = [_rows_view(t, f"encode_set: images[{i}]") for i, t in enumerate(images)]
+    c, dev = images[0].shape[2], images[0].device
+    if any(t.shape[2] != c or t.device != dev for t in images):
+        raise NiceError(E_ARG, "encode_set: the images must share their channels and their device")
+    widths, heights = [t.shape[1] for t in images], [t.shape[0] for t in images]
+    first = set_grid(widths, heights, tw, th)
+    k, n = len(images), first[-1]
+    if packed is None:
+        packed = torch.empty(set_bound(widths, heights, tw, th), dtype=torch.uint8, device=dev)
+    off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    lens = torch.empty(n, dtype=torch.int64, device=dev)
+    kind = torch.empty(n, dtype=torch.uint8, device=dev)
+    status = torch.full((1,), 99, dtype=torch.int32, device=dev)
+    rc = lib().nice_encode_set_dev(
+        (ctx or _ctx(dev.index or 0)).ptr, _stream_of(torch, stream, dev),
+        (ctypes.c_void_p * k)(*[t.data_ptr() for t in images]), (ctypes.c_uint64 * k)(*pitches),
+        _u32_array(widths), _u32_array(heights), k, c, c if channels_out is None else channels_out, tw, th,
+        ctypes.c_void_p(packed.data_ptr()), packed.numel(), ctypes.c_void_p(off.data_ptr()),
+        ctypes.c_void_p(lens.data_ptr()), ctypes.c_void_p(kind.data_ptr()), ctypes.c_void_p(status.data_ptr()))
+    _check(rc, "nice_encode_set_dev")
+    if stream is not None:
+        stream.synchronize()
+    _check(int(status.cpu()[0]), "nice_encode_set_dev")
+    off_h = off.cpu()
+    return ImageSet(widths, heights, c, tw, th, first, packed[:int(off_h[n])], off_h, lens.cpu(), kind.cpu())
+
+
+def decode_set(iset: ImageSet, images=None, windows=None, out=None, out_channels: int | None = None,
+               flags: int = DEC_ALPHA_FILL_FF, stream=None, ctx: "_Ctx | None" = None):
+    """Decode ``iset`` (``packed`` on the GPU) with one batch decode: all its
+    images (the default), the images ``images`` = [i, ...], or the rectangles
+    ``windows`` = [(i, x, y, w, h), ...] (not both).  Returns a list of uint8
+    cuda tensors [h, w, out_channels], one per image or window, in that order.
+    ``out``: a list of such tensors to decode into (rows may be strided), or,
+    where all windows share one size, one tensor [M, rh, rw, C] whose
+    ``out[j]`` takes window j (the crop batch; ``out`` itself is returned).
+    The outputs must not overlap.  Only the tiles the windows touch are
+    decoded, a tile touched by two windows once for each.  If a tile fails,
+    its pixels are left as they were, the others are written, and NiceError is
+    raised with ``.statuses`` (one per window and tile, window after window,
+    row-major inside each: ``set_select``) and ``.out``.  Waits for the device
+    (the statuses come back)."""
+    import torch
+    if images is not None and windows is not None:
+        raise NiceError(E_ARG, "decode_set: images or windows, not both")
+    k = len(iset.widths)
+    tw, th = iset.tile_w, iset.tile_h
+    if windows is None:
+        idx = range(k) if images is None else [int(i) for i in images]
+        if any(i < 0 or i >= k for i in idx):
+            raise NiceError(E_ARG, "decode_set: image index outside the set")
+        windows = [(i, 0, 0, iset.widths[i], iset.heights[i]) for i in idx]
+    windows = [tuple(int(v) for v in wdw) for wdw in windows]
+    m = len(windows)
+    slot_first = set_select(iset.widths, iset.heights, tw, th, windows)
+    first = set_grid(iset.widths, iset.heights, tw, th)
+    n = first[-1]
+    packed = iset.packed
+    if not packed.is_cuda:
+        raise NiceError(E_ARG, "decode_set: iset.packed must be on the GPU (load_set(path, device=...))")
+    off = iset.off.to("cpu", torch.int64).contiguous()
+    lens = iset.stream_len.to("cpu", torch.int64).contiguous()
+    kind = iset.kind.to("cpu", torch.uint8).contiguous()
+    if off.numel() < n + 1 or lens.numel() != n or kind.numel() != n or int(off[n]) > packed.numel():
+        raise NiceError(E_ARG, "decode_set: tables do not match the set")
+    dev = packed.device
+    result = out
+    if out is None:
+        oc = iset.channels if out_channels is None else out_channels
+        outs = result = [torch.empty((wdw[4], wdw[3], oc), dtype=torch.uint8, device=dev) for wdw in windows]
+    elif hasattr(out, "dim"):
+        if out.dim() != 4 or out.shape[0] != m:
+            raise NiceError(E_ARG, "decode_set: out must be [M, rh, rw, out_channels] or a list of M tensors")
+        outs = [out[j] for j in range(m)]
+    else:
+        outs = list(out)
+        if len(outs) != m:
+            raise NiceError(E_ARG, "decode_set: out must be [M, rh, rw, out_channels] or a list of M tensors")
+    oc = outs[0].shape[-1] if outs[0].dim() == 3 else 0
+    for wdw, o in zip(windows, outs):
+        if o.dim() != 3 or tuple(o.shape) != (wdw[4], wdw[3], oc) or out_channels not in (None, oc):
+            raise NiceError(E_ARG, "decode_set: every output must be [rh, rw, out_channels] of its window")
+        if o.device != dev:
+            raise NiceError(E_ARG, "decode_set: out on another device")
+    pitches = [_rows_view(o, "decode_set: out") for o in outs]
+    status = torch.full((slot_first[m],), 99, dtype=torch.int32, device=dev)
+    rc = lib().nice_decode_set_dev(
+        (ctx or _ctx(dev.index or 0)).ptr, _stream_of(torch, stream, dev), ctypes.c_void_p(packed.data_ptr()),
+        int(off[n]), ctypes.c_void_p(off.data_ptr()), ctypes.c_void_p(lens.data_ptr()),
+        ctypes.c_void_p(kind.data_ptr()), _u32_array(iset.widths), _u32_array(iset.heights), k, tw, th,
+        _win_array(windows), (ctypes.c_void_p * m)(*[o.data_ptr() for o in outs]), (ctypes.c_uint64 * m)(*pitches), m,
+        oc, flags, ctypes.c_void_p(status.data_ptr()))
+    _check(rc, "nice_decode_set_dev")
+    if stream is not None:
+        stream.synchronize()
+    st = status.cpu().tolist()
+    bad = [s for s in st if s != OK]
+    if bad:
+        err = NiceError(bad[0], f"nice_decode_set_dev: {len(bad)} of {len(st)} tiles failed")
+        err.statuses = st
+        err.out = result
+        raise err
+    return result
+
+
+# Host-side container of an image set: one file, little-endian throughout
+# (NICEPACK and NICETILE above are different files and stay as they are).
+#   header (48 bytes): magic "NICESETS", u32 version (1), u32 channels, tile_w,
+#                      tile_h, K, u32 reserved (0), u64 tile count n, u64 packed size
+#   K x (u32 width, u32 height), then, exactly as in NICETILE: n x u64 lengths,
+#   (n + 1) x u64 offsets, n x u8 kinds zero-padded to a multiple of 8 bytes,
+#   then the packed bytes
+_SET_MAGIC = b"NICESETS"
+_SET_VERSION = 1
+_SET_HEADER = "<8sIIIIIIQQ"
+
+
+def _set_first(widths, heights, tw, th):
+    """The tile scan of a set in plain Python (load_set needs no library)."""
+    first = [0]
+    for w, h in zip(widths, heights):
+        first.append(first[-1] + (-(-int(w) // tw)) * (-(-int(h) // th)))
+    return first
+
+
+def save_set(path, iset: ImageSet) -> None:
+    """Write ``iset`` (tensors on the GPU or the CPU) to ``path``."""
+    import struct
+    import numpy as np
+    k = len(iset.widths)
+    n = _set_first(iset.widths, iset.heights, iset.tile_w, iset.tile_h)[-1] if k == len(iset.heights) else -1
+    lens = np.asarray(iset.stream_len.detach().cpu().numpy(), dtype=np.int64).reshape(-1)
+    offs = np.asarray(iset.off.detach().cpu().numpy(), dtype=np.int64).reshape(-1)
+    kinds = np.asarray(iset.kind.detach().cpu().numpy(), dtype=np.uint8).reshape(-1)
+    if k == 0 or lens.size != n or offs.size != n + 1 or kinds.size != n:
+        raise NiceError(E_ARG, f"save_set: tables do not match the {k} images")
+    size = int(offs[n])
+    if size < 0 or size > iset.packed.numel():
+        raise NiceError(E_ARG, "save_set: off[n] exceeds the packed buffer")
+    blob = iset.packed.detach().reshape(-1)[:size].cpu().numpy()
+    with open(path, "wb") as fh:
+        fh.write(struct.pack(_SET_HEADER, _SET_MAGIC, _SET_VERSION, iset.channels, iset.tile_w, iset.tile_h, k, 0, n,
+                             size))
+        fh.write(np.stack([np.asarray(iset.widths, "<u4"), np.asarray(iset.heights, "<u4")], axis=1).tobytes())
+        fh.write(lens.astype("<u8").tobytes())
+        fh.write(offs.astype("<u8").tobytes())
+        fh.write(kinds.tobytes() + bytes(-n % 8))
+        fh.write(blob.tobytes())
+
+
+def load_set(path, device=None) -> ImageSet:
+    """Read a ``save_set`` file.  ``packed`` goes to ``device`` (one
+    host-to-device copy), or stays on the CPU with ``device=None`` (no GPU and
+    no libnice_hip.so needed); the tables are CPU tensors.  A file that is not
+    a consistent image set raises NiceError(E_FORMAT)."""
+    import struct
+    import numpy as np
+    import torch
+
+    def bad(why):
+        return NiceError(E_FORMAT, f"load_set({path}): {why}")
+
+    hsz = struct.calcsize(_SET_HEADER)
+    fsize = os.path.getsize(path)
+    with open(path, "rb") as fh:
+        head = fh.read(hsz)
+        if len(head) < hsz:
+            raise bad("truncated header")
+        magic, version, c, tw, th, k, reserved, n, size = struct.unpack(_SET_HEADER, head)
+        if magic != _SET_MAGIC:
+            raise bad("wrong magic")
+        if version != _SET_VERSION:
+            raise bad(f"version {version}")
+        if reserved != 0:
+            raise bad("reserved word")
+        if c not in (3, 4):
+            raise bad("channels")
+        if not (2 <= tw <= 8192 and 2 <= th <= 8192):
+            raise bad("tile size")
+        if k == 0 or fsize < hsz + 8 * k:
+            raise bad("image count")
+        if size % 16 or size >= 1 << 62:
+            raise bad("packed size")
+        dims = np.frombuffer(fh.read(8 * k), "<u4").reshape(k, 2).astype(np.int64)
+        widths, heights = dims[:, 0].tolist(), dims[:, 1].tolist()
+        if any(w == 0 or h == 0 or w * h > 1 << 30 for w, h in zip(widths, heights)):
+            raise bad("image size")
+        first = _set_first(widths, heights, tw, th)   # always recomputed from the sizes
+        if n != first[k]:
+            raise bad("tile count does not match the image and tile sizes")
+        if n * (-(-tw * th // 1024)) >= 1 << 32:
+            raise bad("too many tiles")
+        kpad = n + (-n % 8)
+        if fsize != hsz + 8 * k + 8 * n + 8 * (n + 1) + kpad + size:
+            raise bad("file size does not match the header")
+        lens = np.frombuffer(fh.read(8 * n), "<u8")
+        offs = np.frombuffer(fh.read(8 * (n + 1)), "<u8")
+        kinds = np.frombuffer(fh.read(kpad), np.uint8)
+        if lens.size != n or offs.size != n + 1 or kinds.size != kpad:
+            raise bad("truncated")
+        if offs[0] != 0 or offs[n] != size or (offs % 16).any():
+            raise bad("offsets not 16-byte aligned from 0 to the packed size")
+        if (offs[1:] < offs[:-1]).any():
+            raise bad("offsets not monotone")
+        if (lens > offs[1:] - offs[:-1]).any():
+            raise bad("a tile overlaps the next")
+        if kinds[n:].any() or (kinds[:n] > 1).any():
+            raise bad("tile kinds")
+        if (lens[kinds[:n] == 1] != tw * th * 3).any():
+            raise bad("raw tile length")
+        blob = np.frombuffer(fh.read(size), np.uint8)
+        if blob.size != size:
+            raise bad("truncated")
+    packed = torch.from_numpy(blob.copy())
+    if device is not None:
+        packed = packed.to(device)
+    return ImageSet(widths, heights, c, tw, th, first, packed, torch.from_numpy(offs.astype(np.int64)),
+                    torch.from_numpy(lens.astype(np.int64)), torch.from_numpy(kinds[:n].copy()))
 
 
 def checksum64(buf) -> int:

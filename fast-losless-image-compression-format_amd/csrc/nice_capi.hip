@@ -170,6 +170,7 @@ struct nice_ctx {
   // (gathered offsets, tile indices, statuses) of one call
   Arena tiles, tile_dec, tile_tab;
   uint32_t last_tiled_coded = 0, last_tiled_raw = 0;   // test hook nice_test_last_tiled
+  uint32_t last_set_coded = 0, last_set_raw = 0;       // test hook nice_test_last_set
   PhaseTimer timer;
   BandState bs;
   // decoder record tags (DecArgs::rec_tag): the region the last call used and its tag
@@ -1312,6 +1313,279 @@ int nice_decode_tiled_alpha_dev(nice_ctx* ctx, void* stream, const uint8_t* d_ap
                                   tile_w, tile_h, nx, x0, y0, rw, rh, d_out, out_pitch);
 }
 
+// ---- image sets --------------------------------------------------------------
+int nice_set_grid(const uint32_t* h_w, const uint32_t* h_h, uint32_t K, uint32_t tile_w, uint32_t tile_h,
+                  uint32_t* first) {
+  if (!h_w || !h_h || !first || K == 0) return NICE_E_ARG;
+  uint64_t n = 0;
+  for (uint32_t i = 0; i < K; ++i) {
+    uint32_t nx, ny;
+    int rc = nice_tile_grid(h_w[i], h_h[i], tile_w, tile_h, &nx, &ny);
+    if (rc) return rc;
+    first[i] = (uint32_t)n;
+    n += (uint64_t)nx * ny;
+    // the batch encoder's 32-bit work counter, over all tiles of the set
+    if (n * enc_tiles(tile_w, tile_h) >= (1ull << 32)) return NICE_E_ARG;
+  }
+  first[K] = (uint32_t)n;
+  return NICE_OK;
+}
+
+uint64_t nice_set_bound(const uint32_t* h_w, const uint32_t* h_h, uint32_t K, uint32_t tile_w, uint32_t tile_h) {
+  std::vector<uint32_t> first((size_t)K + 1);
+  if (nice_set_grid(h_w, h_h, K, tile_w, tile_h, first.data())) return 0;
+  return nice_packed_bound(first[K], tile_w, tile_h);
+}
+
+int nice_set_select(const uint32_t* h_w, const uint32_t* h_h, uint32_t K, uint32_t tile_w, uint32_t tile_h,
+                    const uint32_t* h_win, uint32_t M, uint32_t* slot_first) {
+  if (!h_win || !slot_first || M == 0) return NICE_E_ARG;
+  std::vector<uint32_t> first((size_t)K + 1);
+  int rc = nice_set_grid(h_w, h_h, K, tile_w, tile_h, first.data());
+  if (rc) return rc;
+  uint64_t s = 0;
+  for (uint32_t j = 0; j < M; ++j) {
+    const uint32_t* q = h_win + 5ull * j;
+    if (q[0] >= K) return NICE_E_ARG;
+    uint32_t tx0, ty0, tx1, ty1;
+    if ((rc = nice_tile_select(h_w[q[0]], h_h[q[0]], tile_w, tile_h, q[1], q[2], q[3], q[4], &tx0, &ty0, &tx1, &ty1)))
+      return rc;
+    slot_first[j] = (uint32_t)s;
+    s += (uint64_t)(tx1 - tx0) * (ty1 - ty0);
+    if (s >= (1ull << 32)) return NICE_E_ARG;
+  }
+  slot_first[M] = (uint32_t)s;
+  return NICE_OK;
+}
+
+namespace {
+// The image descriptors of a set (checked: pointers, pitches); NICE_E_ARG otherwise.
+int set_image_table(const uint8_t* const* h_img, const uint64_t* h_pitch, const uint32_t* h_w, const uint32_t* h_h,
+                    uint32_t K, uint32_t channels, uint32_t tile_w, const uint32_t* first, std::vector<SetImage>& tab) {
+  if (!h_img || !h_pitch) return NICE_E_ARG;
+  tab.resize(K);
+  for (uint32_t i = 0; i < K; ++i) {
+    if (!h_img[i] || h_pitch[i] < (uint64_t)h_w[i] * channels) return NICE_E_ARG;
+    tab[i] = SetImage{h_img[i], h_pitch[i], h_w[i], h_h[i], (h_w[i] + tile_w - 1) / tile_w, first[i],
+                      nice::set_image_mode(h_img[i], h_pitch[i]), 0};
+  }
+  return NICE_OK;
+}
+
+// The window descriptors of M windows {image, x0, y0, rw, rh} (checked as by
+// nice_set_select, plus pointers and pitches).
+int set_window_table(const uint32_t* h_w, const uint32_t* h_h, uint32_t K, uint32_t tile_w, uint32_t tile_h,
+                     const uint32_t* h_win, uint8_t* const* h_out, const uint64_t* h_out_pitch, uint32_t M,
+                     uint32_t out_channels, std::vector<SetWindow>& tab) {
+  if (!h_out || !h_out_pitch) return NICE_E_ARG;
+  tab.resize(M);
+  for (uint32_t j = 0; j < M; ++j) {
+    const uint32_t* q = h_win + 5ull * j;
+    const uint32_t w = h_w[q[0]], h = h_h[q[0]];
+    if (!h_out[j] || h_out_pitch[j] < (uint64_t)q[3] * out_channels) return NICE_E_ARG;
+    const uint32_t nx = (w + tile_w - 1) / tile_w, ny = (h + tile_h - 1) / tile_h;
+    tab[j] = SetWindow{h_out[j], h_out_pitch[j], q[1], q[2], q[3], q[4], w, h, nx, nx * ny,
+                       nice::set_window_mode(h_out[j], h_out_pitch[j], q[1]), 0};
+  }
+  return NICE_OK;
+}
+}  // namespace
+
+int nice_set_split_dev(nice_ctx* ctx, void* stream, const uint8_t* const* h_img, const uint64_t* h_pitch,
+                       const uint32_t* h_w, const uint32_t* h_h, uint32_t K, uint8_t channels, uint32_t tile_w,
+                       uint32_t tile_h, uint8_t* d_tiles, uint64_t tile_stride) {
+  if (!ctx || !d_tiles || (channels != 3 && channels != 4)) return NICE_E_ARG;
+  std::vector<uint32_t> first((size_t)K + 1);
+  int rc = nice_set_grid(h_w, h_h, K, tile_w, tile_h, first.data());
+  if (rc) return rc;
+  if (tile_stride < (uint64_t)tile_w * tile_h * channels) return NICE_E_ARG;
+  std::vector<SetImage> tab;
+  if ((rc = set_image_table(h_img, h_pitch, h_w, h_h, K, channels, tile_w, first.data(), tab))) return rc;
+  NICE_HIP(hipSetDevice(ctx->device));
+  if ((rc = ctx->tile_tab.grow(K * sizeof(SetImage)))) return rc;
+  NICE_HIP(hipMemcpyAsync(ctx->tile_tab.ptr, tab.data(), K * sizeof(SetImage), hipMemcpyHostToDevice,
+                          (hipStream_t)stream));
+  return nice::set_split_launch(stream, (const SetImage*)ctx->tile_tab.ptr, K, first[K], channels, tile_w, tile_h,
+                                d_tiles, tile_stride);
+}
+
+int nice_set_merge_dev(nice_ctx* ctx, void* stream, const uint8_t* d_tiles, uint64_t tile_stride,
+                       const uint64_t* d_src_off, const uint32_t* d_slot_win, const uint32_t* d_slot_tile,
+                       const int32_t* d_slot_status, uint32_t n_slots, uint8_t tile_channels, const uint32_t* h_w,
+                       const uint32_t* h_h, uint32_t K, uint32_t tile_w, uint32_t tile_h, const uint32_t* h_win,
+                       uint8_t* const* h_out, const uint64_t* h_out_pitch, uint32_t M, uint8_t out_channels,
+                       uint8_t alpha) {
+  if (!ctx) return NICE_E_ARG;
+  if ((tile_channels != 3 && tile_channels != 4) || (out_channels != 3 && out_channels != 4)) return NICE_E_ARG;
+  if (d_src_off && tile_channels != 3) return NICE_E_ARG;   // (raw tiles in a packed buffer hold 3 bytes per pixel)
+  std::vector<uint32_t> slot_first((size_t)M + 1);
+  int rc = nice_set_select(h_w, h_h, K, tile_w, tile_h, h_win, M, slot_first.data());
+  if (rc) return rc;
+  std::vector<SetWindow> tab;
+  if ((rc = set_window_table(h_w, h_h, K, tile_w, tile_h, h_win, h_out, h_out_pitch, M, out_channels, tab))) return rc;
+  if (n_slots == 0) return NICE_OK;
+  if (!d_tiles || !d_slot_win || !d_slot_tile) return NICE_E_ARG;
+  if (!d_src_off && tile_stride < (uint64_t)tile_w * tile_h * tile_channels) return NICE_E_ARG;
+  NICE_HIP(hipSetDevice(ctx->device));
+  if ((rc = ctx->tile_tab.grow(M * sizeof(SetWindow)))) return rc;
+  NICE_HIP(hipMemcpyAsync(ctx->tile_tab.ptr, tab.data(), M * sizeof(SetWindow), hipMemcpyHostToDevice,
+                          (hipStream_t)stream));
+  return nice::set_merge_launch(stream, d_tiles, tile_stride, d_src_off, d_slot_win, d_slot_tile, d_slot_status,
+                                n_slots, (const SetWindow*)ctx->tile_tab.ptr, M, tile_w, tile_h, tile_channels,
+                                out_channels, alpha);
+}
+
+int nice_encode_set_dev(nice_ctx* ctx, void* stream, const uint8_t* const* h_img, const uint64_t* h_pitch,
+                        const uint32_t* h_w, const uint32_t* h_h, uint32_t K, uint8_t channels, uint8_t channels_out,
+                        uint32_t tile_w, uint32_t tile_h, uint8_t* d_packed, uint64_t packed_cap, uint64_t* d_off,
+                        uint64_t* d_len, uint8_t* d_kind, int32_t* d_status) {
+  if (!ctx || !d_off || !d_len || !d_kind || !d_status) return NICE_E_ARG;
+  if (channels != 3 && channels != 4) return NICE_E_ARG;
+  if ((!d_packed && packed_cap) || ((uintptr_t)d_packed & 15)) return NICE_E_ARG;
+  std::vector<uint32_t> first((size_t)K + 1);
+  int rc = nice_set_grid(h_w, h_h, K, tile_w, tile_h, first.data());
+  if (rc) return rc;
+  std::vector<SetImage> tab;
+  if ((rc = set_image_table(h_img, h_pitch, h_w, h_h, K, channels, tile_w, first.data(), tab))) return rc;
+  NICE_HIP(hipSetDevice(ctx->device));
+  const uint32_t n = first[K], npx = tile_w * tile_h;
+  const uint64_t tile_stride = align_up((size_t)npx * channels, 16);
+  const uint64_t slot = packed_slot_bytes(tile_w, tile_h);
+  // the small tables: the verify decode's statuses, then the image descriptors
+  const size_t o_img = align_up((size_t)n * 4, 16);
+  if ((rc = ctx->tiles.grow((size_t)n * tile_stride))) return rc;
+  if ((rc = ctx->tile_dec.grow((size_t)n * tile_stride))) return rc;
+  if ((rc = ctx->pack.grow((size_t)n * slot))) return rc;
+  if ((rc = ctx->tile_tab.grow(o_img + K * sizeof(SetImage)))) return rc;
+  uint8_t* tiles = (uint8_t*)ctx->tiles.ptr;
+  uint8_t* back = (uint8_t*)ctx->tile_dec.ptr;
+  uint8_t* slots = (uint8_t*)ctx->pack.ptr;
+  int32_t* dec_status = (int32_t*)ctx->tile_tab.ptr;
+  const SetImage* d_imgs = (const SetImage*)((uint8_t*)ctx->tile_tab.ptr + o_img);
+  NICE_HIP(hipMemcpyAsync((void*)d_imgs, tab.data(), K * sizeof(SetImage), hipMemcpyHostToDevice, (hipStream_t)stream));
+  if ((rc = nice::set_split_launch(stream, d_imgs, K, n, channels, tile_w, tile_h, tiles, tile_stride))) return rc;
+  // from here on exactly nice_encode_tiled_dev's sequence, over the tiles of all images
+  if ((rc = nice_encode_batch_dev(ctx, stream, tiles, tile_stride, n, tile_w, tile_h, channels, channels_out, slots,
+                                  slot, d_len)))
+    return rc;
+  if ((rc = nice::decode_batch_impl(ctx, stream, slots, slot, d_len, nullptr, n, tile_w, tile_h, channels, back,
+                                    tile_stride, NICE_DEC_TOLERANT_HEADER, dec_status)))
+    return rc;
+  if ((rc = nice::tiles_compare_launch(stream, tiles, tile_stride, back, tile_stride, channels, n, npx, dec_status,
+                                       d_kind)))
+    return rc;
+  if ((rc = nice::tiles_store_raw_launch(stream, tiles, tile_stride, channels, n, npx, d_kind, slots, slot, d_len)))
+    return rc;
+  return nice::pack_streams_launch(stream, ctx->cus, slots, slot, d_len, n, d_packed, packed_cap, d_off, d_status);
+}
+
+int nice_decode_set_dev(nice_ctx* ctx, void* stream, const uint8_t* d_packed, uint64_t packed_bytes,
+                        const uint64_t* h_off, const uint64_t* h_len, const uint8_t* h_kind, const uint32_t* h_w,
+                        const uint32_t* h_h, uint32_t K, uint32_t tile_w, uint32_t tile_h, const uint32_t* h_win,
+                        uint8_t* const* h_out, const uint64_t* h_out_pitch, uint32_t M, uint8_t out_channels,
+                        uint32_t flags, int32_t* d_status) {
+  if (!ctx || !d_packed || !h_off || !h_len || !h_kind || !d_status) return NICE_E_ARG;
+  if (out_channels != 3 && out_channels != 4) return NICE_E_ARG;
+  if ((flags & NICE_DEC_STRICT_REFERENCE) || ((uintptr_t)d_packed & 15)) return NICE_E_ARG;
+  std::vector<uint32_t> first((size_t)K + 1), slot_first((size_t)M + 1);
+  int rc = nice_set_select(h_w, h_h, K, tile_w, tile_h, h_win, M, slot_first.data());
+  if (rc) return rc;
+  (void)nice_set_grid(h_w, h_h, K, tile_w, tile_h, first.data());
+  std::vector<SetWindow> wins;
+  if ((rc = set_window_table(h_w, h_h, K, tile_w, tile_h, h_win, h_out, h_out_pitch, M, out_channels, wins))) return rc;
+  NICE_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = (hipStream_t)stream;
+  const uint32_t m = slot_first[M];
+  const uint64_t npx = (uint64_t)tile_w * tile_h;
+  // every (window, tile) pair is a slot; the slots by kind.  A slot refused
+  // here keeps its status and is not touched.
+  std::vector<uint64_t> c_off, c_len, r_off;
+  std::vector<uint32_t> c_idx, c_win, c_pos, r_idx, r_win;
+  std::vector<int32_t> init(m, NICE_OK);
+  uint32_t p = 0;
+  for (uint32_t j = 0; j < M; ++j) {
+    const uint32_t* q = h_win + 5ull * j;
+    const uint32_t nx = wins[j].nx;
+    const uint32_t tx0 = q[1] / tile_w, ty0 = q[2] / tile_h;
+    const uint32_t tx1 = (q[1] + q[3] - 1) / tile_w + 1, ty1 = (q[2] + q[4] - 1) / tile_h + 1;
+    for (uint32_t ty = ty0; ty < ty1; ++ty) {
+      for (uint32_t tx = tx0; tx < tx1; ++tx, ++p) {
+        const uint32_t ti = ty * nx + tx, t = first[q[0]] + ti;
+        if (h_kind[t] == 0) {   // (its offset and length are checked on the device, as for any packed batch)
+          c_off.push_back(h_off[t]);
+          c_len.push_back(h_len[t]);
+          c_idx.push_back(ti);
+          c_win.push_back(j);
+          c_pos.push_back(p);
+        } else if (h_kind[t] != 1) {
+          init[p] = NICE_E_FORMAT;
+        } else if ((h_off[t] & 15) || h_off[t] > packed_bytes || h_len[t] > packed_bytes - h_off[t]) {
+          init[p] = NICE_E_ARG;
+        } else if (h_len[t] != 3 * npx) {
+          init[p] = NICE_E_FORMAT;
+        } else {
+          r_off.push_back(h_off[t]);
+          r_idx.push_back(ti);
+          r_win.push_back(j);
+        }
+      }
+    }
+  }
+  const uint32_t nc = (uint32_t)c_idx.size(), nr = (uint32_t)r_idx.size();
+  ctx->last_set_coded = nc;
+  ctx->last_set_raw = nr;
+  // one upload: the window descriptors, u64 {coded offsets, coded lengths, raw
+  // offsets}, u32 {coded tile indices, windows, positions, raw tile indices,
+  // windows}; then the coded statuses
+  const size_t o_win = 0, o_coff = o_win + M * sizeof(SetWindow), o_clen = o_coff + 8ull * nc,
+               o_roff = o_clen + 8ull * nc, o_cidx = o_roff + 8ull * nr, o_cwin = o_cidx + 4ull * nc,
+               o_cpos = o_cwin + 4ull * nc, o_ridx = o_cpos + 4ull * nc, o_rwin = o_ridx + 4ull * nr,
+               o_cst = align_up(o_rwin + 4ull * nr, 16), tab_bytes = o_cst + 4ull * nc;
+  std::vector<uint8_t> tab(o_cst);
+  memcpy(&tab[o_win], wins.data(), M * sizeof(SetWindow));
+  if (nc) {
+    memcpy(&tab[o_coff], c_off.data(), 8ull * nc);
+    memcpy(&tab[o_clen], c_len.data(), 8ull * nc);
+    memcpy(&tab[o_cidx], c_idx.data(), 4ull * nc);
+    memcpy(&tab[o_cwin], c_win.data(), 4ull * nc);
+    memcpy(&tab[o_cpos], c_pos.data(), 4ull * nc);
+  }
+  if (nr) {
+    memcpy(&tab[o_roff], r_off.data(), 8ull * nr);
+    memcpy(&tab[o_ridx], r_idx.data(), 4ull * nr);
+    memcpy(&tab[o_rwin], r_win.data(), 4ull * nr);
+  }
+  const uint64_t stride = align_up((size_t)npx * out_channels, 16);
+  if ((rc = ctx->tile_tab.grow(tab_bytes))) return rc;
+  if (nc && (rc = ctx->tile_dec.grow((size_t)nc * stride))) return rc;
+  uint8_t* dt = (uint8_t*)ctx->tile_tab.ptr;
+  NICE_HIP(hipMemcpyAsync(dt, tab.data(), o_cst, hipMemcpyHostToDevice, st));
+  NICE_HIP(hipMemcpyAsync(d_status, init.data(), 4ull * m, hipMemcpyHostToDevice, st));
+  const SetWindow* d_wins = (const SetWindow*)(dt + o_win);
+  if (nc) {
+    uint8_t* dec = (uint8_t*)ctx->tile_dec.ptr;
+    int32_t* cst = (int32_t*)(dt + o_cst);
+    const uint32_t f = (flags & NICE_DEC_ALPHA_FILL_FF) | NICE_DEC_TOLERANT_HEADER;
+    if ((rc = nice::decode_batch_impl(ctx, stream, d_packed, 0, (const uint64_t*)(dt + o_clen), c_len.data(), nc, tile_w,
+                                      tile_h, out_channels, dec, stride, f, cst, (const uint64_t*)(dt + o_coff),
+                                      packed_bytes)))
+      return rc;
+    if ((rc = nice::tiles_scatter_status_launch(stream, cst, (const uint32_t*)(dt + o_cpos), nc, d_status))) return rc;
+    if ((rc = nice::set_merge_launch(stream, dec, stride, nullptr, (const uint32_t*)(dt + o_cwin),
+                                     (const uint32_t*)(dt + o_cidx), cst, nc, d_wins, M, tile_w, tile_h, out_channels,
+                                     out_channels, 0)))
+      return rc;
+  }
+  if (nr) {
+    const uint32_t fill = (flags & NICE_DEC_ALPHA_FILL_FF) ? 255u : 0u;
+    if ((rc = nice::set_merge_launch(stream, d_packed, 0, (const uint64_t*)(dt + o_roff),
+                                     (const uint32_t*)(dt + o_rwin), (const uint32_t*)(dt + o_ridx), nullptr, nr, d_wins,
+                                     M, tile_w, tile_h, 3, out_channels, fill)))
+      return rc;
+  }
+  return NICE_OK;
+}
+
 // ---- one image sharded over ranks ------------------------
 int nice_band_classify(nice_ctx* ctx, void* stream, const uint8_t* d_px, uint64_t px0, uint64_t px_count,
                        uint32_t w, uint32_t h, uint8_t channels, uint8_t channels_out, uint32_t tile_lo,
@@ -1681,6 +1955,13 @@ int nice_test_last_tiled(nice_ctx* ctx, uint32_t* coded, uint32_t* raw) {
   if (!ctx || !coded || !raw) return NICE_E_ARG;
   *coded = ctx->last_tiled_coded;
   *raw = ctx->last_tiled_raw;
+  return NICE_OK;
+}
+
+int nice_test_last_set(nice_ctx* ctx, uint32_t* coded, uint32_t* raw) {
+  if (!ctx || !coded || !raw) return NICE_E_ARG;
+  *coded = ctx->last_set_coded;
+  *raw = ctx->last_set_raw;
   return NICE_OK;
 }
 

@@ -83,6 +83,39 @@ int alpha_merge_launch(void* stream, const uint8_t* d_dec, uint64_t dec_stride, 
                        uint32_t n_slots, uint32_t w, uint32_t h, uint32_t tile_w, uint32_t tile_h, uint32_t nx,
                        uint32_t x0, uint32_t y0, uint32_t rw, uint32_t rh, uint8_t* d_out, uint64_t out_pitch);
 
+// ---- image sets (nice_sets.hip) ----------------------------------------------
+// Device descriptor tables, built and uploaded by the callers (nice_capi.hip).
+// mode: the best move mode (0 bytes, 1 dwords, 2 16 bytes) the member's own
+// base, pitch and, for a window, x0 allow; the kernels take the lower of it
+// and what the tile array allows.
+struct SetImage {
+  const uint8_t* img;
+  uint64_t pitch;
+  uint32_t w, h, nx;
+  uint32_t first;   // the image's first global tile; first of entry 0 is 0, ascending
+  uint32_t mode, pad;
+};
+struct SetWindow {
+  uint8_t* out;
+  uint64_t pitch;
+  uint32_t x0, y0, rw, rh;      // the rectangle, inside its image
+  uint32_t w, h, nx, n_tiles;   // of that image
+  uint32_t mode, pad;
+};
+uint32_t set_image_mode(const uint8_t* d_img, uint64_t row_pitch);
+uint32_t set_window_mode(const uint8_t* d_out, uint64_t out_pitch, uint32_t x0);
+// K images -> n dense tiles (global tile order) with clamped-coordinate padding.
+int set_split_launch(void* stream, const SetImage* d_imgs, uint32_t K, uint32_t n, uint32_t channels, uint32_t tile_w,
+                     uint32_t tile_h, uint8_t* d_tiles, uint64_t tile_stride);
+// Slot i (at d_tiles + i * tile_stride, or d_tiles + d_src_off[i]) holds tile
+// d_slot_tile[i] of the image of window d_slot_win[i]; its part inside that
+// window goes there.  Skipped: a slot with d_slot_status[i] != 0 (may be null),
+// a window index >= n_wins, a tile index outside the image.
+int set_merge_launch(void* stream, const uint8_t* d_tiles, uint64_t tile_stride, const uint64_t* d_src_off,
+                     const uint32_t* d_slot_win, const uint32_t* d_slot_tile, const int32_t* d_slot_status,
+                     uint32_t n_slots, const SetWindow* d_wins, uint32_t n_wins, uint32_t tile_w, uint32_t tile_h,
+                     uint32_t tile_channels, uint32_t out_channels, uint32_t fill);
+
 // nice_ctx_reserve; with_packed: also the strided scratch of
 // nice_encode_batch_packed_dev (n_frames stream slots).
 int ctx_reserve_impl(nice_ctx* ctx, uint32_t n_frames, uint32_t w, uint32_t h, bool with_packed);

@@ -341,6 +341,104 @@ int nice_decode_tiled_alpha_dev(nice_ctx* ctx, void* stream, const uint8_t* d_ap
                                 uint32_t x0, uint32_t y0, uint32_t rw, uint32_t rh, uint8_t* d_out, uint64_t out_pitch,
                                 int32_t* d_status);
 
+/* ---- image sets ----
+ * K >= 1 images of different sizes as one packed batch of tiles: a dataset or
+ * a loader's minibatch is encoded, verified and decoded by one call of the
+ * batch encoder and decoder, and a batch of M windows from M images decodes
+ * only the tiles the windows touch.
+ *
+ * Image i is w[i] x h[i]; all images share `channels` (3 or 4) and one tile
+ * size tile_w x tile_h, and each obeys the rules of nice_tile_grid, which
+ * gives its nx[i] x ny[i] tiles.
+ *   first[0] = 0, first[i + 1] = first[i] + nx[i] * ny[i], n = first[K]
+ *   global tile first[i] + ty * nx[i] + tx is tile (tx, ty) of image i, padded
+ *   by the clamp rule inside its own image
+ * The set is one packed batch of n tiles: d_packed, off[n + 1], len[n],
+ * kind[n], exactly as for a tiled image.  Tile first[i] + t of the set is,
+ * byte for byte and kind for kind, tile t of nice_encode_tiled_dev of image i
+ * alone at the same tile size: a set of one image is that image's tiled form,
+ * and the tables of any set are its images' tables one after the other with
+ * the offsets rebased.
+ * NICE_E_ARG: K == 0, an image outside nice_tile_grid's limits, n times the
+ * 1024-pixel encoder tiles of one tile >= 2^32, a launch grid that does not
+ * fit.  Alpha is not stored: a 4-channel output gets NICE_DEC_ALPHA_FILL_FF or
+ * 0 in byte +3, as a tiled image without an alpha batch does.  An alpha batch
+ * for sets does not exist (yet).
+ *
+ * Host tables are parallel arrays: h_w, h_h (K u32), pointers and pitches (K
+ * or M entries).  A window is five u32 {image, x0, y0, rw, rh}: the rectangle
+ * [x0, x0 + rw) x [y0, y0 + rh) of image `image`; h_win holds M of them.  Its
+ * slots are the tiles nice_tile_select gives inside its image, row-major; the
+ * slots of window j are [slot_first[j], slot_first[j + 1]).  A tile that two
+ * windows touch is one slot in each. */
+/* Validates the set; first (K + 1 u32) receives the tile scan. */
+int nice_set_grid(const uint32_t* h_w, const uint32_t* h_h, uint32_t K, uint32_t tile_w, uint32_t tile_h,
+                  uint32_t* first /* K + 1 */);
+/* nice_packed_bound(n, tile_w, tile_h); 0 for a bad set. */
+uint64_t nice_set_bound(const uint32_t* h_w, const uint32_t* h_h, uint32_t K, uint32_t tile_w, uint32_t tile_h);
+/* slot_first (M + 1 u32): the exclusive scan of the windows' slot counts.
+ * NICE_E_ARG: a bad set, M == 0, an image index >= K, an empty window or one
+ * that leaves its image, 2^32 slots or more. */
+int nice_set_select(const uint32_t* h_w, const uint32_t* h_h, uint32_t K, uint32_t tile_w, uint32_t tile_h,
+                    const uint32_t* h_win /* 5 * M */, uint32_t M, uint32_t* slot_first /* M + 1 */);
+/* Images -> tiles.  Image i: rows of h_w[i] pixels, row y at h_img[i] +
+ * y * h_pitch[i] (device memory; h_pitch[i] >= h_w[i] * channels; any
+ * alignment).  Global tile g is written dense at d_tiles + g * tile_stride
+ * (tile_stride >= tile_w * tile_h * channels) with the clamp padding.  One
+ * launch whatever K is; each image moves as nice_tiles_split_dev would move it
+ * (16 bytes per lane, dwords or bytes by its own alignment).  Asynchronous
+ * after the upload of the K image descriptors. */
+int nice_set_split_dev(nice_ctx* ctx, void* stream, const uint8_t* const* h_img, const uint64_t* h_pitch,
+                       const uint32_t* h_w, const uint32_t* h_h, uint32_t K, uint8_t channels, uint32_t tile_w,
+                       uint32_t tile_h, uint8_t* d_tiles, uint64_t tile_stride);
+/* Slots -> windows.  Slot i (d_tiles + i * tile_stride, or, with d_src_off
+ * non-null, d_tiles + d_src_off[i]: raw tiles straight from a packed buffer,
+ * tile_channels must be 3) holds tile d_slot_tile[i], counted inside its
+ * image, for window d_slot_win[i]; both tables are device memory, slots in any
+ * order.  Skipped: a slot whose d_slot_status[i] (optional, device) is not 0,
+ * a window index >= M, a tile index outside its image.  Window j goes to
+ * h_out[j] (device memory) with row pitch h_out_pitch[j] >= rw * out_channels,
+ * as nice_tiles_merge_dev writes its window: nothing outside a window is
+ * written, and no padding.  The windows' outputs must not overlap.
+ * tile_channels 3 -> out_channels 4 writes `alpha` as byte +3; 4 -> 3 drops
+ * it.  One launch whatever M is; each window moves by its own alignment and
+ * x0 % 4.  Asynchronous after the upload of the M window descriptors. */
+int nice_set_merge_dev(nice_ctx* ctx, void* stream, const uint8_t* d_tiles, uint64_t tile_stride,
+                       const uint64_t* d_src_off, const uint32_t* d_slot_win, const uint32_t* d_slot_tile,
+                       const int32_t* d_slot_status, uint32_t n_slots, uint8_t tile_channels, const uint32_t* h_w,
+                       const uint32_t* h_h, uint32_t K, uint32_t tile_w, uint32_t tile_h, const uint32_t* h_win,
+                       uint8_t* const* h_out, const uint64_t* h_out_pitch, uint32_t M, uint8_t out_channels,
+                       uint8_t alpha);
+/* Encodes K device-resident images as the n tiles of a set: the set split,
+ * then exactly nice_encode_tiled_dev's sequence over all n tiles at once
+ * (nice_encode_batch_dev, the verify decode with NICE_DEC_TOLERANT_HEADER, the
+ * compare, the raw store, the pack).  The number of launches does not depend
+ * on K.  d_packed, packed_cap (nice_set_bound() always suffices), d_off
+ * (n + 1), d_len, d_kind (n), *d_status, the one wait and the scratch: as for
+ * nice_encode_tiled_dev. */
+int nice_encode_set_dev(nice_ctx* ctx, void* stream, const uint8_t* const* h_img, const uint64_t* h_pitch,
+                        const uint32_t* h_w, const uint32_t* h_h, uint32_t K, uint8_t channels, uint8_t channels_out,
+                        uint32_t tile_w, uint32_t tile_h, uint8_t* d_packed, uint64_t packed_cap,
+                        uint64_t* d_off /* n + 1 */, uint64_t* d_len /* n */, uint8_t* d_kind /* n */,
+                        int32_t* d_status /* 1 */);
+/* Decodes M windows of a set, window j into h_out[j] (device memory, row
+ * pitch h_out_pitch[j] >= rw * out_channels; the windows' outputs must not
+ * overlap).  h_off, h_len, h_kind: the tables of all n tiles in host memory.
+ * Every slot (above) is decoded on its own: a tile that two windows touch is
+ * decoded once for each.  One batch decode over all coded slots, one status
+ * scatter, one merge of the coded and one of the raw slots: the number of
+ * launches does not depend on K or M.  Flags as for nice_decode_tiled_dev
+ * (NICE_DEC_STRICT_REFERENCE is NICE_E_ARG).
+ * d_status: slot_first[M] entries, one per slot, with nice_decode_tiled_dev's
+ * codes; a slot whose status is not NICE_OK leaves its pixels untouched, the
+ * others are written.  The call uploads the gathered tables and the window
+ * descriptors and otherwise only enqueues work. */
+int nice_decode_set_dev(nice_ctx* ctx, void* stream, const uint8_t* d_packed, uint64_t packed_bytes,
+                        const uint64_t* h_off, const uint64_t* h_len, const uint8_t* h_kind, const uint32_t* h_w,
+                        const uint32_t* h_h, uint32_t K, uint32_t tile_w, uint32_t tile_h, const uint32_t* h_win,
+                        uint8_t* const* h_out, const uint64_t* h_out_pitch, uint32_t M, uint8_t out_channels,
+                        uint32_t flags, int32_t* d_status /* slot_first[M] */);
+
 /* ---- one image sharded over ranks (config 4) ----
  * The image's raster is cut into bands of whole encoder tiles (1024 pixels in
  * raster order); rank r encodes tiles [tile_lo, tile_hi).  The caller runs the

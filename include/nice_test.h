@@ -51,6 +51,10 @@ int nice_test_last_dec_route(struct nice_ctx* ctx, uint32_t* route, uint32_t* fa
  * expanded from raw pixels: together the tiles its rectangle selected, minus
  * those refused on the host (bad kind, raw length or raw offset) */
 int nice_test_last_tiled(struct nice_ctx* ctx, uint32_t* coded, uint32_t* raw);
+/* the same for the context's last nice_decode_set_dev: its slots (one per
+ * window and tile the window touches) decoded as streams and expanded from raw
+ * pixels, minus those refused on the host */
+int nice_test_last_set(struct nice_ctx* ctx, uint32_t* coded, uint32_t* raw);
 
 #ifdef __cplusplus
 }
