@@ -29,8 +29,8 @@ __all__ = [
     "packed_bound", "pack_streams", "encode_batch_packed", "decode_batch_packed", "save_packed", "load_packed",
     "TiledImage", "TiledAlpha", "tiled_alpha_bound", "tile_grid", "tile_select", "tiled_bound", "encode_tiled", "decode_tiled", "save_tiled",
     "load_tiled", "DEFAULT_TILE",
-    "ImageSet", "set_grid", "set_select", "set_bound", "encode_set", "decode_set", "save_set", "load_set",
-    "DEFAULT_SET_TILE",
+    "ImageSet", "set_grid", "set_select", "set_bound", "set_alpha_bound", "encode_set", "decode_set", "save_set",
+    "load_set", "DEFAULT_SET_TILE",
     "DEC_STRICT_REFERENCE", "DEC_ALPHA_FILL_FF", "DEC_TOLERANT_HEADER",
 ]
 
@@ -63,6 +63,7 @@ EXPORTS = [
     "nice_decode_tiled_alpha_dev",
     "nice_set_grid", "nice_set_bound", "nice_set_select", "nice_set_split_dev", "nice_set_merge_dev",
     "nice_encode_set_dev", "nice_decode_set_dev",
+    "nice_set_alpha_bound", "nice_set_alpha_range_dev", "nice_encode_set_alpha_dev", "nice_decode_set_alpha_dev",
 ]
 
 
@@ -153,6 +154,12 @@ def lib():
     L.nice_encode_set_dev.argtypes = [vp, vp, vp, vp, vp, vp, u32, u8, u8, u32, u32, u8p, u64, u8p, u8p, u8p, u8p]
     L.nice_decode_set_dev.argtypes = [vp, vp, u8p, u64, vp, vp, vp, vp, vp, u32, u32, u32, vp, vp, vp, u32, u8, u32,
                                       u8p]
+    L.nice_set_alpha_bound.restype = u64
+    L.nice_set_alpha_bound.argtypes = [vp, vp, u32, u32, u32]
+    L.nice_set_alpha_range_dev.argtypes = [vp, vp, vp, vp, vp, vp, u32, u32, u32, u8p, u8p]
+    L.nice_encode_set_alpha_dev.argtypes = [vp, vp, vp, vp, vp, vp, u32, u32, u32, u8p, u64, u8p, u8p, u8p, u8p, u8p]
+    L.nice_decode_set_alpha_dev.argtypes = [vp, vp, u8p, u64, vp, vp, vp, vp, vp, vp, u32, u32, u32, vp, vp, vp, u32,
+                                            u8p]
     L.nice_pipe_create.argtypes = [ctypes.c_int, u32, u32, ctypes.c_uint8, u32, u32,
                                    ctypes.POINTER(ctypes.c_void_p)]
     L.nice_pipe_destroy.argtypes = [ctypes.c_void_p]
@@ -793,16 +800,7 @@ def save_tiled(path, timg: TiledImage) -> None:
     blob = timg.packed.detach().reshape(-1)[:size].cpu().numpy()
     al = timg.alpha
     if al is not None:
-        alens = np.asarray(al.stream_len.detach().cpu().numpy(), dtype=np.int64).reshape(-1)
-        aoffs = np.asarray(al.off.detach().cpu().numpy(), dtype=np.int64).reshape(-1)
-        akinds = np.asarray(al.kind.detach().cpu().numpy(), dtype=np.uint8).reshape(-1)
-        avals = np.asarray(al.value.detach().cpu().numpy(), dtype=np.uint8).reshape(-1)
-        if alens.size != n or aoffs.size != n + 1 or akinds.size != n or avals.size != n:
-            raise NiceError(E_ARG, f"save_tiled: alpha tables do not match the {timg.nx} x {timg.ny} grid")
-        asize = int(aoffs[n])
-        if asize < 0 or asize > al.packed.numel():
-            raise NiceError(E_ARG, "save_tiled: alpha off[n] exceeds the alpha packed buffer")
-        ablob = al.packed.detach().reshape(-1)[:asize].cpu().numpy()
+        apart = _alpha_part(al, n, "save_tiled")
     with open(path, "wb") as fh:
         fh.write(struct.pack(_TILE_HEADER, _TILE_MAGIC, _TILE_VERSION if al is None else _TILE_VERSION_ALPHA,
                              timg.width, timg.height, timg.channels, timg.tile_w, timg.tile_h, timg.nx, timg.ny,
@@ -812,12 +810,64 @@ def save_tiled(path, timg: TiledImage) -> None:
         fh.write(kinds.tobytes() + bytes(-n % 8))
         fh.write(blob.tobytes())
         if al is not None:
-            fh.write(struct.pack("<Q", asize))
-            fh.write(alens.astype("<u8").tobytes())
-            fh.write(aoffs.astype("<u8").tobytes())
-            fh.write(akinds.tobytes() + bytes(-n % 8))
-            fh.write(avals.tobytes() + bytes(-n % 8))
-            fh.write(ablob.tobytes())
+            fh.write(apart)
+
+
+def _alpha_part(al: TiledAlpha, n: int, who: str) -> bytes:
+    """The alpha part of a version 2 container (NICETILE and NICESETS alike)."""
+    import struct
+    import numpy as np
+    alens = np.asarray(al.stream_len.detach().cpu().numpy(), dtype=np.int64).reshape(-1)
+    aoffs = np.asarray(al.off.detach().cpu().numpy(), dtype=np.int64).reshape(-1)
+    akinds = np.asarray(al.kind.detach().cpu().numpy(), dtype=np.uint8).reshape(-1)
+    avals = np.asarray(al.value.detach().cpu().numpy(), dtype=np.uint8).reshape(-1)
+    if alens.size != n or aoffs.size != n + 1 or akinds.size != n or avals.size != n:
+        raise NiceError(E_ARG, f"{who}: alpha tables do not match the {n} tiles")
+    asize = int(aoffs[n])
+    if asize < 0 or asize > al.packed.numel():
+        raise NiceError(E_ARG, f"{who}: alpha off[n] exceeds the alpha packed buffer")
+    ablob = al.packed.detach().reshape(-1)[:asize].cpu().numpy()
+    return b"".join([struct.pack("<Q", asize), alens.astype("<u8").tobytes(), aoffs.astype("<u8").tobytes(),
+                     akinds.tobytes() + bytes(-n % 8), avals.tobytes() + bytes(-n % 8), ablob.tobytes()])
+
+
+def _load_alpha_part(fh, fsize: int, start: int, n: int, tw: int, th: int, bad, device) -> TiledAlpha:
+    """Reads and validates, as strictly as the colour tables, the alpha part
+    that begins at byte ``start`` of a version 2 container and must end the file."""
+    import struct
+    import numpy as np
+    import torch
+    kpad = n + (-n % 8)
+    (asize,) = struct.unpack("<Q", fh.read(8))
+    if asize % 16 or asize >= 1 << 62:
+        raise bad("alpha packed size")
+    if fsize != start + 8 + 8 * n + 8 * (n + 1) + 2 * kpad + asize:
+        raise bad("file size does not match the alpha tables")
+    alens = np.frombuffer(fh.read(8 * n), "<u8")
+    aoffs = np.frombuffer(fh.read(8 * (n + 1)), "<u8")
+    akinds = np.frombuffer(fh.read(kpad), np.uint8)
+    avals = np.frombuffer(fh.read(kpad), np.uint8)
+    if aoffs[0] != 0 or aoffs[n] != asize or (aoffs % 16).any():
+        raise bad("alpha offsets not 16-byte aligned from 0 to the alpha packed size")
+    if (aoffs[1:] < aoffs[:-1]).any():
+        raise bad("alpha offsets not monotone")
+    if (alens > aoffs[1:] - aoffs[:-1]).any():
+        raise bad("an alpha tile overlaps the next")
+    if akinds[n:].any() or avals[n:].any() or (akinds[:n] > 2).any():
+        raise bad("alpha tile kinds")
+    if (alens[akinds[:n] == 1] != tw * th).any():
+        raise bad("raw alpha tile length")
+    if (alens[akinds[:n] == 2] != 0).any():
+        raise bad("constant alpha tile with a length")
+    if avals[:n][akinds[:n] != 2].any():
+        raise bad("alpha value of a tile that is not constant")
+    ablob = np.frombuffer(fh.read(asize), np.uint8)
+    if ablob.size != asize:
+        raise bad("truncated")
+    apacked = torch.from_numpy(ablob.copy())
+    return TiledAlpha(apacked if device is None else apacked.to(device),
+                      torch.from_numpy(aoffs.astype(np.int64)), torch.from_numpy(alens.astype(np.int64)),
+                      torch.from_numpy(akinds[:n].copy()), torch.from_numpy(avals[:n].copy()))
 
 
 def load_tiled(path, device=None) -> TiledImage:
@@ -881,37 +931,8 @@ def load_tiled(path, device=None) -> TiledImage:
         if blob.size != size:
             raise bad("truncated")
         alpha = None
-        if has_alpha:   # validated as strictly as the colour tables
-            (asize,) = struct.unpack("<Q", fh.read(8))
-            if asize % 16 or asize >= 1 << 62:
-                raise bad("alpha packed size")
-            if fsize != colour_end + 8 + 8 * n + 8 * (n + 1) + 2 * kpad + asize:
-                raise bad("file size does not match the alpha tables")
-            alens = np.frombuffer(fh.read(8 * n), "<u8")
-            aoffs = np.frombuffer(fh.read(8 * (n + 1)), "<u8")
-            akinds = np.frombuffer(fh.read(kpad), np.uint8)
-            avals = np.frombuffer(fh.read(kpad), np.uint8)
-            if aoffs[0] != 0 or aoffs[n] != asize or (aoffs % 16).any():
-                raise bad("alpha offsets not 16-byte aligned from 0 to the alpha packed size")
-            if (aoffs[1:] < aoffs[:-1]).any():
-                raise bad("alpha offsets not monotone")
-            if (alens > aoffs[1:] - aoffs[:-1]).any():
-                raise bad("an alpha tile overlaps the next")
-            if akinds[n:].any() or avals[n:].any() or (akinds[:n] > 2).any():
-                raise bad("alpha tile kinds")
-            if (alens[akinds[:n] == 1] != tw * th).any():
-                raise bad("raw alpha tile length")
-            if (alens[akinds[:n] == 2] != 0).any():
-                raise bad("constant alpha tile with a length")
-            if avals[:n][akinds[:n] != 2].any():
-                raise bad("alpha value of a tile that is not constant")
-            ablob = np.frombuffer(fh.read(asize), np.uint8)
-            if ablob.size != asize:
-                raise bad("truncated")
-            apacked = torch.from_numpy(ablob.copy())
-            alpha = TiledAlpha(apacked if device is None else apacked.to(device),
-                               torch.from_numpy(aoffs.astype(np.int64)), torch.from_numpy(alens.astype(np.int64)),
-                               torch.from_numpy(akinds[:n].copy()), torch.from_numpy(avals[:n].copy()))
+        if has_alpha:
+            alpha = _load_alpha_part(fh, fsize, colour_end, n, tw, th, bad, device)
     packed = torch.from_numpy(blob.copy())
     if device is not None:
         packed = packed.to(device)
@@ -934,7 +955,9 @@ class ImageSet:
     tile t at ``off[t] : off[t] + stream_len[t]``; ``kind[t]`` is 0 for a NICE
     stream of the padded tile and 1 for raw RGB.  ``widths``, ``heights`` and
     ``first`` (K + 1) are lists; ``off`` (n + 1, int64), ``stream_len`` (n,
-    int64) and ``kind`` (n, uint8) are CPU tensors.  Alpha is not stored."""
+    int64) and ``kind`` (n, uint8) are CPU tensors.  ``alpha``: the alpha batch
+    (``TiledAlpha``, its tables over the same n global tiles) of a set encoded
+    with ``alpha=True``, else None."""
     widths: list
     heights: list
     channels: int
@@ -945,6 +968,7 @@ class ImageSet:
     off: object
     stream_len: object
     kind: object
+    alpha: "TiledAlpha | None" = None
 
     @property
     def nbytes(self) -> int:
@@ -980,6 +1004,36 @@ def set_bound(widths, heights, tile_w: int, tile_h: int) -> int:
     return int(lib().nice_set_bound(_u32_array(widths), _u32_array(heights), len(widths), tile_w, tile_h))
 
 
+def set_alpha_bound(widths, heights, tile_w: int, tile_h: int) -> int:
+    """Worst-case packed size of the set's alpha batch (0: bad set)."""
+    if len(heights) != len(widths):
+        return 0
+    return int(lib().nice_set_alpha_bound(_u32_array(widths), _u32_array(heights), len(widths), tile_w, tile_h))
+
+
+def _encode_set_alpha(torch, images, pitches, widths, heights, tw, th, n, stream, ctx) -> TiledAlpha:
+    k, dev = len(images), images[0].device
+    packed = torch.empty(set_alpha_bound(widths, heights, tw, th), dtype=torch.uint8, device=dev)
+    off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    lens = torch.empty(n, dtype=torch.int64, device=dev)
+    kind = torch.empty(n, dtype=torch.uint8, device=dev)
+    val = torch.empty(n, dtype=torch.uint8, device=dev)
+    status = torch.full((1,), 99, dtype=torch.int32, device=dev)
+    rc = lib().nice_encode_set_alpha_dev(
+        (ctx or _ctx(dev.index or 0)).ptr, _stream_of(torch, stream, dev),
+        (ctypes.c_void_p * k)(*[t.data_ptr() for t in images]), (ctypes.c_uint64 * k)(*pitches),
+        _u32_array(widths), _u32_array(heights), k, tw, th, ctypes.c_void_p(packed.data_ptr()), packed.numel(),
+        ctypes.c_void_p(off.data_ptr()), ctypes.c_void_p(lens.data_ptr()), ctypes.c_void_p(kind.data_ptr()),
+        ctypes.c_void_p(val.data_ptr()), ctypes.c_void_p(status.data_ptr()))
+    _check(rc, "nice_encode_set_alpha_dev")
+    if stream is not None:
+        stream.synchronize()
+    _check(int(status.cpu()[0]), "nice_encode_set_alpha_dev")
+    off_h = off.cpu()
+    # (a copy: the alpha of mostly opaque images is far smaller than its bound)
+    return TiledAlpha(packed[:int(off_h[n])].clone(), off_h, lens.cpu(), kind.cpu(), val.cpu())
+
+
 def _win_array(windows):
     flat = []
     for wdw in windows:
@@ -1005,7 +1059,7 @@ def set_select(widths, heights, tile_w: int, tile_h: int, windows):
 
 
 def encode_set(images, tile=None, channels_out: int | None = None, stream=None, ctx: "_Ctx | None" = None,
-               packed=None) -> ImageSet:
+               packed=None, alpha: bool = False) -> ImageSet:
     """Encode ``images`` (a list of uint8 cuda tensors [H, W, C] of any sizes,
     one C of 3 or 4 and one device; rows may be strided as for
     ``encode_tiled``) as one set with tiles of ``tile`` = (tile_w, tile_h)
@@ -1013,7 +1067,12 @@ def encode_set(images, tile=None, channels_out: int | None = None, stream=None, 
     tiles of all images.  Tile ``first[i] + t`` equals tile t of
     ``encode_tiled(images[i], tile)``.  ``packed`` (optional uint8 cuda buffer,
     16-byte aligned) receives the tiles; too small a buffer raises
-    NiceError(E_CAPACITY).  Waits for the device (the tables come back)."""
+    NiceError(E_CAPACITY).  ``alpha=True`` (4-channel images; 3 channels raise
+    NiceError(E_ARG)) also stores byte +3 of every pixel, as the result's
+    ``alpha`` batch over the same n tiles (one more batch encode over the
+    tiles whose alpha is not constant, whatever the number of images):
+    ``decode_set`` then returns all four channels.  Waits for the device (the
+    tables come back)."""
     import torch
     tw, th = DEFAULT_SET_TILE if tile is None else tile
     images = list(images)
@@ -1023,6 +1082,8 @@ def encode_set(images, tile=None, channels_out: int | None = None, stream=None, 
     c, dev = images[0].shape[2], images[0].device
     if any(t.shape[2] != c or t.device != dev for t in images):
         raise NiceError(E_ARG, "encode_set: the images must share their channels and their device")
+    if alpha and c != 4:
+        raise NiceError(E_ARG, "encode_set: alpha=True needs 4-channel images")
     widths, heights = [t.shape[1] for t in images], [t.shape[0] for t in images]
     first = set_grid(widths, heights, tw, th)
     k, n = len(images), first[-1]
@@ -1043,7 +1104,10 @@ def encode_set(images, tile=None, channels_out: int | None = None, stream=None, 
         stream.synchronize()
     _check(int(status.cpu()[0]), "nice_encode_set_dev")
     off_h = off.cpu()
-    return ImageSet(widths, heights, c, tw, th, first, packed[:int(off_h[n])], off_h, lens.cpu(), kind.cpu())
+    iset = ImageSet(widths, heights, c, tw, th, first, packed[:int(off_h[n])], off_h, lens.cpu(), kind.cpu())
+    if alpha:
+        iset.alpha = _encode_set_alpha(torch, images, pitches, widths, heights, tw, th, n, stream, ctx)
+    return iset
 
 
 def decode_set(iset: ImageSet, images=None, windows=None, out=None, out_channels: int | None = None,
@@ -1059,8 +1123,12 @@ def decode_set(iset: ImageSet, images=None, windows=None, out=None, out_channels
     decoded, a tile touched by two windows once for each.  If a tile fails,
     its pixels are left as they were, the others are written, and NiceError is
     raised with ``.statuses`` (one per window and tile, window after window,
-    row-major inside each: ``set_select``) and ``.out``.  Waits for the device
-    (the statuses come back)."""
+    row-major inside each: ``set_select``) and ``.out``.  Where ``iset.alpha``
+    is set and the outputs have 4 channels, a second pass writes the stored
+    alpha into byte +3 (``flags``' DEC_ALPHA_FILL_FF is then irrelevant); its
+    statuses, slot for slot, are the error's ``.alpha_statuses`` (None without
+    that pass), and a failed alpha slot keeps what the colour pass wrote
+    there.  Waits for the device (the statuses come back)."""
     import torch
     if images is not None and windows is not None:
         raise NiceError(E_ARG, "decode_set: images or windows, not both")
@@ -1112,13 +1180,36 @@ def decode_set(iset: ImageSet, images=None, windows=None, out=None, out_channels
         _win_array(windows), (ctypes.c_void_p * m)(*[o.data_ptr() for o in outs]), (ctypes.c_uint64 * m)(*pitches), m,
         oc, flags, ctypes.c_void_p(status.data_ptr()))
     _check(rc, "nice_decode_set_dev")
+    al = iset.alpha if oc == 4 else None
+    if al is not None:   # the stored alpha over byte +3 of what the colour pass wrote
+        if not al.packed.is_cuda or al.packed.device != dev:
+            raise NiceError(E_ARG, "decode_set: iset.alpha.packed must be on the GPU, with iset.packed")
+        aoff = al.off.to("cpu", torch.int64).contiguous()
+        alens = al.stream_len.to("cpu", torch.int64).contiguous()
+        akind = al.kind.to("cpu", torch.uint8).contiguous()
+        aval = al.value.to("cpu", torch.uint8).contiguous()
+        if (aoff.numel() < n + 1 or alens.numel() != n or akind.numel() != n or aval.numel() != n
+                or int(aoff[n]) > al.packed.numel()):
+            raise NiceError(E_ARG, "decode_set: alpha tables do not match the set")
+        astatus = torch.full((slot_first[m],), 99, dtype=torch.int32, device=dev)
+        rc = lib().nice_decode_set_alpha_dev(
+            (ctx or _ctx(dev.index or 0)).ptr, _stream_of(torch, stream, dev),
+            ctypes.c_void_p(al.packed.data_ptr() if int(aoff[n]) else None), int(aoff[n]),
+            ctypes.c_void_p(aoff.data_ptr()), ctypes.c_void_p(alens.data_ptr()), ctypes.c_void_p(akind.data_ptr()),
+            ctypes.c_void_p(aval.data_ptr()), _u32_array(iset.widths), _u32_array(iset.heights), k, tw, th,
+            _win_array(windows), (ctypes.c_void_p * m)(*[o.data_ptr() for o in outs]), (ctypes.c_uint64 * m)(*pitches),
+            m, ctypes.c_void_p(astatus.data_ptr()))
+        _check(rc, "nice_decode_set_alpha_dev")
     if stream is not None:
         stream.synchronize()
     st = status.cpu().tolist()
-    bad = [s for s in st if s != OK]
+    ast = astatus.cpu().tolist() if al is not None else None
+    bad = [s for s in st + (ast or []) if s != OK]
     if bad:
-        err = NiceError(bad[0], f"nice_decode_set_dev: {len(bad)} of {len(st)} tiles failed")
+        what = "nice_decode_set_dev" if al is None else "nice_decode_set_dev + nice_decode_set_alpha_dev"
+        err = NiceError(bad[0], f"{what}: {len(bad)} of {len(st) + len(ast or [])} tiles failed")
         err.statuses = st
+        err.alpha_statuses = ast
         err.out = result
         raise err
     return result
@@ -1131,8 +1222,15 @@ def decode_set(iset: ImageSet, images=None, windows=None, out=None, out_channels
 #   K x (u32 width, u32 height), then, exactly as in NICETILE: n x u64 lengths,
 #   (n + 1) x u64 offsets, n x u8 kinds zero-padded to a multiple of 8 bytes,
 #   then the packed bytes
+# A set with an alpha batch is version 2: the reserved word is a flags word
+# (bit 0: alpha present, the only flag and always set), and after the colour
+# packed bytes comes the alpha part exactly as in NICETILE version 2 (u64 alpha
+# packed size, alpha lengths, offsets, kinds, values, alpha packed bytes).
+# A set without one is written as version 1, as before.
 _SET_MAGIC = b"NICESETS"
 _SET_VERSION = 1
+_SET_VERSION_ALPHA = 2
+_SET_FLAG_ALPHA = 1
 _SET_HEADER = "<8sIIIIIIQQ"
 
 
@@ -1159,14 +1257,22 @@ def save_set(path, iset: ImageSet) -> None:
     if size < 0 or size > iset.packed.numel():
         raise NiceError(E_ARG, "save_set: off[n] exceeds the packed buffer")
     blob = iset.packed.detach().reshape(-1)[:size].cpu().numpy()
+    al = iset.alpha
+    if al is not None:
+        if iset.channels != 4:
+            raise NiceError(E_ARG, "save_set: an alpha batch needs a 4-channel set")
+        apart = _alpha_part(al, n, "save_set")
     with open(path, "wb") as fh:
-        fh.write(struct.pack(_SET_HEADER, _SET_MAGIC, _SET_VERSION, iset.channels, iset.tile_w, iset.tile_h, k, 0, n,
+        fh.write(struct.pack(_SET_HEADER, _SET_MAGIC, _SET_VERSION if al is None else _SET_VERSION_ALPHA,
+                             iset.channels, iset.tile_w, iset.tile_h, k, 0 if al is None else _SET_FLAG_ALPHA, n,
                              size))
         fh.write(np.stack([np.asarray(iset.widths, "<u4"), np.asarray(iset.heights, "<u4")], axis=1).tobytes())
         fh.write(lens.astype("<u8").tobytes())
         fh.write(offs.astype("<u8").tobytes())
         fh.write(kinds.tobytes() + bytes(-n % 8))
         fh.write(blob.tobytes())
+        if al is not None:
+            fh.write(apart)
 
 
 def load_set(path, device=None) -> ImageSet:
@@ -1190,11 +1296,13 @@ def load_set(path, device=None) -> ImageSet:
         magic, version, c, tw, th, k, reserved, n, size = struct.unpack(_SET_HEADER, head)
         if magic != _SET_MAGIC:
             raise bad("wrong magic")
-        if version != _SET_VERSION:
+        if version not in (_SET_VERSION, _SET_VERSION_ALPHA):
             raise bad(f"version {version}")
-        if reserved != 0:
-            raise bad("reserved word")
-        if c not in (3, 4):
+        # version 1: a reserved zero; version 2: the flags, alpha (bit 0) the only one and always set
+        has_alpha = version == _SET_VERSION_ALPHA
+        if reserved != (_SET_FLAG_ALPHA if has_alpha else 0):
+            raise bad("flags" if has_alpha else "reserved word")
+        if c not in (3, 4) or (has_alpha and c != 4):
             raise bad("channels")
         if not (2 <= tw <= 8192 and 2 <= th <= 8192):
             raise bad("tile size")
@@ -1212,7 +1320,8 @@ def load_set(path, device=None) -> ImageSet:
         if n * (-(-tw * th // 1024)) >= 1 << 32:
             raise bad("too many tiles")
         kpad = n + (-n % 8)
-        if fsize != hsz + 8 * k + 8 * n + 8 * (n + 1) + kpad + size:
+        colour_end = hsz + 8 * k + 8 * n + 8 * (n + 1) + kpad + size
+        if (fsize < colour_end + 8) if has_alpha else (fsize != colour_end):
             raise bad("file size does not match the header")
         lens = np.frombuffer(fh.read(8 * n), "<u8")
         offs = np.frombuffer(fh.read(8 * (n + 1)), "<u8")
@@ -1232,11 +1341,12 @@ def load_set(path, device=None) -> ImageSet:
         blob = np.frombuffer(fh.read(size), np.uint8)
         if blob.size != size:
             raise bad("truncated")
+        alpha = _load_alpha_part(fh, fsize, colour_end, n, tw, th, bad, device) if has_alpha else None
     packed = torch.from_numpy(blob.copy())
     if device is not None:
         packed = packed.to(device)
     return ImageSet(widths, heights, c, tw, th, first, packed, torch.from_numpy(offs.astype(np.int64)),
-                    torch.from_numpy(lens.astype(np.int64)), torch.from_numpy(kinds[:n].copy()))
+                    torch.from_numpy(lens.astype(np.int64)), torch.from_numpy(kinds[:n].copy()), alpha)
 
 
 def checksum64(buf) -> int:

@@ -24,13 +24,15 @@ is written as an RGBA PNG.
 
 Image sets (many images of different sizes in one container):
 
-    python fast-losless-image-compression-format_amd/cli.py --set DIR OUT[.nices] [--tile WxH]
+    python fast-losless-image-compression-format_amd/cli.py --set DIR OUT[.nices] [--tile WxH] [--alpha]
     python fast-losless-image-compression-format_amd/cli.py IN.nices DIR
     python fast-losless-image-compression-format_amd/cli.py IN.nices OUT.png --index I
 
 --set encodes the 8-bit RGB or RGBA PNGs of DIR (all of one kind, in the order
 of their sorted names) as one set; a .nices input is decoded into DIR as
-000000.png, 000001.png, ..., or image I alone into OUT.png.
+000000.png, 000001.png, ..., or image I alone into OUT.png.  --alpha (RGBA
+PNGs) also stores the alpha channels; a .nices that holds them is written as
+RGBA PNGs.
 """
 from __future__ import annotations
 
@@ -64,7 +66,7 @@ def main(argv=None) -> int:
     ap.add_argument("--strict", action="store_true", help="decode only what the reference decoder can")
     ap.add_argument("--tile", metavar="WxH", help="encode a .png as a tiled image (.nicet) with tiles of W x H pixels")
     ap.add_argument("--roi", metavar="X,Y,W,H", help="decode only this rectangle of a .nicet")
-    ap.add_argument("--alpha", action="store_true", help="with --tile: keep the alpha channel of an RGBA .png")
+    ap.add_argument("--alpha", action="store_true", help="with --tile or --set: keep the alpha channel of RGBA .png input")
     ap.add_argument("--set", action="store_true", help="encode the .png files of directory SRC as one image set (.nices)")
     ap.add_argument("--index", type=int, metavar="I", help="decode image I of a .nices into a .png")
     args = ap.parse_args(argv)
@@ -79,8 +81,8 @@ def main(argv=None) -> int:
         ap.error("--roi needs a .nicet input")
     if tile and not args.src.endswith(".png") and not args.set:
         ap.error("--tile needs a .png input")
-    if args.alpha and (not tile or args.set):
-        ap.error("--alpha needs --tile and a single image")
+    if args.alpha and not tile and not args.set:
+        ap.error("--alpha needs --tile or --set")
     if args.index is not None and not args.src.endswith(".nices"):
         ap.error("--index needs a .nices input")
     nice = _pkg()
@@ -95,19 +97,27 @@ def main(argv=None) -> int:
         if not imgs or len({ch for _, _, _, ch in imgs}) != 1:
             print("--set needs a directory of .png files, all RGB or all RGBA", file=sys.stderr)
             return 2
+        if args.alpha and imgs[0][3] != 4:
+            print("--alpha needs RGBA .png files", file=sys.stderr)
+            return 2
         if not dst.endswith(".nices"):
             dst += ".nices"
         t1 = time.perf_counter()
         iset = nice.encode_set([torch.from_numpy(np.array(px, np.uint8).reshape(h, w, ch)).cuda()
-                                for px, w, h, ch in imgs], tile=tile)
+                                for px, w, h, ch in imgs], tile=tile, alpha=args.alpha)
         print(f"{(time.perf_counter() - t1) * 1e3:.0f}")
         nice.save_set(dst, iset)
         print(f"images: {len(iset)} tiles: {iset.first[-1]} raw: {int(iset.kind.sum())} bytes: {iset.nbytes}")
+        if iset.alpha is not None:
+            k = iset.alpha.kind
+            print(f"alpha tiles: coded: {int((k == 0).sum())} raw: {int((k == 1).sum())} "
+                  f"constant: {int((k == 2).sum())} bytes: {iset.alpha.nbytes}")
         return 0
     if args.src.endswith(".nices"):
         iset = nice.load_set(args.src, device="cuda")
         t0 = time.perf_counter()
-        outs = nice.decode_set(iset, images=None if args.index is None else [args.index], out_channels=3)
+        oc = 3 if iset.alpha is None else 4
+        outs = nice.decode_set(iset, images=None if args.index is None else [args.index], out_channels=oc)
         rgbs = [o.cpu().numpy() for o in outs]
         print(f"nice elapsed in: {(time.perf_counter() - t0) * 1e3:.0f}")
         if args.index is not None:
@@ -116,7 +126,7 @@ def main(argv=None) -> int:
             os.makedirs(dst, exist_ok=True)
             paths = [os.path.join(dst, f"{i:06d}.png") for i in range(len(rgbs))]
         for path, rgb in zip(paths, rgbs):
-            png.write_png(path, rgb.reshape(-1, 3), rgb.shape[1], rgb.shape[0], 3)
+            png.write_png(path, rgb.reshape(-1, oc), rgb.shape[1], rgb.shape[0], oc)
         return 0
     if args.src.endswith(".png") and tile:
         import torch

@@ -171,6 +171,7 @@ struct nice_ctx {
   Arena tiles, tile_dec, tile_tab;
   uint32_t last_tiled_coded = 0, last_tiled_raw = 0;   // test hook nice_test_last_tiled
   uint32_t last_set_coded = 0, last_set_raw = 0;       // test hook nice_test_last_set
+  uint32_t last_set_alpha_coded = 0, last_set_alpha_raw = 0, last_set_alpha_const = 0;   // nice_test_last_set_alpha
   PhaseTimer timer;
   BandState bs;
   // decoder record tags (DecArgs::rec_tag): the region the last call used and its tag
@@ -1586,6 +1587,216 @@ int nice_decode_set_dev(nice_ctx* ctx, void* stream, const uint8_t* d_packed, ui
   return NICE_OK;
 }
 
+// ---- image sets: the alpha batch ---------------------------------------------
+uint64_t nice_set_alpha_bound(const uint32_t* h_w, const uint32_t* h_h, uint32_t K, uint32_t tile_w, uint32_t tile_h) {
+  std::vector<uint32_t> first((size_t)K + 1);
+  if (nice_set_grid(h_w, h_h, K, tile_w, tile_h, first.data())) return 0;
+  const uint64_t per = std::max<uint64_t>(nice_encode_bound(nice_tile_alpha_width(tile_w), tile_h),
+                                          (uint64_t)tile_w * tile_h);
+  return (uint64_t)first[K] * align_up(per, 16);
+}
+
+int nice_set_alpha_range_dev(nice_ctx* ctx, void* stream, const uint8_t* const* h_img, const uint64_t* h_pitch,
+                             const uint32_t* h_w, const uint32_t* h_h, uint32_t K, uint32_t tile_w, uint32_t tile_h,
+                             uint32_t* d_lo, uint32_t* d_hi) {
+  if (!ctx || !d_lo || !d_hi) return NICE_E_ARG;
+  std::vector<uint32_t> first((size_t)K + 1);
+  int rc = nice_set_grid(h_w, h_h, K, tile_w, tile_h, first.data());
+  if (rc) return rc;
+  std::vector<SetImage> tab;
+  if ((rc = set_image_table(h_img, h_pitch, h_w, h_h, K, 4, tile_w, first.data(), tab))) return rc;
+  NICE_HIP(hipSetDevice(ctx->device));
+  if ((rc = ctx->tile_tab.grow(K * sizeof(SetImage)))) return rc;
+  NICE_HIP(hipMemcpyAsync(ctx->tile_tab.ptr, tab.data(), K * sizeof(SetImage), hipMemcpyHostToDevice,
+                          (hipStream_t)stream));
+  return nice::set_alpha_range_launch(stream, (const SetImage*)ctx->tile_tab.ptr, K, first[K], tile_w, tile_h, d_lo,
+                                      d_hi);
+}
+
+int nice_encode_set_alpha_dev(nice_ctx* ctx, void* stream, const uint8_t* const* h_img, const uint64_t* h_pitch,
+                              const uint32_t* h_w, const uint32_t* h_h, uint32_t K, uint32_t tile_w, uint32_t tile_h,
+                              uint8_t* d_apacked, uint64_t apacked_cap, uint64_t* d_aoff, uint64_t* d_alen,
+                              uint8_t* d_akind, uint8_t* d_aval, int32_t* d_status) {
+  if (!ctx || !d_aoff || !d_alen || !d_akind || !d_aval || !d_status) return NICE_E_ARG;
+  if ((!d_apacked && apacked_cap) || ((uintptr_t)d_apacked & 15)) return NICE_E_ARG;
+  std::vector<uint32_t> first((size_t)K + 1);
+  int rc = nice_set_grid(h_w, h_h, K, tile_w, tile_h, first.data());
+  if (rc) return rc;
+  std::vector<SetImage> imgs;
+  if ((rc = set_image_table(h_img, h_pitch, h_w, h_h, K, 4, tile_w, first.data(), imgs))) return rc;
+  NICE_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = (hipStream_t)stream;
+  const uint32_t n = first[K];
+  const uint32_t aw = nice_tile_alpha_width(tile_w);
+  // small tables, sized for every tile coded, as in nice_encode_tiled_alpha_dev
+  // (stream lengths, ranges, the list of coded tiles, their decode statuses and
+  // verdicts), then the image descriptors
+  const size_t o_mlen = 0, o_lo = o_mlen + 8ull * n, o_hi = o_lo + 4ull * n, o_list = o_hi + 4ull * n,
+               o_st = o_list + 4ull * n, o_vk = o_st + 4ull * n, o_img = align_up(o_vk + n, 16);
+  if ((rc = ctx->tile_tab.grow(o_img + K * sizeof(SetImage)))) return rc;
+  uint8_t* dt = (uint8_t*)ctx->tile_tab.ptr;
+  const SetImage* d_imgs = (const SetImage*)(dt + o_img);
+  NICE_HIP(hipMemcpyAsync((void*)d_imgs, imgs.data(), K * sizeof(SetImage), hipMemcpyHostToDevice, st));
+  // first wait: the ranges say which tiles are coded at all
+  if ((rc = nice::set_alpha_range_launch(stream, d_imgs, K, n, tile_w, tile_h, (uint32_t*)(dt + o_lo),
+                                         (uint32_t*)(dt + o_hi))))
+    return rc;
+  std::vector<uint32_t> range(2ull * n), list;
+  NICE_HIP(hipMemcpyAsync(range.data(), dt + o_lo, 8ull * n, hipMemcpyDeviceToHost, st));
+  NICE_HIP(hipStreamSynchronize(st));
+  std::vector<uint8_t> kind(n), val(n);
+  for (uint32_t t = 0; t < n; ++t) {
+    const bool flat = range[t] == range[n + t];
+    kind[t] = flat ? 2 : 0;
+    val[t] = flat ? (uint8_t)range[t] : 0;
+    if (!flat) list.push_back(t);
+  }
+  const uint32_t m = (uint32_t)list.size();
+  NICE_HIP(hipMemcpyAsync(d_akind, kind.data(), n, hipMemcpyHostToDevice, st));
+  NICE_HIP(hipMemcpyAsync(d_aval, val.data(), n, hipMemcpyHostToDevice, st));
+  NICE_HIP(hipMemsetAsync(d_alen, 0, 8ull * n, st));
+  const uint64_t slot = alpha_slot_bytes(tile_w, tile_h);
+  if (m) {
+    const uint64_t trip_stride = align_up((size_t)aw * 3 * tile_h, 16);
+    if ((rc = ctx->tiles.grow((size_t)m * trip_stride))) return rc;
+    if ((rc = ctx->tile_dec.grow((size_t)m * trip_stride))) return rc;
+    if ((rc = ctx->pack.grow((size_t)m * slot))) return rc;
+    uint8_t* trip = (uint8_t*)ctx->tiles.ptr;
+    uint8_t* back = (uint8_t*)ctx->tile_dec.ptr;
+    uint8_t* slots = (uint8_t*)ctx->pack.ptr;
+    uint32_t* d_list = (uint32_t*)(dt + o_list);
+    uint64_t* mlen = (uint64_t*)(dt + o_mlen);
+    int32_t* dec_status = (int32_t*)(dt + o_st);
+    uint8_t* vk = dt + o_vk;
+    NICE_HIP(hipMemcpyAsync(d_list, list.data(), 4ull * m, hipMemcpyHostToDevice, st));
+    if ((rc = nice::set_alpha_gather_launch(stream, d_imgs, K, tile_w, tile_h, d_list, m, trip, trip_stride))) return rc;
+    // from here on exactly nice_encode_tiled_alpha_dev's sequence, over the non-constant tiles of all images
+    if ((rc = nice_encode_batch_dev(ctx, stream, trip, trip_stride, m, aw, tile_h, 3, 3, slots, slot, mlen))) return rc;
+    // second wait: the stream lengths size the verify decode
+    if ((rc = nice::decode_batch_impl(ctx, stream, slots, slot, mlen, nullptr, m, aw, tile_h, 3, back, trip_stride,
+                                      NICE_DEC_TOLERANT_HEADER, dec_status)))
+      return rc;
+    if ((rc = nice::tiles_compare_launch(stream, trip, trip_stride, back, trip_stride, 3, m, aw * tile_h, dec_status,
+                                         vk)))
+      return rc;
+    if ((rc = nice::alpha_store_launch(stream, trip, trip_stride, tile_w, tile_h, d_list, m, vk, mlen, slots, slot,
+                                       d_akind, d_alen)))
+      return rc;
+  }
+  if ((rc = nice::pack_offsets_launch(stream, slot, d_alen, n, apacked_cap, d_aoff, d_status))) return rc;
+  return m ? nice::alpha_pack_launch(stream, (const uint8_t*)ctx->pack.ptr, slot, (const uint64_t*)(dt + o_mlen),
+                                     (const uint32_t*)(dt + o_list), m, d_aoff, d_apacked, apacked_cap)
+           : NICE_OK;
+}
+
+int nice_decode_set_alpha_dev(nice_ctx* ctx, void* stream, const uint8_t* d_apacked, uint64_t apacked_bytes,
+                              const uint64_t* h_aoff, const uint64_t* h_alen, const uint8_t* h_akind,
+                              const uint8_t* h_aval, const uint32_t* h_w, const uint32_t* h_h, uint32_t K,
+                              uint32_t tile_w, uint32_t tile_h, const uint32_t* h_win, uint8_t* const* h_out,
+                              const uint64_t* h_out_pitch, uint32_t M, int32_t* d_status) {
+  if (!ctx || !h_aoff || !h_alen || !h_akind || !h_aval || !d_status) return NICE_E_ARG;
+  if ((!d_apacked && apacked_bytes) || ((uintptr_t)d_apacked & 15)) return NICE_E_ARG;
+  std::vector<uint32_t> first((size_t)K + 1), slot_first((size_t)M + 1);
+  int rc = nice_set_select(h_w, h_h, K, tile_w, tile_h, h_win, M, slot_first.data());
+  if (rc) return rc;
+  (void)nice_set_grid(h_w, h_h, K, tile_w, tile_h, first.data());
+  std::vector<SetWindow> wins;
+  if ((rc = set_window_table(h_w, h_h, K, tile_w, tile_h, h_win, h_out, h_out_pitch, M, 4, wins))) return rc;
+  NICE_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = (hipStream_t)stream;
+  const uint32_t m = slot_first[M];
+  const uint64_t npx = (uint64_t)tile_w * tile_h;
+  const uint32_t aw = nice_tile_alpha_width(tile_w);
+  // every (window, tile) pair is a slot: the coded ones to decode, and every
+  // slot to merge with its source; a slot refused here keeps its status and is
+  // not touched
+  std::vector<uint64_t> c_off, c_len, s_src;
+  std::vector<uint32_t> c_pos, s_win, s_idx;
+  std::vector<uint8_t> s_kind;
+  std::vector<int32_t> init(m, NICE_OK);
+  uint32_t by_kind[3] = {0, 0, 0};
+  uint32_t p = 0;
+  for (uint32_t j = 0; j < M; ++j) {
+    const uint32_t* q = h_win + 5ull * j;
+    const uint32_t nx = wins[j].nx;
+    const uint32_t tx0 = q[1] / tile_w, ty0 = q[2] / tile_h;
+    const uint32_t tx1 = (q[1] + q[3] - 1) / tile_w + 1, ty1 = (q[2] + q[4] - 1) / tile_h + 1;
+    for (uint32_t ty = ty0; ty < ty1; ++ty) {
+      for (uint32_t tx = tx0; tx < tx1; ++tx, ++p) {
+        const uint32_t ti = ty * nx + tx, t = first[q[0]] + ti;
+        const uint64_t off = h_aoff[t], len = h_alen[t];
+        const uint8_t k = h_akind[t];
+        uint64_t src;
+        if (k > 2) {
+          init[p] = NICE_E_FORMAT;
+          continue;
+        } else if ((off & 15) || off > apacked_bytes || len > apacked_bytes - off) {
+          init[p] = NICE_E_ARG;
+          continue;
+        } else if (k == 2 ? len != 0 : k == 1 ? len != npx : len == 0) {   // (no stream is empty)
+          init[p] = NICE_E_FORMAT;
+          continue;
+        } else if (k == 2) {
+          src = h_aval[t];
+        } else if (k == 1) {
+          src = off;
+        } else {
+          src = c_off.size();
+          c_off.push_back(off);
+          c_len.push_back(len);
+          c_pos.push_back(p);
+        }
+        s_src.push_back(src);
+        s_win.push_back(j);
+        s_idx.push_back(ti);
+        s_kind.push_back(k);
+        ++by_kind[k];
+      }
+    }
+  }
+  const uint32_t nc = (uint32_t)c_off.size(), ns = (uint32_t)s_idx.size();
+  ctx->last_set_alpha_coded = by_kind[0];
+  ctx->last_set_alpha_raw = by_kind[1];
+  ctx->last_set_alpha_const = by_kind[2];
+  // one upload: the window descriptors, u64 {coded offsets, coded lengths,
+  // sources}, u32 {coded positions, windows, tile indices}, u8 kinds; then the
+  // coded statuses
+  const size_t o_win = 0, o_coff = o_win + M * sizeof(SetWindow), o_clen = o_coff + 8ull * nc, o_src = o_clen + 8ull * nc,
+               o_cpos = o_src + 8ull * ns, o_swin = o_cpos + 4ull * nc, o_idx = o_swin + 4ull * ns,
+               o_kind = o_idx + 4ull * ns, o_cst = align_up(o_kind + ns, 16), tab_bytes = o_cst + 4ull * nc;
+  std::vector<uint8_t> tab(o_cst);
+  memcpy(&tab[o_win], wins.data(), M * sizeof(SetWindow));
+  if (nc) {
+    memcpy(&tab[o_coff], c_off.data(), 8ull * nc);
+    memcpy(&tab[o_clen], c_len.data(), 8ull * nc);
+    memcpy(&tab[o_cpos], c_pos.data(), 4ull * nc);
+  }
+  if (ns) {
+    memcpy(&tab[o_src], s_src.data(), 8ull * ns);
+    memcpy(&tab[o_swin], s_win.data(), 4ull * ns);
+    memcpy(&tab[o_idx], s_idx.data(), 4ull * ns);
+    memcpy(&tab[o_kind], s_kind.data(), ns);
+  }
+  const uint64_t stride = align_up((size_t)aw * 3 * tile_h, 16);
+  if ((rc = ctx->tile_tab.grow(std::max<size_t>(tab_bytes, 16)))) return rc;
+  if (nc && (rc = ctx->tile_dec.grow((size_t)nc * stride))) return rc;
+  uint8_t* dt = (uint8_t*)ctx->tile_tab.ptr;
+  NICE_HIP(hipMemcpyAsync(dt, tab.data(), o_cst, hipMemcpyHostToDevice, st));
+  NICE_HIP(hipMemcpyAsync(d_status, init.data(), 4ull * m, hipMemcpyHostToDevice, st));
+  int32_t* cst = (int32_t*)(dt + o_cst);
+  if (nc) {
+    if ((rc = nice::decode_batch_impl(ctx, stream, d_apacked, 0, (const uint64_t*)(dt + o_clen), c_len.data(), nc, aw,
+                                      tile_h, 3, (uint8_t*)ctx->tile_dec.ptr, stride, NICE_DEC_TOLERANT_HEADER, cst,
+                                      (const uint64_t*)(dt + o_coff), apacked_bytes)))
+      return rc;
+    if ((rc = nice::tiles_scatter_status_launch(stream, cst, (const uint32_t*)(dt + o_cpos), nc, d_status))) return rc;
+  }
+  return nice::set_alpha_merge_launch(stream, (const uint8_t*)ctx->tile_dec.ptr, stride, cst, d_apacked,
+                                      (const uint64_t*)(dt + o_src), dt + o_kind, (const uint32_t*)(dt + o_swin),
+                                      (const uint32_t*)(dt + o_idx), ns, (const SetWindow*)(dt + o_win), M, tile_w,
+                                      tile_h);
+}
+
 // ---- one image sharded over ranks ------------------------
 int nice_band_classify(nice_ctx* ctx, void* stream, const uint8_t* d_px, uint64_t px0, uint64_t px_count,
                        uint32_t w, uint32_t h, uint8_t channels, uint8_t channels_out, uint32_t tile_lo,
@@ -1962,6 +2173,14 @@ int nice_test_last_set(nice_ctx* ctx, uint32_t* coded, uint32_t* raw) {
   if (!ctx || !coded || !raw) return NICE_E_ARG;
   *coded = ctx->last_set_coded;
   *raw = ctx->last_set_raw;
+  return NICE_OK;
+}
+
+int nice_test_last_set_alpha(nice_ctx* ctx, uint32_t* coded, uint32_t* raw, uint32_t* constant) {
+  if (!ctx || !coded || !raw || !constant) return NICE_E_ARG;
+  *coded = ctx->last_set_alpha_coded;
+  *raw = ctx->last_set_alpha_raw;
+  *constant = ctx->last_set_alpha_const;
   return NICE_OK;
 }
 

@@ -116,6 +116,24 @@ int set_merge_launch(void* stream, const uint8_t* d_tiles, uint64_t tile_stride,
                      uint32_t n_slots, const SetWindow* d_wins, uint32_t n_wins, uint32_t tile_w, uint32_t tile_h,
                      uint32_t tile_channels, uint32_t out_channels, uint32_t fill);
 
+// ---- the alpha batch of an image set (nice_sets.hip) --------------------------
+// The set forms of alpha_range_launch, alpha_gather_launch and alpha_merge_launch
+// above: tiles are global tile indices, their images (RGBA) come from d_imgs.
+// d_lo[g], d_hi[g] = min, max of byte +3 over global tile g, g < n (both preset by the call).
+int set_alpha_range_launch(void* stream, const SetImage* d_imgs, uint32_t K, uint32_t n, uint32_t tile_w,
+                           uint32_t tile_h, uint32_t* d_lo, uint32_t* d_hi);
+// The triplet image of global tile d_list[i] dense at d_trip + i * trip_stride, i < m.
+int set_alpha_gather_launch(void* stream, const SetImage* d_imgs, uint32_t K, uint32_t tile_w, uint32_t tile_h,
+                            const uint32_t* d_list, uint32_t m, uint8_t* d_trip, uint64_t trip_stride);
+// Byte +3 of the windows' RGBA pixels.  Slot i holds tile d_slot_tile[i] of the
+// image of window d_slot_win[i], of d_kind[i] with source d_src[i] as for
+// alpha_merge_launch.  Skipped: a coded slot whose d_dec_status is nonzero, a
+// window index >= n_wins, a tile index outside the image.
+int set_alpha_merge_launch(void* stream, const uint8_t* d_dec, uint64_t dec_stride, const int32_t* d_dec_status,
+                           const uint8_t* d_packed, const uint64_t* d_src, const uint8_t* d_kind,
+                           const uint32_t* d_slot_win, const uint32_t* d_slot_tile, uint32_t n_slots,
+                           const SetWindow* d_wins, uint32_t n_wins, uint32_t tile_w, uint32_t tile_h);
+
 // nice_ctx_reserve; with_packed: also the strided scratch of
 // nice_encode_batch_packed_dev (n_frames stream slots).
 int ctx_reserve_impl(nice_ctx* ctx, uint32_t n_frames, uint32_t w, uint32_t h, bool with_packed);

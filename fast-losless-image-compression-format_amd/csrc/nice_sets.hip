@@ -7,6 +7,7 @@
 // a block works for is found once per block from a small descriptor table, by
 // wave-uniform loads, and the move mode is a field of that descriptor, so one
 // launch serves members that need different modes (a wave-uniform branch).
+// The set's alpha batch (range, gather, merge) follows the colour kernels.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -86,19 +87,24 @@ __device__ __forceinline__ void set_split_rows(const SetImage& d, uint32_t C, ui
   }
 }
 
-// Images -> tiles.  Block b works on global tile b / bands; its image is the
-// last one whose `first` is not above that tile (first[0] == 0), found by a
-// binary search of the descriptor table as pack_copy searches the offsets:
-// log2(K) dependent scalar loads per block of about 32 KiB moved.
-__global__ __launch_bounds__(TL_THREADS) void set_split(SetSplitArgs a) {
-  const uint32_t gt = blockIdx.x / a.bands, band = blockIdx.x % a.bands;
-  uint32_t lo = 0, hi = a.K;
+// The image of global tile gt (wave-uniform): the last one whose `first` is not
+// above that tile (first[0] == 0), found by a binary search of the descriptor
+// table as pack_copy searches the offsets: log2(K) dependent scalar loads.
+__device__ __forceinline__ uint32_t set_image_of(const SetImage* imgs, uint32_t K, uint32_t gt) {
+  uint32_t lo = 0, hi = K;
   while (hi - lo > 1) {
     const uint32_t mid = lo + ((hi - lo) >> 1);
-    if (a.imgs[mid].first <= gt) lo = mid;
+    if (imgs[mid].first <= gt) lo = mid;
     else hi = mid;
   }
-  const SetImage d = a.imgs[lo];
+  return lo;
+}
+
+// Images -> tiles.  Block b works on global tile b / bands of its image
+// (set_image_of: once per block of about 32 KiB moved).
+__global__ __launch_bounds__(TL_THREADS) void set_split(SetSplitArgs a) {
+  const uint32_t gt = blockIdx.x / a.bands, band = blockIdx.x % a.bands;
+  const SetImage d = a.imgs[set_image_of(a.imgs, a.K, gt)];
   const uint32_t t = gt - d.first;
   const uint32_t ty = t / d.nx, tx = t % d.nx;
   const uint32_t r0 = band * a.rows_pb, r1 = min(r0 + a.rows_pb, a.th);
@@ -207,6 +213,135 @@ __global__ __launch_bounds__(TL_THREADS) void set_merge(SetMergeArgs a) {
   else set_merge_rows<TL_BYTES>(a, d, st, (uint32_t)tx0, (uint32_t)ty0, xa, nxp, ya, yb);
 }
 
+// ---- alpha (include/nice.h, "image sets: alpha") -------------------------------
+// The set forms of nice_tiles.hip's alpha_range, alpha_gather and alpha_merge:
+// the rows are theirs (nice_tiles.hpp); the image or the window comes from the
+// descriptor table, and with it the mode.
+
+struct SetAlphaRangeArgs {
+  const SetImage* imgs;
+  uint32_t K;
+  uint32_t tw, th, bands, rows_pb;
+  uint32_t* lo;
+  uint32_t* hi;
+};
+
+template <int MODE>
+__device__ __forceinline__ void set_alpha_range_rows(const SetImage& d, uint32_t xs, uint32_t xe, uint32_t ys, uint32_t ye,
+                                                     uint32_t* lo, uint32_t* hi) {
+  const uint32_t lane = threadIdx.x & 63u, wave = tl_wave();
+  uint32_t mn = 255u, mx = 0u;
+  for (uint32_t y = ys + wave; y < ye; y += TL_WAVES)
+    alpha_range_row<MODE>(d.img + (uint64_t)y * d.pitch, d.w, xs, xe, lane, mn, mx);
+  alpha_range_commit(mn, mx, lane, lo, hi);
+}
+
+// lo[g] / hi[g] = min / max of byte +3 over global tile g (preset to 255 / 0).
+// Only pixels inside the tile's image are read.
+__global__ __launch_bounds__(TL_THREADS) void set_alpha_range(SetAlphaRangeArgs a) {
+  const uint32_t gt = blockIdx.x / a.bands, band = blockIdx.x % a.bands;
+  const SetImage d = a.imgs[set_image_of(a.imgs, a.K, gt)];
+  const uint32_t t = gt - d.first;
+  const uint32_t ty = t / d.nx, tx = t % d.nx;
+  const uint32_t xs = tx * a.tw, xe = min(xs + a.tw, d.w);
+  const uint32_t ys = ty * a.th + band * a.rows_pb;
+  const uint32_t ye = min(ty * a.th + min((band + 1) * a.rows_pb, a.th), d.h);
+  if (d.mode == TL_QUAD) set_alpha_range_rows<TL_QUAD>(d, xs, xe, ys, ye, &a.lo[gt], &a.hi[gt]);
+  else if (d.mode == TL_DWORD) set_alpha_range_rows<TL_DWORD>(d, xs, xe, ys, ye, &a.lo[gt], &a.hi[gt]);
+  else set_alpha_range_rows<TL_BYTES>(d, xs, xe, ys, ye, &a.lo[gt], &a.hi[gt]);
+}
+
+struct SetAlphaGatherArgs {
+  const SetImage* imgs;
+  uint32_t K;
+  uint32_t tw, th, bands, rows_pb;
+  const uint32_t* list;
+  uint32_t aw3;
+  uint8_t* trip;
+  uint64_t trip_stride;
+};
+
+// Triplet image of global tile list[i] at trip + i * trip_stride (bytes, as alpha_gather).
+__global__ __launch_bounds__(TL_THREADS) void set_alpha_gather(SetAlphaGatherArgs a) {
+  const uint32_t i = blockIdx.x / a.bands, band = blockIdx.x % a.bands;
+  const uint32_t gt = a.list[i];
+  const SetImage d = a.imgs[set_image_of(a.imgs, a.K, gt)];
+  const uint32_t t = gt - d.first;
+  const uint32_t ty = t / d.nx, tx = t % d.nx;
+  const uint32_t lane = threadIdx.x & 63u, wave = tl_wave();
+  const uint32_t r0 = band * a.rows_pb, r1 = min(r0 + a.rows_pb, a.th);
+  const uint32_t xs = tx * a.tw, xl = d.w - 1;
+  uint8_t* dt = a.trip + (uint64_t)i * a.trip_stride;
+  for (uint32_t r = r0 + wave; r < r1; r += TL_WAVES) {
+    const uint8_t* srow = d.img + (uint64_t)min(ty * a.th + r, d.h - 1) * d.pitch;
+    alpha_gather_row(srow, dt + (uint64_t)r * a.aw3, a.aw3, xs, a.tw, xl, lane);
+  }
+}
+
+struct SetAlphaMergeArgs {
+  const uint8_t* dec;                  // decoded triplet images, dec_stride apart, rows of aw3 bytes
+  uint64_t dec_stride;
+  uint32_t aw3;
+  const int32_t* dec_status;           // of the decoded images
+  const uint8_t* packed;               // raw planes at their offsets
+  const unsigned long long* src;       // per slot: decoded image index, offset in packed, or the constant
+  const uint8_t* kind;                 // per slot: 0 coded, 1 raw, 2 constant
+  const uint32_t* slot_win;
+  const uint32_t* slot_tile;
+  const SetWindow* wins;
+  uint32_t n_wins;
+  uint32_t tw, th, bands, rows_pb;
+  uint32_t mode_cap;                   // TL_QUAD where tw % 4 == 0, else TL_BYTES
+};
+
+template <int MODE>
+__device__ __forceinline__ void set_alpha_merge_rows(const SetWindow& d, const uint8_t* st, uint32_t sp, bool cst,
+                                                     uint32_t cval, uint32_t tx0, uint32_t ty0, uint32_t xa, uint32_t nxp,
+                                                     uint32_t ya, uint32_t yb) {
+  const uint32_t lane = threadIdx.x & 63u, wave = tl_wave();
+  for (uint32_t y = ya + wave; y < yb; y += TL_WAVES) {
+    const uint8_t* srow = st + (uint64_t)(y - ty0) * sp + (xa - tx0);
+    uint8_t* drow = d.out + (uint64_t)(y - d.y0) * d.pitch + 4ull * (xa - d.x0);
+    alpha_merge_row<MODE>(srow, drow, nxp, cst, cval, lane);
+  }
+}
+
+// Byte +3 of the windows' pixels.  Slot i holds tile slot_tile[i] of the image
+// of window slot_win[i], cut to that window and the image exactly as set_merge
+// cuts it.  Skipped: a coded slot whose decode failed, a window index >= n_wins,
+// a tile index outside its image.  The quad mode is the window's own (16-byte
+// base and pitch, x0 % 4 == 0) where tw % 4 == 0: then xa and the row are
+// 16-byte aligned.
+__global__ __launch_bounds__(TL_THREADS) void set_alpha_merge(SetAlphaMergeArgs a) {
+  const uint32_t slot = blockIdx.x / a.bands, band = blockIdx.x % a.bands;
+  const uint32_t kind = a.kind[slot];
+  const unsigned long long src = a.src[slot];
+  if (kind == 0 && a.dec_status[src] != 0) return;
+  const uint32_t wi = a.slot_win[slot];
+  if (wi >= a.n_wins) return;
+  const SetWindow d = a.wins[wi];
+  const uint32_t t = a.slot_tile[slot];
+  if (t >= d.n_tiles) return;
+  const uint32_t ty = t / d.nx, tx = t % d.nx;
+  const uint64_t tx0 = (uint64_t)tx * a.tw, ty0 = (uint64_t)ty * a.th;
+  const uint64_t xa64 = max(tx0, (uint64_t)d.x0);
+  const uint64_t xb64 = min(min(tx0 + a.tw, (uint64_t)d.x0 + d.rw), (uint64_t)d.w);
+  const uint64_t ya64 = max(ty0 + (uint64_t)band * a.rows_pb, (uint64_t)d.y0);
+  const uint64_t yb64 = min(min(ty0 + min((uint64_t)(band + 1) * a.rows_pb, (uint64_t)a.th), (uint64_t)d.y0 + d.rh),
+                            (uint64_t)d.h);
+  if (xa64 >= xb64 || ya64 >= yb64) return;
+  const uint32_t xa = (uint32_t)xa64, nxp = (uint32_t)(xb64 - xa64), ya = (uint32_t)ya64, yb = (uint32_t)yb64;
+  const bool cst = kind == 2;
+  const uint32_t cval = (uint32_t)src & 255u;
+  // the tile's plane: row pitch and first byte (unused for a constant)
+  const uint32_t sp = kind == 0 ? a.aw3 : a.tw;
+  const uint8_t* st = cst ? d.out : kind == 0 ? a.dec + src * a.dec_stride : a.packed + src;
+  if (min(d.mode, a.mode_cap) == TL_QUAD)
+    set_alpha_merge_rows<TL_QUAD>(d, st, sp, cst, cval, (uint32_t)tx0, (uint32_t)ty0, xa, nxp, ya, yb);
+  else
+    set_alpha_merge_rows<TL_BYTES>(d, st, sp, cst, cval, (uint32_t)tx0, (uint32_t)ty0, xa, nxp, ya, yb);
+}
+
 namespace {
 // the best mode a base and its pitch (or stride) allow on their own
 uint32_t mode_of(const void* p, uint64_t s) {
@@ -246,6 +381,40 @@ int set_merge_launch(void* stream, const uint8_t* d_tiles, uint64_t tile_stride,
     if (a.mode_cap == TL_QUAD && (tile_w & 3u) != 0) a.mode_cap = TL_DWORD;
   }
   hipLaunchKernelGGL(set_merge, dim3(n_slots * a.bands), dim3(TL_THREADS), 0, (hipStream_t)stream, a);
+  return hipGetLastError() == hipSuccess ? NICE_OK : NICE_E_HIP;
+}
+
+int set_alpha_range_launch(void* stream, const SetImage* d_imgs, uint32_t K, uint32_t n, uint32_t tile_w,
+                           uint32_t tile_h, uint32_t* d_lo, uint32_t* d_hi) {
+  SetAlphaRangeArgs a{d_imgs, K, tile_w, tile_h, 0, 0, d_lo, d_hi};
+  if (!tl_bands(n, tile_h, 4ull * tile_w, a.bands, a.rows_pb)) return NICE_E_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  if (hipMemsetAsync(d_lo, 0xFF, 4ull * n, st) != hipSuccess) return NICE_E_HIP;   // (atomicMin brings it down to <= 255)
+  if (hipMemsetAsync(d_hi, 0, 4ull * n, st) != hipSuccess) return NICE_E_HIP;
+  hipLaunchKernelGGL(set_alpha_range, dim3(n * a.bands), dim3(TL_THREADS), 0, st, a);
+  return hipGetLastError() == hipSuccess ? NICE_OK : NICE_E_HIP;
+}
+
+int set_alpha_gather_launch(void* stream, const SetImage* d_imgs, uint32_t K, uint32_t tile_w, uint32_t tile_h,
+                            const uint32_t* d_list, uint32_t m, uint8_t* d_trip, uint64_t trip_stride) {
+  if (m == 0) return NICE_OK;
+  const uint32_t aw3 = (tile_w + 2u) / 3u * 3u;
+  SetAlphaGatherArgs a{d_imgs, K, tile_w, tile_h, 0, 0, d_list, aw3, d_trip, trip_stride};
+  if (!tl_bands(m, tile_h, aw3, a.bands, a.rows_pb)) return NICE_E_ARG;
+  hipLaunchKernelGGL(set_alpha_gather, dim3(m * a.bands), dim3(TL_THREADS), 0, (hipStream_t)stream, a);
+  return hipGetLastError() == hipSuccess ? NICE_OK : NICE_E_HIP;
+}
+
+int set_alpha_merge_launch(void* stream, const uint8_t* d_dec, uint64_t dec_stride, const int32_t* d_dec_status,
+                           const uint8_t* d_packed, const uint64_t* d_src, const uint8_t* d_kind,
+                           const uint32_t* d_slot_win, const uint32_t* d_slot_tile, uint32_t n_slots,
+                           const SetWindow* d_wins, uint32_t n_wins, uint32_t tile_w, uint32_t tile_h) {
+  if (n_slots == 0) return NICE_OK;
+  SetAlphaMergeArgs a{d_dec, dec_stride, (tile_w + 2u) / 3u * 3u, d_dec_status, d_packed, (const unsigned long long*)d_src,
+                      d_kind, d_slot_win, d_slot_tile, d_wins, n_wins, tile_w, tile_h, 0, 0,
+                      (tile_w & 3u) == 0 ? (uint32_t)TL_QUAD : (uint32_t)TL_BYTES};
+  if (!tl_bands(n_slots, tile_h, 4ull * tile_w, a.bands, a.rows_pb)) return NICE_E_ARG;
+  hipLaunchKernelGGL(set_alpha_merge, dim3(n_slots * a.bands), dim3(TL_THREADS), 0, (hipStream_t)stream, a);
   return hipGetLastError() == hipSuccess ? NICE_OK : NICE_E_HIP;
 }
 

@@ -257,79 +257,13 @@ __global__ __launch_bounds__(TL_THREADS) void alpha_range(const uint8_t* __restr
   const uint32_t t = blockIdx.x / q.bands, band = blockIdx.x % q.bands;
   const uint32_t ty = t / q.nx, tx = t % q.nx;
   const uint32_t lane = threadIdx.x & 63u, wave = tl_wave();
-  const uint32_t xs = tx * q.tw, xe = min(xs + q.tw, q.w), xl = q.w - 1;
+  const uint32_t xs = tx * q.tw, xe = min(xs + q.tw, q.w);
   const uint32_t ys = ty * q.th + band * q.rows_pb;
   const uint32_t ye = min(ty * q.th + min((band + 1) * q.rows_pb, q.th), q.h);
   uint32_t mn = 255u, mx = 0u;
-  for (uint32_t y = ys + wave; y < ye; y += TL_WAVES) {
-    const uint8_t* srow = img + (uint64_t)y * pitch;
-    if (MODE == TL_QUAD) {   // the 16-byte groups of the row that hold [xs, xe)
-      const uint32_t gb = xs >> 2, ge = (xe + 3u) >> 2;
-      for (uint32_t g0 = gb; g0 < ge; g0 += 64u * TL_UNROLL) {
-        uint4 v[TL_UNROLL];
-#pragma unroll
-        for (uint32_t u = 0; u < TL_UNROLL; ++u) {
-          const uint32_t g = g0 + 64u * u + lane;
-          if (g < ge) {
-            const uint32_t x = 4u * g;
-            if (x + 4u <= q.w) {
-              v[u] = *reinterpret_cast<const uint4*>(srow + 16ull * g);
-            } else {   // the image ends inside this group
-              v[u].x = ld32(srow + 4ull * x);
-              v[u].y = ld32(srow + 4ull * min(x + 1u, xl));
-              v[u].z = ld32(srow + 4ull * min(x + 2u, xl));
-              v[u].w = ld32(srow + 4ull * min(x + 3u, xl));
-            }
-          }
-        }
-#pragma unroll
-        for (uint32_t u = 0; u < TL_UNROLL; ++u) {
-          const uint32_t g = g0 + 64u * u + lane;
-          if (g < ge) {
-            const uint32_t x = 4u * g;
-            const uint32_t a[4] = {v[u].x >> 24, v[u].y >> 24, v[u].z >> 24, v[u].w >> 24};
-#pragma unroll
-            for (uint32_t k = 0; k < 4; ++k) {
-              if (x + k >= xs && x + k < xe) {   // the tile's own pixels of the group
-                mn = min(mn, a[k]);
-                mx = max(mx, a[k]);
-              }
-            }
-          }
-        }
-      }
-    } else {
-      const uint32_t nxp = xe - xs;
-      for (uint32_t g0 = 0; g0 < nxp; g0 += 64u * TL_UNROLL) {
-        uint32_t a[TL_UNROLL];
-#pragma unroll
-        for (uint32_t u = 0; u < TL_UNROLL; ++u) {
-          const uint32_t g = g0 + 64u * u + lane;
-          if (g < nxp) {
-            const uint8_t* s = srow + 4ull * (xs + g);
-            a[u] = MODE == TL_DWORD ? ld32(s) >> 24 : (uint32_t)s[3];
-          }
-        }
-#pragma unroll
-        for (uint32_t u = 0; u < TL_UNROLL; ++u) {
-          const uint32_t g = g0 + 64u * u + lane;
-          if (g < nxp) {
-            mn = min(mn, a[u]);
-            mx = max(mx, a[u]);
-          }
-        }
-      }
-    }
-  }
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) {
-    mn = min(mn, (uint32_t)__shfl_xor((int)mn, d, 64));
-    mx = max(mx, (uint32_t)__shfl_xor((int)mx, d, 64));
-  }
-  if (lane == 0 && mn <= mx) {   // (a wave without rows has nothing to say)
-    atomicMin(&lo[t], mn);
-    atomicMax(&hi[t], mx);
-  }
+  for (uint32_t y = ys + wave; y < ye; y += TL_WAVES)
+    alpha_range_row<MODE>(img + (uint64_t)y * pitch, q.w, xs, xe, lane, mn, mx);
+  alpha_range_commit(mn, mx, lane, &lo[t], &hi[t]);
 }
 
 // Triplet image of tile list[i] at trip + i * trip_stride: byte j of row r is
@@ -347,20 +281,7 @@ __global__ __launch_bounds__(TL_THREADS) void alpha_gather(const uint8_t* __rest
   uint8_t* dt = trip + (uint64_t)i * trip_stride;
   for (uint32_t r = r0 + wave; r < r1; r += TL_WAVES) {
     const uint8_t* srow = img + (uint64_t)min(ty * q.th + r, q.h - 1) * pitch;
-    uint8_t* drow = dt + (uint64_t)r * aw3;
-    for (uint32_t g0 = 0; g0 < aw3; g0 += 64u * TL_UNROLL) {
-      uint8_t v[TL_UNROLL];
-#pragma unroll
-      for (uint32_t u = 0; u < TL_UNROLL; ++u) {
-        const uint32_t g = g0 + 64u * u + lane;
-        if (g < aw3) v[u] = srow[4ull * min(xs + min(g, q.tw - 1u), xl) + 3u];
-      }
-#pragma unroll
-      for (uint32_t u = 0; u < TL_UNROLL; ++u) {
-        const uint32_t g = g0 + 64u * u + lane;
-        if (g < aw3) drow[g] = v[u];
-      }
-    }
+    alpha_gather_row(srow, dt + (uint64_t)r * aw3, aw3, xs, q.tw, xl, lane);
   }
 }
 
@@ -488,63 +409,7 @@ __global__ __launch_bounds__(TL_THREADS) void alpha_merge(AlphaMergeArgs a, Tile
   for (uint32_t y = ya + wave; y < yb; y += TL_WAVES) {
     const uint8_t* srow = st + (uint64_t)(y - (uint32_t)ty0) * sp + (xa - (uint32_t)tx0);
     uint8_t* drow = a.out + (uint64_t)(y - a.y0) * a.out_pitch + 4ull * (xa - a.x0);
-    if (MODE == TL_QUAD) {
-      const uint32_t G = (nxp + 3u) >> 2;
-      for (uint32_t g0 = 0; g0 < G; g0 += 64u * TL_UNROLL) {
-        uint4 v[TL_UNROLL];
-        uint32_t al4[TL_UNROLL];   // four alpha bytes, pixel k in bits 8k..8k+7
-#pragma unroll
-        for (uint32_t u = 0; u < TL_UNROLL; ++u) {
-          const uint32_t g = g0 + 64u * u + lane;
-          if (g < G) {
-            const uint32_t k = min(nxp - 4u * g, 4u);   // pixels of the group: 1..4
-            if (k == 4u) v[u] = *reinterpret_cast<const uint4*>(drow + 16ull * g);
-            uint32_t p = cval * 0x01010101u;
-            if (!cst) {
-              const uint8_t* s = srow + 4u * g;
-              p = s[0];
-              if (k > 1) p |= (uint32_t)s[1] << 8;
-              if (k > 2) p |= (uint32_t)s[2] << 16;
-              if (k > 3) p |= (uint32_t)s[3] << 24;
-            }
-            al4[u] = p;
-          }
-        }
-#pragma unroll
-        for (uint32_t u = 0; u < TL_UNROLL; ++u) {
-          const uint32_t g = g0 + 64u * u + lane;
-          if (g < G) {
-            uint8_t* d = drow + 16ull * g;
-            const uint32_t k = min(nxp - 4u * g, 4u), p = al4[u];
-            if (k == 4u) {
-              v[u].x = (v[u].x & 0xFFFFFFu) | (p << 24);
-              v[u].y = (v[u].y & 0xFFFFFFu) | ((p >> 8) << 24);
-              v[u].z = (v[u].z & 0xFFFFFFu) | ((p >> 16) << 24);
-              v[u].w = (v[u].w & 0xFFFFFFu) | ((p >> 24) << 24);
-              *reinterpret_cast<uint4*>(d) = v[u];
-            } else {
-              d[3] = (uint8_t)p;
-              if (k > 1) d[7] = (uint8_t)(p >> 8);
-              if (k > 2) d[11] = (uint8_t)(p >> 16);
-            }
-          }
-        }
-      }
-    } else {
-      for (uint32_t g0 = 0; g0 < nxp; g0 += 64u * TL_UNROLL) {
-        uint8_t v[TL_UNROLL];
-#pragma unroll
-        for (uint32_t u = 0; u < TL_UNROLL; ++u) {
-          const uint32_t g = g0 + 64u * u + lane;
-          if (g < nxp) v[u] = cst ? (uint8_t)cval : srow[g];
-        }
-#pragma unroll
-        for (uint32_t u = 0; u < TL_UNROLL; ++u) {
-          const uint32_t g = g0 + 64u * u + lane;
-          if (g < nxp) drow[4ull * g + 3u] = v[u];
-        }
-      }
-    }
+    alpha_merge_row<MODE>(srow, drow, nxp, cst, cval, lane);
   }
 }
 

@@ -361,9 +361,10 @@ int nice_decode_tiled_alpha_dev(nice_ctx* ctx, void* stream, const uint8_t* d_ap
  * the offsets rebased.
  * NICE_E_ARG: K == 0, an image outside nice_tile_grid's limits, n times the
  * 1024-pixel encoder tiles of one tile >= 2^32, a launch grid that does not
- * fit.  Alpha is not stored: a 4-channel output gets NICE_DEC_ALPHA_FILL_FF or
- * 0 in byte +3, as a tiled image without an alpha batch does.  An alpha batch
- * for sets does not exist (yet).
+ * fit.  The calls of this section do not store alpha: a 4-channel output gets
+ * NICE_DEC_ALPHA_FILL_FF or 0 in byte +3, as a tiled image without an alpha
+ * batch does.  The alpha batch of a set is a second packed batch with calls of
+ * its own: "image sets: alpha" below.
  *
  * Host tables are parallel arrays: h_w, h_h (K u32), pointers and pitches (K
  * or M entries).  A window is five u32 {image, x0, y0, rw, rh}: the rectangle
@@ -438,6 +439,65 @@ int nice_decode_set_dev(nice_ctx* ctx, void* stream, const uint8_t* d_packed, ui
                         const uint32_t* h_h, uint32_t K, uint32_t tile_w, uint32_t tile_h, const uint32_t* h_win,
                         uint8_t* const* h_out, const uint64_t* h_out_pitch, uint32_t M, uint8_t out_channels,
                         uint32_t flags, int32_t* d_status /* slot_first[M] */);
+
+/* ---- image sets: alpha ----
+ * Byte +3 of the K RGBA images of a set, as a packed batch of its own over the
+ * same n global tiles: d_apacked, aoff[n + 1], alen[n], akind[n], aval[n],
+ * laid out and with the kinds and the two raw rules exactly as "tiled images:
+ * alpha" defines them.  Global tile first[i] + t equals tile t of
+ * nice_encode_tiled_alpha_dev of image i alone in kind, value, stored bytes and
+ * zero padding up to the next multiple of 16: a set of one image is that
+ * image's tiled alpha batch, and the alpha tables of any set are its images'
+ * alpha tables one after the other with the offsets rebased.  The colour batch
+ * of the set and every call above are untouched. */
+/* n * align16(max(nice_encode_bound(aw, tile_h), tile_w * tile_h)): always
+ * enough for d_apacked.  0 for a bad set. */
+uint64_t nice_set_alpha_bound(const uint32_t* h_w, const uint32_t* h_h, uint32_t K, uint32_t tile_w, uint32_t tile_h);
+/* The range pass alone: d_lo[g], d_hi[g] (n u32 each, device memory) = the
+ * smallest and the largest byte +3 of global tile g.  Images as for
+ * nice_set_split_dev with channels = 4.  One launch whatever K is; each image
+ * is read by its own alignment (16 bytes per lane, dwords or bytes).
+ * Asynchronous after the upload of the K image descriptors. */
+int nice_set_alpha_range_dev(nice_ctx* ctx, void* stream, const uint8_t* const* h_img, const uint64_t* h_pitch,
+                             const uint32_t* h_w, const uint32_t* h_h, uint32_t K, uint32_t tile_w, uint32_t tile_h,
+                             uint32_t* d_lo /* n */, uint32_t* d_hi /* n */);
+/* Encodes the alpha batch of K device-resident 4-channel images (h_pitch[i] >=
+ * 4 * h_w[i], any alignment), read in place.  The sequence is
+ * nice_encode_tiled_alpha_dev's over all n tiles at once: the set range pass,
+ * the first wait, the host verdict constant / not and the list of the m
+ * non-constant global tiles, the set gather, nice_encode_batch_dev over the m
+ * triplet images, the second wait, the tolerant verify decode, the compare,
+ * verdict and raw store, the offset scan over the n lengths, the pack.  The
+ * call waits at most twice and its number of launches does not depend on K; a
+ * set whose images are all opaque launches no encode and no decode.
+ * d_apacked, apacked_cap (nice_set_alpha_bound() always suffices), d_aoff,
+ * d_alen, d_akind, d_aval, *d_status (NICE_E_CAPACITY included) and the
+ * scratch: as for nice_encode_tiled_alpha_dev. */
+int nice_encode_set_alpha_dev(nice_ctx* ctx, void* stream, const uint8_t* const* h_img, const uint64_t* h_pitch,
+                              const uint32_t* h_w, const uint32_t* h_h, uint32_t K, uint32_t tile_w, uint32_t tile_h,
+                              uint8_t* d_apacked, uint64_t apacked_cap, uint64_t* d_aoff /* n + 1 */,
+                              uint64_t* d_alen /* n */, uint8_t* d_akind /* n */, uint8_t* d_aval /* n */,
+                              int32_t* d_status /* 1 */);
+/* Writes byte +3, and only byte +3, of the 4-byte pixels of M windows: run
+ * nice_decode_set_dev with out_channels = 4 first, on the same stream and with
+ * the same windows and outputs, then this.  h_aoff, h_alen, h_akind, h_aval:
+ * the tables of all n tiles in host memory (d_apacked may be null when
+ * apacked_bytes is 0).  Slots and their order are nice_set_select's; a tile
+ * that two windows touch is one slot in each.  d_status: slot_first[M]
+ * entries, with nice_decode_tiled_alpha_dev's host checks and codes per slot;
+ * a coded slot reports its decode status.  A slot whose status is not NICE_OK
+ * leaves its alpha bytes as the colour pass left them; the others are written.
+ * Nothing outside a window is written.  A window whose base and pitch are
+ * 16-byte aligned and whose x0 % 4 == 0 is written, where tile_w % 4 == 0, by
+ * 16-byte read-modify-writes of four pixels; every other window by bytes, in
+ * the same launch.  One upload (window descriptors and gathered tables), one
+ * batch decode over the coded slots, one status scatter, one merge launch: the
+ * number of launches depends on neither K nor M. */
+int nice_decode_set_alpha_dev(nice_ctx* ctx, void* stream, const uint8_t* d_apacked, uint64_t apacked_bytes,
+                              const uint64_t* h_aoff, const uint64_t* h_alen, const uint8_t* h_akind,
+                              const uint8_t* h_aval, const uint32_t* h_w, const uint32_t* h_h, uint32_t K,
+                              uint32_t tile_w, uint32_t tile_h, const uint32_t* h_win, uint8_t* const* h_out,
+                              const uint64_t* h_out_pitch, uint32_t M, int32_t* d_status /* slot_first[M] */);
 
 /* ---- one image sharded over ranks (config 4) ----
  * The image's raster is cut into bands of whole encoder tiles (1024 pixels in

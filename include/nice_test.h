@@ -55,6 +55,9 @@ int nice_test_last_tiled(struct nice_ctx* ctx, uint32_t* coded, uint32_t* raw);
  * window and tile the window touches) decoded as streams and expanded from raw
  * pixels, minus those refused on the host */
 int nice_test_last_set(struct nice_ctx* ctx, uint32_t* coded, uint32_t* raw);
+/* the slots of the context's last nice_decode_set_alpha_dev by kind: decoded as
+ * streams, read from raw planes, constant; minus those refused on the host */
+int nice_test_last_set_alpha(struct nice_ctx* ctx, uint32_t* coded, uint32_t* raw, uint32_t* constant);
 
 #ifdef __cplusplus
 }
