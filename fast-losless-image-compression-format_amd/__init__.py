@@ -30,7 +30,7 @@ __all__ = [
     "TiledImage", "TiledAlpha", "tiled_alpha_bound", "tile_grid", "tile_select", "tiled_bound", "encode_tiled", "decode_tiled", "save_tiled",
     "load_tiled", "DEFAULT_TILE",
     "ImageSet", "set_grid", "set_select", "set_bound", "set_alpha_bound", "encode_set", "decode_set", "save_set",
-    "load_set", "DEFAULT_SET_TILE",
+    "load_set", "DEFAULT_SET_TILE", "decode_set_tensor", "normalize_affine",
     "DEC_STRICT_REFERENCE", "DEC_ALPHA_FILL_FF", "DEC_TOLERANT_HEADER",
 ]
 
@@ -64,7 +64,10 @@ EXPORTS = [
     "nice_set_grid", "nice_set_bound", "nice_set_select", "nice_set_split_dev", "nice_set_merge_dev",
     "nice_encode_set_dev", "nice_decode_set_dev",
     "nice_set_alpha_bound", "nice_set_alpha_range_dev", "nice_encode_set_alpha_dev", "nice_decode_set_alpha_dev",
+    "nice_set_merge_tensor_dev", "nice_decode_set_tensor_dev",
 ]
+TENSOR_F32, TENSOR_F16, TENSOR_BF16 = 0, 1, 2
+TENSOR_PLANAR, TENSOR_INTERLEAVED = 0, 1
 
 
 class NiceError(RuntimeError):
@@ -160,6 +163,10 @@ def lib():
     L.nice_encode_set_alpha_dev.argtypes = [vp, vp, vp, vp, vp, vp, u32, u32, u32, u8p, u64, u8p, u8p, u8p, u8p, u8p]
     L.nice_decode_set_alpha_dev.argtypes = [vp, vp, u8p, u64, vp, vp, vp, vp, vp, vp, u32, u32, u32, vp, vp, vp, u32,
                                             u8p]
+    L.nice_set_merge_tensor_dev.argtypes = [vp, vp, u8p, u64, vp, vp, vp, vp, u32, u8, vp, vp, u32, u32, u32, vp, vp, vp,
+                                            vp, vp, u32, u32, u32, vp, vp]
+    L.nice_decode_set_tensor_dev.argtypes = [vp, vp, u8p, u64, vp, vp, vp, vp, vp, u32, u32, u32, vp, vp, vp, vp, vp, u32,
+                                             u32, u32, vp, vp, u32, u8p]
     L.nice_pipe_create.argtypes = [ctypes.c_int, u32, u32, ctypes.c_uint8, u32, u32,
                                    ctypes.POINTER(ctypes.c_void_p)]
     L.nice_pipe_destroy.argtypes = [ctypes.c_void_p]
@@ -1210,6 +1217,145 @@ def decode_set(iset: ImageSet, images=None, windows=None, out=None, out_channels
         err = NiceError(bad[0], f"{what}: {len(bad)} of {len(st) + len(ast or [])} tiles failed")
         err.statuses = st
         err.alpha_statuses = ast
+        err.out = result
+        raise err
+    return result
+
+
+def _f32(v) -> float:
+    """``v`` rounded to float32 (to nearest even), as a Python float."""
+    return ctypes.c_float(float(v)).value
+
+
+def normalize_affine(mean, std):
+    """``(scale, bias)`` for ``decode_set_tensor`` such that an element is
+    ``(x / 255 - mean[c]) / std[c]``: ``scale[c] = 1 / (255 * std[c])`` and
+    ``bias[c] = -mean[c] / std[c]``, each computed in double and rounded once to
+    float32; returned as two triples of Python floats that float32 holds
+    exactly.  These float32 constants, not the doubles, define the result:
+    an element is ``fmaf(byte, scale[c], bias[c])`` in float32, which may
+    differ in the last place from the double expression rounded once."""
+    mean, std = [float(v) for v in mean], [float(v) for v in std]
+    if len(mean) != 3 or len(std) != 3:
+        raise NiceError(E_ARG, "normalize_affine: mean and std have three entries each")
+    return (tuple(_f32(1.0 / (255.0 * s)) for s in std), tuple(_f32(-m / s) for m, s in zip(mean, std)))
+
+
+def _tensor_pitches(t, layout):
+    """(row pitch, plane pitch), in elements, of a [3, rh, rw] output read as
+    ``layout``, or None where its strides are not that layout's.  (A stride
+    over an axis of one element says nothing.)"""
+    _, rh, rw = t.shape
+    s0, s1, s2 = t.stride()
+    if layout == TENSOR_PLANAR:
+        return ((s1 if rh > 1 else rw), s0) if rw == 1 or s2 == 1 else None
+    return ((s1 if rh > 1 else 3 * rw), 0) if s0 == 1 and (rw == 1 or s2 == 3) else None
+
+
+def decode_set_tensor(iset: ImageSet, images=None, windows=None, out=None, dtype=None,
+                      scale=(1 / 255,) * 3, bias=(0.,) * 3, flip=None, channels_last: bool = False,
+                      flags: int = DEC_ALPHA_FILL_FF, stream=None, ctx: "_Ctx | None" = None):
+    """``decode_set`` straight into what a model reads: a list of cuda tensors
+    [3, h, w] of ``dtype`` (torch.float16, the default, torch.bfloat16 or
+    torch.float32), one per image or window (``images`` / ``windows`` as for
+    ``decode_set``).  Element (c, y, x) is ``fmaf(b, scale[c], bias[c])`` in
+    float32, b being byte +c of the decoded pixel, stored as float32 or rounded
+    to nearest even to ``dtype``; ``scale`` and ``bias`` (three numbers each,
+    ``normalize_affine`` gives those of a mean and a std) are rounded to
+    float32 once, here, and passed on as they are.  The output has three
+    channels, always: a 4-channel set decodes its colour, ``iset.alpha`` is not
+    read.  ``flip``: M truthy or falsy values, or None; a truthy one mirrors
+    its window (output column x takes window column w - 1 - x).
+    ``out``: a list of [3, h, w] tensors to decode into, whose rows and planes
+    may be strided while the innermost stride is fixed by the layout, or, where
+    all windows share one size, one tensor [M, 3, rh, rw] (``out`` itself is
+    returned).  The strides decide the layout, one per call: ``stride(3) == 1``
+    is planar (NCHW), ``stride(1) == 1 and stride(3) == 3`` interleaved (a
+    ``channels_last`` tensor); anything else is NiceError(E_ARG).  The outputs
+    must not overlap.  ``channels_last=True`` only chooses the memory format of
+    the tensors the function allocates.  The conversion happens in the merge
+    kernel: no uint8 image and no float32 temporary exist.  Errors, the
+    untouched elements of a failed tile, ``.statuses`` and ``.out`` and the wait
+    are ``decode_set``'s."""
+    import torch
+    dtype = torch.float16 if dtype is None else dtype
+    dt = {torch.float32: TENSOR_F32, torch.float16: TENSOR_F16, torch.bfloat16: TENSOR_BF16}.get(dtype)
+    if dt is None:
+        raise NiceError(E_ARG, "decode_set_tensor: dtype must be torch.float32, torch.float16 or torch.bfloat16")
+    if images is not None and windows is not None:
+        raise NiceError(E_ARG, "decode_set_tensor: images or windows, not both")
+    k = len(iset.widths)
+    tw, th = iset.tile_w, iset.tile_h
+    if windows is None:
+        idx = range(k) if images is None else [int(i) for i in images]
+        if any(i < 0 or i >= k for i in idx):
+            raise NiceError(E_ARG, "decode_set_tensor: image index outside the set")
+        windows = [(i, 0, 0, iset.widths[i], iset.heights[i]) for i in idx]
+    windows = [tuple(int(v) for v in wdw) for wdw in windows]
+    m = len(windows)
+    slot_first = set_select(iset.widths, iset.heights, tw, th, windows)
+    n = set_grid(iset.widths, iset.heights, tw, th)[-1]
+    packed = iset.packed
+    if not packed.is_cuda:
+        raise NiceError(E_ARG, "decode_set_tensor: iset.packed must be on the GPU (load_set(path, device=...))")
+    off = iset.off.to("cpu", torch.int64).contiguous()
+    lens = iset.stream_len.to("cpu", torch.int64).contiguous()
+    kind = iset.kind.to("cpu", torch.uint8).contiguous()
+    if off.numel() < n + 1 or lens.numel() != n or kind.numel() != n or int(off[n]) > packed.numel():
+        raise NiceError(E_ARG, "decode_set_tensor: tables do not match the set")
+    scale, bias = [_f32(v) for v in scale], [_f32(v) for v in bias]
+    if len(scale) != 3 or len(bias) != 3:
+        raise NiceError(E_ARG, "decode_set_tensor: scale and bias have three entries each")
+    flips = [0] * m if flip is None else [1 if f else 0 for f in flip]
+    if len(flips) != m:
+        raise NiceError(E_ARG, "decode_set_tensor: flip must have one entry per window")
+    dev = packed.device
+    result = out
+    shape_msg = "decode_set_tensor: out must be [M, 3, rh, rw] or a list of M tensors [3, rh, rw] of their windows"
+    if out is None:
+        if channels_last:
+            outs = [torch.empty((wdw[4], wdw[3], 3), dtype=dtype, device=dev).permute(2, 0, 1) for wdw in windows]
+        else:
+            outs = [torch.empty((3, wdw[4], wdw[3]), dtype=dtype, device=dev) for wdw in windows]
+        result = outs
+    elif hasattr(out, "dim"):
+        if out.dim() != 4 or out.shape[0] != m:
+            raise NiceError(E_ARG, shape_msg)
+        outs = [out[j] for j in range(m)]
+    else:
+        outs = list(out)
+        if len(outs) != m:
+            raise NiceError(E_ARG, shape_msg)
+    for wdw, o in zip(windows, outs):
+        if not hasattr(o, "dim") or o.dim() != 3 or tuple(o.shape) != (3, wdw[4], wdw[3]):
+            raise NiceError(E_ARG, shape_msg)
+        if o.dtype != dtype or not o.is_cuda or o.device != dev:
+            raise NiceError(E_ARG, "decode_set_tensor: out must have the dtype asked for, on the set's device")
+    # one layout per call: the first that every output's strides fit
+    for layout in (TENSOR_PLANAR, TENSOR_INTERLEAVED):
+        pitches = [_tensor_pitches(o, layout) for o in outs]
+        if all(v is not None for v in pitches):
+            break
+    else:
+        raise NiceError(E_ARG, "decode_set_tensor: the outputs' strides must all be planar (innermost 1) or all "
+                               "interleaved (channel stride 1, innermost 3)")
+    status = torch.full((slot_first[m],), 99, dtype=torch.int32, device=dev)
+    rc = lib().nice_decode_set_tensor_dev(
+        (ctx or _ctx(dev.index or 0)).ptr, _stream_of(torch, stream, dev), ctypes.c_void_p(packed.data_ptr()),
+        int(off[n]), ctypes.c_void_p(off.data_ptr()), ctypes.c_void_p(lens.data_ptr()),
+        ctypes.c_void_p(kind.data_ptr()), _u32_array(iset.widths), _u32_array(iset.heights), k, tw, th,
+        _win_array(windows), (ctypes.c_uint8 * m)(*flips), (ctypes.c_void_p * m)(*[o.data_ptr() for o in outs]),
+        (ctypes.c_uint64 * m)(*[v[0] for v in pitches]), (ctypes.c_uint64 * m)(*[v[1] for v in pitches]), m,
+        dt, layout, (ctypes.c_float * 3)(*scale), (ctypes.c_float * 3)(*bias), flags,
+        ctypes.c_void_p(status.data_ptr()))
+    _check(rc, "nice_decode_set_tensor_dev")
+    if stream is not None:
+        stream.synchronize()
+    st = status.cpu().tolist()
+    bad = [s for s in st if s != OK]
+    if bad:
+        err = NiceError(bad[0], f"nice_decode_set_tensor_dev: {len(bad)} of {len(st)} tiles failed")
+        err.statuses = st
         err.out = result
         raise err
     return result

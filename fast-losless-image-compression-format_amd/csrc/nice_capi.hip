@@ -7,6 +7,7 @@
 #include <string.h>
 
 #include <atomic>
+#include <cmath>
 #include <mutex>
 #include <algorithm>
 #include <vector>
@@ -1480,23 +1481,31 @@ int nice_encode_set_dev(nice_ctx* ctx, void* stream, const uint8_t* const* h_img
   return nice::pack_streams_launch(stream, ctx->cus, slots, slot, d_len, n, d_packed, packed_cap, d_off, d_status);
 }
 
-int nice_decode_set_dev(nice_ctx* ctx, void* stream, const uint8_t* d_packed, uint64_t packed_bytes,
-                        const uint64_t* h_off, const uint64_t* h_len, const uint8_t* h_kind, const uint32_t* h_w,
-                        const uint32_t* h_h, uint32_t K, uint32_t tile_w, uint32_t tile_h, const uint32_t* h_win,
-                        uint8_t* const* h_out, const uint64_t* h_out_pitch, uint32_t M, uint8_t out_channels,
-                        uint32_t flags, int32_t* d_status) {
-  if (!ctx || !d_packed || !h_off || !h_len || !h_kind || !d_status) return NICE_E_ARG;
-  if (out_channels != 3 && out_channels != 4) return NICE_E_ARG;
-  if ((flags & NICE_DEC_STRICT_REFERENCE) || ((uintptr_t)d_packed & 15)) return NICE_E_ARG;
-  std::vector<uint32_t> first((size_t)K + 1), slot_first((size_t)M + 1);
-  int rc = nice_set_select(h_w, h_h, K, tile_w, tile_h, h_win, M, slot_first.data());
-  if (rc) return rc;
-  (void)nice_set_grid(h_w, h_h, K, tile_w, tile_h, first.data());
-  std::vector<SetWindow> wins;
-  if ((rc = set_window_table(h_w, h_h, K, tile_w, tile_h, h_win, h_out, h_out_pitch, M, out_channels, wins))) return rc;
-  NICE_HIP(hipSetDevice(ctx->device));
+namespace {
+// The slots of a set decode on the device: the decoded coded slots with their
+// tables and statuses, the tables of the raw slots, the window descriptors.
+struct SetSlots {
+  uint32_t nc = 0, nr = 0;
+  const uint8_t* d_wins = nullptr;
+  const uint8_t* dec = nullptr;    // coded slot i decoded at dec + i * stride
+  uint64_t stride = 0;
+  const int32_t* d_cst = nullptr;
+  const uint32_t *d_cwin = nullptr, *d_cidx = nullptr, *d_rwin = nullptr, *d_ridx = nullptr;
+  const uint64_t* d_roff = nullptr;
+};
+
+// What nice_decode_set_dev and nice_decode_set_tensor_dev share, up to their
+// merges: the m slots of the M windows by kind (checked: set and windows, by
+// the caller), one upload of the window descriptors (`wins`, wins_bytes, a
+// multiple of 8) and the gathered tables, the initial statuses, the batch
+// decode of the coded slots at dec_channels bytes per pixel and the scatter of
+// its statuses into d_status.
+int set_decode_slots(nice_ctx* ctx, void* stream, const uint8_t* d_packed, uint64_t packed_bytes, const uint64_t* h_off,
+                     const uint64_t* h_len, const uint8_t* h_kind, const uint32_t* h_w, uint32_t tile_w, uint32_t tile_h,
+                     const uint32_t* h_win, uint32_t M, const uint32_t* first, uint32_t m, const void* wins,
+                     size_t wins_bytes, uint32_t dec_channels, uint32_t flags, int32_t* d_status, SetSlots& s) {
+  int rc;
   hipStream_t st = (hipStream_t)stream;
-  const uint32_t m = slot_first[M];
   const uint64_t npx = (uint64_t)tile_w * tile_h;
   // every (window, tile) pair is a slot; the slots by kind.  A slot refused
   // here keeps its status and is not touched.
@@ -1506,7 +1515,7 @@ int nice_decode_set_dev(nice_ctx* ctx, void* stream, const uint8_t* d_packed, ui
   uint32_t p = 0;
   for (uint32_t j = 0; j < M; ++j) {
     const uint32_t* q = h_win + 5ull * j;
-    const uint32_t nx = wins[j].nx;
+    const uint32_t nx = (h_w[q[0]] + tile_w - 1) / tile_w;
     const uint32_t tx0 = q[1] / tile_w, ty0 = q[2] / tile_h;
     const uint32_t tx1 = (q[1] + q[3] - 1) / tile_w + 1, ty1 = (q[2] + q[4] - 1) / tile_h + 1;
     for (uint32_t ty = ty0; ty < ty1; ++ty) {
@@ -1538,12 +1547,12 @@ int nice_decode_set_dev(nice_ctx* ctx, void* stream, const uint8_t* d_packed, ui
   // one upload: the window descriptors, u64 {coded offsets, coded lengths, raw
   // offsets}, u32 {coded tile indices, windows, positions, raw tile indices,
   // windows}; then the coded statuses
-  const size_t o_win = 0, o_coff = o_win + M * sizeof(SetWindow), o_clen = o_coff + 8ull * nc,
+  const size_t o_win = 0, o_coff = o_win + wins_bytes, o_clen = o_coff + 8ull * nc,
                o_roff = o_clen + 8ull * nc, o_cidx = o_roff + 8ull * nr, o_cwin = o_cidx + 4ull * nc,
                o_cpos = o_cwin + 4ull * nc, o_ridx = o_cpos + 4ull * nc, o_rwin = o_ridx + 4ull * nr,
                o_cst = align_up(o_rwin + 4ull * nr, 16), tab_bytes = o_cst + 4ull * nc;
   std::vector<uint8_t> tab(o_cst);
-  memcpy(&tab[o_win], wins.data(), M * sizeof(SetWindow));
+  memcpy(&tab[o_win], wins, wins_bytes);
   if (nc) {
     memcpy(&tab[o_coff], c_off.data(), 8ull * nc);
     memcpy(&tab[o_clen], c_len.data(), 8ull * nc);
@@ -1556,32 +1565,173 @@ int nice_decode_set_dev(nice_ctx* ctx, void* stream, const uint8_t* d_packed, ui
     memcpy(&tab[o_ridx], r_idx.data(), 4ull * nr);
     memcpy(&tab[o_rwin], r_win.data(), 4ull * nr);
   }
-  const uint64_t stride = align_up((size_t)npx * out_channels, 16);
+  const uint64_t stride = align_up((size_t)npx * dec_channels, 16);
   if ((rc = ctx->tile_tab.grow(tab_bytes))) return rc;
   if (nc && (rc = ctx->tile_dec.grow((size_t)nc * stride))) return rc;
   uint8_t* dt = (uint8_t*)ctx->tile_tab.ptr;
   NICE_HIP(hipMemcpyAsync(dt, tab.data(), o_cst, hipMemcpyHostToDevice, st));
   NICE_HIP(hipMemcpyAsync(d_status, init.data(), 4ull * m, hipMemcpyHostToDevice, st));
-  const SetWindow* d_wins = (const SetWindow*)(dt + o_win);
+  s.nc = nc;
+  s.nr = nr;
+  s.d_wins = dt + o_win;
+  s.dec = (const uint8_t*)ctx->tile_dec.ptr;
+  s.stride = stride;
+  s.d_cst = (const int32_t*)(dt + o_cst);
+  s.d_cwin = (const uint32_t*)(dt + o_cwin);
+  s.d_cidx = (const uint32_t*)(dt + o_cidx);
+  s.d_rwin = (const uint32_t*)(dt + o_rwin);
+  s.d_ridx = (const uint32_t*)(dt + o_ridx);
+  s.d_roff = (const uint64_t*)(dt + o_roff);
   if (nc) {
     uint8_t* dec = (uint8_t*)ctx->tile_dec.ptr;
     int32_t* cst = (int32_t*)(dt + o_cst);
     const uint32_t f = (flags & NICE_DEC_ALPHA_FILL_FF) | NICE_DEC_TOLERANT_HEADER;
     if ((rc = nice::decode_batch_impl(ctx, stream, d_packed, 0, (const uint64_t*)(dt + o_clen), c_len.data(), nc, tile_w,
-                                      tile_h, out_channels, dec, stride, f, cst, (const uint64_t*)(dt + o_coff),
+                                      tile_h, (uint8_t)dec_channels, dec, stride, f, cst, (const uint64_t*)(dt + o_coff),
                                       packed_bytes)))
       return rc;
     if ((rc = nice::tiles_scatter_status_launch(stream, cst, (const uint32_t*)(dt + o_cpos), nc, d_status))) return rc;
-    if ((rc = nice::set_merge_launch(stream, dec, stride, nullptr, (const uint32_t*)(dt + o_cwin),
-                                     (const uint32_t*)(dt + o_cidx), cst, nc, d_wins, M, tile_w, tile_h, out_channels,
-                                     out_channels, 0)))
+  }
+  return NICE_OK;
+}
+}  // namespace
+
+int nice_decode_set_dev(nice_ctx* ctx, void* stream, const uint8_t* d_packed, uint64_t packed_bytes,
+                        const uint64_t* h_off, const uint64_t* h_len, const uint8_t* h_kind, const uint32_t* h_w,
+                        const uint32_t* h_h, uint32_t K, uint32_t tile_w, uint32_t tile_h, const uint32_t* h_win,
+                        uint8_t* const* h_out, const uint64_t* h_out_pitch, uint32_t M, uint8_t out_channels,
+                        uint32_t flags, int32_t* d_status) {
+  if (!ctx || !d_packed || !h_off || !h_len || !h_kind || !d_status) return NICE_E_ARG;
+  if (out_channels != 3 && out_channels != 4) return NICE_E_ARG;
+  if ((flags & NICE_DEC_STRICT_REFERENCE) || ((uintptr_t)d_packed & 15)) return NICE_E_ARG;
+  std::vector<uint32_t> first((size_t)K + 1), slot_first((size_t)M + 1);
+  int rc = nice_set_select(h_w, h_h, K, tile_w, tile_h, h_win, M, slot_first.data());
+  if (rc) return rc;
+  (void)nice_set_grid(h_w, h_h, K, tile_w, tile_h, first.data());
+  std::vector<SetWindow> wins;
+  if ((rc = set_window_table(h_w, h_h, K, tile_w, tile_h, h_win, h_out, h_out_pitch, M, out_channels, wins))) return rc;
+  NICE_HIP(hipSetDevice(ctx->device));
+  SetSlots s;
+  if ((rc = set_decode_slots(ctx, stream, d_packed, packed_bytes, h_off, h_len, h_kind, h_w, tile_w, tile_h, h_win, M,
+                             first.data(), slot_first[M], wins.data(), M * sizeof(SetWindow), out_channels, flags,
+                             d_status, s)))
+    return rc;
+  const SetWindow* d_wins = (const SetWindow*)s.d_wins;
+  if (s.nc) {
+    if ((rc = nice::set_merge_launch(stream, s.dec, s.stride, nullptr, s.d_cwin, s.d_cidx, s.d_cst, s.nc, d_wins, M,
+                                     tile_w, tile_h, out_channels, out_channels, 0)))
       return rc;
   }
-  if (nr) {
+  if (s.nr) {
     const uint32_t fill = (flags & NICE_DEC_ALPHA_FILL_FF) ? 255u : 0u;
-    if ((rc = nice::set_merge_launch(stream, d_packed, 0, (const uint64_t*)(dt + o_roff),
-                                     (const uint32_t*)(dt + o_rwin), (const uint32_t*)(dt + o_ridx), nullptr, nr, d_wins,
-                                     M, tile_w, tile_h, 3, out_channels, fill)))
+    if ((rc = nice::set_merge_launch(stream, d_packed, 0, s.d_roff, s.d_rwin, s.d_ridx, nullptr, s.nr, d_wins, M, tile_w,
+                                     tile_h, 3, out_channels, fill)))
+      return rc;
+  }
+  return NICE_OK;
+}
+
+namespace {
+// The tensor windows of M windows (checked as set_window_table checks its own;
+// NICE_E_ARG also for a base not aligned to the element or a row pitch below the window).
+int set_tensor_window_table(const uint32_t* h_w, const uint32_t* h_h, uint32_t tile_w, uint32_t tile_h,
+                            const uint32_t* h_win, const uint8_t* h_flip, void* const* h_out,
+                            const uint64_t* h_row_pitch, const uint64_t* h_plane_pitch, uint32_t M, uint32_t dtype,
+                            uint32_t layout, std::vector<SetTensorWindow>& tab) {
+  const uint32_t es = nice::set_tensor_elem_bytes(dtype);
+  const bool planar = layout == NICE_TENSOR_PLANAR;
+  if (!h_out || !h_row_pitch || (planar && !h_plane_pitch)) return NICE_E_ARG;
+  tab.resize(M);
+  for (uint32_t j = 0; j < M; ++j) {
+    const uint32_t* q = h_win + 5ull * j;
+    const uint32_t w = h_w[q[0]], h = h_h[q[0]];
+    if (!h_out[j] || ((uintptr_t)h_out[j] & (es - 1))) return NICE_E_ARG;
+    if (h_row_pitch[j] < (uint64_t)q[3] * (planar ? 1u : 3u)) return NICE_E_ARG;
+    const uint32_t nx = (w + tile_w - 1) / tile_w, ny = (h + tile_h - 1) / tile_h;
+    const uint64_t pp = planar ? h_plane_pitch[j] : 0;
+    const bool flip = h_flip && h_flip[j];
+    tab[j] = SetTensorWindow{h_out[j], h_row_pitch[j], pp, q[1], q[2], q[3], q[4], w, h, nx, nx * ny,
+                             nice::set_tensor_window_mode(h_out[j], h_row_pitch[j], pp, q[1], q[3], flip, dtype, layout),
+                             flip ? 1u : 0u};
+  }
+  return NICE_OK;
+}
+
+// dtype, layout and the affine constants of a tensor call
+int set_tensor_check(uint32_t dtype, uint32_t layout, const float* scale, const float* bias) {
+  if (!nice::set_tensor_elem_bytes(dtype)) return NICE_E_ARG;
+  if (layout != NICE_TENSOR_PLANAR && layout != NICE_TENSOR_INTERLEAVED) return NICE_E_ARG;
+  if (!scale || !bias) return NICE_E_ARG;
+  for (int c = 0; c < 3; ++c)
+    if (!std::isfinite(scale[c]) || !std::isfinite(bias[c])) return NICE_E_ARG;
+  return NICE_OK;
+}
+}  // namespace
+
+int nice_set_merge_tensor_dev(nice_ctx* ctx, void* stream, const uint8_t* d_tiles, uint64_t tile_stride,
+                              const uint64_t* d_src_off, const uint32_t* d_slot_win, const uint32_t* d_slot_tile,
+                              const int32_t* d_slot_status, uint32_t n_slots, uint8_t tile_channels, const uint32_t* h_w,
+                              const uint32_t* h_h, uint32_t K, uint32_t tile_w, uint32_t tile_h, const uint32_t* h_win,
+                              const uint8_t* h_flip, void* const* h_out, const uint64_t* h_row_pitch,
+                              const uint64_t* h_plane_pitch, uint32_t M, uint32_t dtype, uint32_t layout,
+                              const float* scale, const float* bias) {
+  if (!ctx) return NICE_E_ARG;
+  if (tile_channels != 3 && tile_channels != 4) return NICE_E_ARG;
+  if (d_src_off && tile_channels != 3) return NICE_E_ARG;   // (raw tiles in a packed buffer hold 3 bytes per pixel)
+  int rc = set_tensor_check(dtype, layout, scale, bias);
+  if (rc) return rc;
+  std::vector<uint32_t> slot_first((size_t)M + 1);
+  if ((rc = nice_set_select(h_w, h_h, K, tile_w, tile_h, h_win, M, slot_first.data()))) return rc;
+  std::vector<SetTensorWindow> tab;
+  if ((rc = set_tensor_window_table(h_w, h_h, tile_w, tile_h, h_win, h_flip, h_out, h_row_pitch, h_plane_pitch, M, dtype,
+                                    layout, tab)))
+    return rc;
+  if (n_slots == 0) return NICE_OK;
+  if (!d_tiles || !d_slot_win || !d_slot_tile) return NICE_E_ARG;
+  if (!d_src_off && tile_stride < (uint64_t)tile_w * tile_h * tile_channels) return NICE_E_ARG;
+  NICE_HIP(hipSetDevice(ctx->device));
+  if ((rc = ctx->tile_tab.grow(M * sizeof(SetTensorWindow)))) return rc;
+  NICE_HIP(hipMemcpyAsync(ctx->tile_tab.ptr, tab.data(), M * sizeof(SetTensorWindow), hipMemcpyHostToDevice,
+                          (hipStream_t)stream));
+  return nice::set_merge_tensor_launch(stream, d_tiles, tile_stride, d_src_off, d_slot_win, d_slot_tile, d_slot_status,
+                                       n_slots, (const SetTensorWindow*)ctx->tile_tab.ptr, M, tile_w, tile_h,
+                                       tile_channels, dtype, layout, scale, bias);
+}
+
+int nice_decode_set_tensor_dev(nice_ctx* ctx, void* stream, const uint8_t* d_packed, uint64_t packed_bytes,
+                               const uint64_t* h_off, const uint64_t* h_len, const uint8_t* h_kind,
+                               const uint32_t* h_w, const uint32_t* h_h, uint32_t K, uint32_t tile_w, uint32_t tile_h,
+                               const uint32_t* h_win, const uint8_t* h_flip, void* const* h_out,
+                               const uint64_t* h_row_pitch, const uint64_t* h_plane_pitch, uint32_t M, uint32_t dtype,
+                               uint32_t layout, const float* scale, const float* bias, uint32_t flags,
+                               int32_t* d_status) {
+  if (!ctx || !d_packed || !h_off || !h_len || !h_kind || !d_status) return NICE_E_ARG;
+  if ((flags & NICE_DEC_STRICT_REFERENCE) || ((uintptr_t)d_packed & 15)) return NICE_E_ARG;
+  int rc = set_tensor_check(dtype, layout, scale, bias);
+  if (rc) return rc;
+  std::vector<uint32_t> first((size_t)K + 1), slot_first((size_t)M + 1);
+  if ((rc = nice_set_select(h_w, h_h, K, tile_w, tile_h, h_win, M, slot_first.data()))) return rc;
+  (void)nice_set_grid(h_w, h_h, K, tile_w, tile_h, first.data());
+  std::vector<SetTensorWindow> wins;
+  if ((rc = set_tensor_window_table(h_w, h_h, tile_w, tile_h, h_win, h_flip, h_out, h_row_pitch, h_plane_pitch, M, dtype,
+                                    layout, wins)))
+    return rc;
+  NICE_HIP(hipSetDevice(ctx->device));
+  // the coded slots at 4 bytes per pixel, whatever the set's channels: a lane loads dwords
+  SetSlots s;
+  if ((rc = set_decode_slots(ctx, stream, d_packed, packed_bytes, h_off, h_len, h_kind, h_w, tile_w, tile_h, h_win, M,
+                             first.data(), slot_first[M], wins.data(), M * sizeof(SetTensorWindow), 4, flags, d_status,
+                             s)))
+    return rc;
+  const SetTensorWindow* d_wins = (const SetTensorWindow*)s.d_wins;
+  if (s.nc) {
+    if ((rc = nice::set_merge_tensor_launch(stream, s.dec, s.stride, nullptr, s.d_cwin, s.d_cidx, s.d_cst, s.nc, d_wins,
+                                            M, tile_w, tile_h, 4, dtype, layout, scale, bias)))
+      return rc;
+  }
+  if (s.nr) {
+    if ((rc = nice::set_merge_tensor_launch(stream, d_packed, 0, s.d_roff, s.d_rwin, s.d_ridx, nullptr, s.nr, d_wins, M,
+                                            tile_w, tile_h, 3, dtype, layout, scale, bias)))
       return rc;
   }
   return NICE_OK;

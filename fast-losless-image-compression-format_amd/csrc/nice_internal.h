@@ -116,6 +116,30 @@ int set_merge_launch(void* stream, const uint8_t* d_tiles, uint64_t tile_stride,
                      uint32_t n_slots, const SetWindow* d_wins, uint32_t n_wins, uint32_t tile_w, uint32_t tile_h,
                      uint32_t tile_channels, uint32_t out_channels, uint32_t fill);
 
+// ---- image sets: tensor output (nice_sets_tensor.hip) --------------------------
+// A window of the tensor merge: element (c, y, x) at out + c * plane_pitch +
+// y * row_pitch + x (planar) or out + y * row_pitch + 3 * x + c (interleaved),
+// pitches in elements.  mode: log2 of the pixels a lane converts and stores as
+// one vector per plane (0: element by element), the best the window's base,
+// pitches, element size and x0 (flipped: x0 + rw) allow.
+struct SetTensorWindow {
+  void* out;
+  uint64_t row_pitch, plane_pitch;
+  uint32_t x0, y0, rw, rh;      // the rectangle, inside its image
+  uint32_t w, h, nx, n_tiles;   // of that image
+  uint32_t mode, flip;
+};
+uint32_t set_tensor_elem_bytes(uint32_t dtype);   // 0: unknown dtype
+uint32_t set_tensor_window_mode(const void* d_out, uint64_t row_pitch, uint64_t plane_pitch, uint32_t x0, uint32_t rw,
+                                bool flip, uint32_t dtype, uint32_t layout);
+// set_merge_launch's slots and skips; every window element takes
+// fmaf(byte, scale[c], bias[c]) of its pixel's bytes +0..+2, converted to dtype.
+int set_merge_tensor_launch(void* stream, const uint8_t* d_tiles, uint64_t tile_stride, const uint64_t* d_src_off,
+                            const uint32_t* d_slot_win, const uint32_t* d_slot_tile, const int32_t* d_slot_status,
+                            uint32_t n_slots, const SetTensorWindow* d_wins, uint32_t n_wins, uint32_t tile_w,
+                            uint32_t tile_h, uint32_t tile_channels, uint32_t dtype, uint32_t layout, const float* scale,
+                            const float* bias);
+
 // ---- the alpha batch of an image set (nice_sets.hip) --------------------------
 // The set forms of alpha_range_launch, alpha_gather_launch and alpha_merge_launch
 // above: tiles are global tile indices, their images (RGBA) come from d_imgs.

@@ -499,6 +499,73 @@ int nice_decode_set_alpha_dev(nice_ctx* ctx, void* stream, const uint8_t* d_apac
                               uint32_t tile_w, uint32_t tile_h, const uint32_t* h_win, uint8_t* const* h_out,
                               const uint64_t* h_out_pitch, uint32_t M, int32_t* d_status /* slot_first[M] */);
 
+/* ---- image sets: tensor output ----
+ * The windows of a set decoded straight into what a model reads: three
+ * channels of float32, float16 or bfloat16, scaled and shifted per channel,
+ * planar (NCHW) or interleaved (NHWC), each window optionally mirrored.  The
+ * set merge converts as it stores; there is no uint8 intermediate.
+ *
+ * The value: for output channel c in {0, 1, 2} (bytes +0..+2 of the decoded
+ * pixel) and byte value b,
+ *   v = fmaf((float)b, scale[c], bias[c])       binary32, one rounding
+ * NICE_TENSOR_F32 stores v; NICE_TENSOR_F16 and NICE_TENSOR_BF16 store v
+ * converted round-to-nearest-even.  The result does not depend on the store
+ * width, the layout, the flip or the kind of a tile.
+ *
+ * The output has three channels, always: a 4-channel set decodes its colour.
+ * This path emits colour only; the alpha batch of a set ("image sets: alpha")
+ * is neither read nor written by it.
+ *
+ * Window j is rw x rh elements per channel at h_out[j] (device memory, aligned
+ * to the element size), pitches counted in elements:
+ *   NICE_TENSOR_PLANAR       (c, y, x) at h_out[j] + c * h_plane_pitch[j] + y * h_row_pitch[j] + x
+ *                            (h_row_pitch[j] >= rw)
+ *   NICE_TENSOR_INTERLEAVED  (c, y, x) at h_out[j] + y * h_row_pitch[j] + 3 * x + c
+ *                            (h_row_pitch[j] >= 3 * rw; h_plane_pitch is not read)
+ * h_flip (M bytes, or null: none): h_flip[j] != 0 mirrors window j, output
+ * column x takes image column x0 + rw - 1 - x.  The windows' outputs must not
+ * overlap; nothing outside a window's elements is written, and no padding.
+ * NICE_E_ARG besides the errors of the uint8 calls: an unknown dtype or
+ * layout, a base pointer not aligned to the element size, a row pitch below
+ * the window, scale or bias null or not finite. */
+#define NICE_TENSOR_F32  0u
+#define NICE_TENSOR_F16  1u
+#define NICE_TENSOR_BF16 2u
+#define NICE_TENSOR_PLANAR      0u
+#define NICE_TENSOR_INTERLEAVED 1u
+/* The kernel alone, as nice_set_merge_dev is for the uint8 merge: the same
+ * slots (d_tiles, tile_stride, d_src_off, the slot tables, tile_channels 3 or
+ * 4; byte +3 of a 4-byte slot pixel is ignored), the same skips, one launch
+ * whatever M is.  Dense 4-byte slots at 4-byte alignment are read as dwords;
+ * a lane converts 1, 2, 4 or 8 consecutive pixels and stores them per plane as
+ * one store of up to 16 bytes, as far as the window's base, its pitches, x0
+ * (mirrored: x0 + rw) and the slots' alignment and tile_w allow; every other
+ * window goes element by element, in the same launch.  Asynchronous after the
+ * upload of the M window descriptors. */
+int nice_set_merge_tensor_dev(nice_ctx* ctx, void* stream, const uint8_t* d_tiles, uint64_t tile_stride,
+                              const uint64_t* d_src_off, const uint32_t* d_slot_win, const uint32_t* d_slot_tile,
+                              const int32_t* d_slot_status, uint32_t n_slots, uint8_t tile_channels /* 3 or 4 */,
+                              const uint32_t* h_w, const uint32_t* h_h, uint32_t K, uint32_t tile_w, uint32_t tile_h,
+                              const uint32_t* h_win, const uint8_t* h_flip /* M, or null */, void* const* h_out,
+                              const uint64_t* h_row_pitch, const uint64_t* h_plane_pitch /* planar only */, uint32_t M,
+                              uint32_t dtype, uint32_t layout, const float* scale /* 3 */, const float* bias /* 3 */);
+/* nice_decode_set_dev with the tensor merge in place of both merges: the same
+ * tables, slots, per-slot statuses and their order, host-side checks of raw
+ * slots and errors.  The coded slots are decoded at 4 bytes per pixel whatever
+ * the set's channel count; raw slots are read in place, 3 bytes per pixel.  One
+ * upload, one batch decode over the coded slots, one status scatter, one
+ * tensor merge of the coded and one of the raw slots: the number of launches
+ * depends on neither K nor M.  A slot whose status is not NICE_OK leaves its
+ * elements untouched.  NICE_DEC_ALPHA_FILL_FF is accepted and irrelevant;
+ * NICE_DEC_STRICT_REFERENCE is NICE_E_ARG. */
+int nice_decode_set_tensor_dev(nice_ctx* ctx, void* stream, const uint8_t* d_packed, uint64_t packed_bytes,
+                               const uint64_t* h_off, const uint64_t* h_len, const uint8_t* h_kind,
+                               const uint32_t* h_w, const uint32_t* h_h, uint32_t K, uint32_t tile_w, uint32_t tile_h,
+                               const uint32_t* h_win, const uint8_t* h_flip, void* const* h_out,
+                               const uint64_t* h_row_pitch, const uint64_t* h_plane_pitch, uint32_t M,
+                               uint32_t dtype, uint32_t layout, const float* scale, const float* bias,
+                               uint32_t flags, int32_t* d_status /* slot_first[M] */);
+
 /* ---- one image sharded over ranks (config 4) ----
  * The image's raster is cut into bands of whole encoder tiles (1024 pixels in
  * raster order); rank r encodes tiles [tile_lo, tile_hi).  The caller runs the

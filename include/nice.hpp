@@ -123,5 +123,49 @@ inline void decode_packed(const Context& ctx, void* stream, const uint8_t* d_pac
         "nice_decode_packed_dev");
 }
 
+// ---- image sets: tensor output (nice.h, "image sets: tensor output") ----
+enum class TensorType : uint32_t { F32 = NICE_TENSOR_F32, F16 = NICE_TENSOR_F16, BF16 = NICE_TENSOR_BF16 };
+enum class TensorLayout : uint32_t { Planar = NICE_TENSOR_PLANAR, Interleaved = NICE_TENSOR_INTERLEAVED };
+
+// An encoded set: the packed tiles in device memory, every table on the host.
+struct SetTables {
+  const uint8_t* d_packed = nullptr;   // 16-byte aligned
+  uint64_t packed_bytes = 0;
+  const uint64_t* off = nullptr;       // n + 1
+  const uint64_t* len = nullptr;       // n
+  const uint8_t* kind = nullptr;       // n
+  const uint32_t* w = nullptr;         // K
+  const uint32_t* h = nullptr;         // K
+  uint32_t K = 0, tile_w = 0, tile_h = 0;
+};
+
+// M windows {image, x0, y0, rw, rh} and where each goes: base pointers (device
+// memory), pitches in elements, flip (null: none) as nice.h defines them.
+struct TensorWindows {
+  const uint32_t* win = nullptr;       // 5 * M
+  const uint8_t* flip = nullptr;       // M, or null
+  void* const* out = nullptr;          // M
+  const uint64_t* row_pitch = nullptr;     // M
+  const uint64_t* plane_pitch = nullptr;   // M (planar only)
+  uint32_t M = 0;
+};
+
+// element = fmaf(byte, scale[c], bias[c]), stored as `type`
+struct TensorAffine {
+  float scale[3] = {1.0f / 255.0f, 1.0f / 255.0f, 1.0f / 255.0f};
+  float bias[3] = {0.0f, 0.0f, 0.0f};
+};
+
+// Decodes the windows of a set straight into normalised tensors (colour only).
+// d_status: one code per slot (nice_set_select), written on the device.
+inline void decode_set_tensor(const Context& ctx, void* stream, const SetTables& s, const TensorWindows& t,
+                              TensorType type, TensorLayout layout, const TensorAffine& a, int32_t* d_status,
+                              uint32_t flags = NICE_DEC_ALPHA_FILL_FF) {
+  check(nice_decode_set_tensor_dev(ctx.get(), stream, s.d_packed, s.packed_bytes, s.off, s.len, s.kind, s.w, s.h, s.K,
+                                   s.tile_w, s.tile_h, t.win, t.flip, t.out, t.row_pitch, t.plane_pitch, t.M,
+                                   (uint32_t)type, (uint32_t)layout, a.scale, a.bias, flags, d_status),
+        "nice_decode_set_tensor_dev");
+}
+
 }  // namespace nice
 #endif  // NICE_HPP
