@@ -19,6 +19,7 @@
 #include "nice_kernels.h"
 #include "nice_dec_plan.hpp"
 #include "nice_enc_plan.hpp"
+#include "nice_slot_plan.hpp"
 #include "nice_rec.hpp"
 #include "nice_internal.h"
 
@@ -933,14 +934,7 @@ extern "C" {
 // ---- tiled images ----------------------------------------------------------
 int nice_tile_grid(uint32_t w, uint32_t h, uint32_t tile_w, uint32_t tile_h, uint32_t* nx, uint32_t* ny) {
   if (!nx || !ny) return NICE_E_ARG;
-  if (w == 0 || h == 0 || (uint64_t)w * h > (1ull << 30)) return NICE_E_ARG;
-  if (tile_w < 2 || tile_h < 2 || tile_w > 8192 || tile_h > 8192) return NICE_E_ARG;
-  const uint64_t gx = ((uint64_t)w + tile_w - 1) / tile_w, gy = ((uint64_t)h + tile_h - 1) / tile_h;
-  // the batch encoder's 32-bit work counter: tiles x their 1024-pixel encoder tiles
-  if (gx * gy * enc_tiles(tile_w, tile_h) >= (1ull << 32)) return NICE_E_ARG;
-  *nx = (uint32_t)gx;
-  *ny = (uint32_t)gy;
-  return NICE_OK;
+  return nice::tile_grid(w, h, tile_w, tile_h, nx, ny);
 }
 
 uint64_t nice_tiled_bound(uint32_t w, uint32_t h, uint32_t tile_w, uint32_t tile_h) {
@@ -952,14 +946,14 @@ uint64_t nice_tiled_bound(uint32_t w, uint32_t h, uint32_t tile_w, uint32_t tile
 int nice_tile_select(uint32_t w, uint32_t h, uint32_t tile_w, uint32_t tile_h, uint32_t x0, uint32_t y0, uint32_t rw,
                      uint32_t rh, uint32_t* tx0, uint32_t* ty0, uint32_t* tx1, uint32_t* ty1) {
   uint32_t nx, ny;
+  TileRange r;
   if (!tx0 || !ty0 || !tx1 || !ty1) return NICE_E_ARG;
-  int rc = nice_tile_grid(w, h, tile_w, tile_h, &nx, &ny);
+  int rc = nice::tile_select(w, h, tile_w, tile_h, x0, y0, rw, rh, &nx, &ny, &r);
   if (rc) return rc;
-  if (rw == 0 || rh == 0 || (uint64_t)x0 + rw > w || (uint64_t)y0 + rh > h) return NICE_E_ARG;
-  *tx0 = x0 / tile_w;
-  *ty0 = y0 / tile_h;
-  *tx1 = (x0 + rw - 1) / tile_w + 1;
-  *ty1 = (y0 + rh - 1) / tile_h + 1;
+  *tx0 = r.tx0;
+  *ty0 = r.ty0;
+  *tx1 = r.tx1;
+  *ty1 = r.ty1;
   return NICE_OK;
 }
 
@@ -981,10 +975,10 @@ int nice_tiles_merge_dev(nice_ctx* ctx, void* stream, const uint8_t* d_tiles, ui
                          uint8_t out_channels, uint8_t alpha, uint8_t* d_out, uint64_t out_pitch) {
   if (!ctx || !d_out) return NICE_E_ARG;
   if ((tile_channels != 3 && tile_channels != 4) || (out_channels != 3 && out_channels != 4)) return NICE_E_ARG;
-  uint32_t a, b, c, d, nx, ny;
-  int rc = nice_tile_select(w, h, tile_w, tile_h, x0, y0, rw, rh, &a, &b, &c, &d);
+  uint32_t nx, ny;
+  TileRange r;
+  int rc = nice::tile_select(w, h, tile_w, tile_h, x0, y0, rw, rh, &nx, &ny, &r);
   if (rc) return rc;
-  (void)nice_tile_grid(w, h, tile_w, tile_h, &nx, &ny);
   if (out_pitch < (uint64_t)rw * out_channels) return NICE_E_ARG;
   if (n_slots == 0) return NICE_OK;
   if (!d_tiles || !d_tile_idx || tile_stride < (uint64_t)tile_w * tile_h * tile_channels) return NICE_E_ARG;
@@ -992,6 +986,105 @@ int nice_tiles_merge_dev(nice_ctx* ctx, void* stream, const uint8_t* d_tiles, ui
   return nice::tiles_merge_launch(stream, d_tiles, tile_stride, nullptr, d_tile_idx, nullptr, n_slots, w, h, tile_w,
                                   tile_h, nx, ny, x0, y0, rw, rh, tile_channels, out_channels, alpha, d_out, out_pitch);
 }
+
+namespace {
+// The scratch of a verified encode of n dense tiles: the tiles, their decode,
+// the strided stream slots, and tab_bytes of small tables that begin with the
+// verify decode's statuses (4 bytes a tile).
+struct TileEncScratch { uint64_t tile_stride, slot; };
+int tile_enc_scratch(nice_ctx* ctx, uint32_t n, uint32_t tile_w, uint32_t tile_h, uint8_t channels, size_t tab_bytes,
+                     TileEncScratch& s) {
+  int rc;
+  s.tile_stride = align_up((size_t)tile_w * tile_h * channels, 16);
+  s.slot = packed_slot_bytes(tile_w, tile_h);
+  if ((rc = ctx->tiles.grow((size_t)n * s.tile_stride))) return rc;
+  if ((rc = ctx->tile_dec.grow((size_t)n * s.tile_stride))) return rc;
+  if ((rc = ctx->pack.grow((size_t)n * s.slot))) return rc;
+  return ctx->tile_tab.grow(tab_bytes);
+}
+
+// The n dense tiles in ctx->tiles to a packed batch, always lossless: encode,
+// decode again, compare, store raw what the codec did not return, pack.
+int encode_tiles_verified(nice_ctx* ctx, void* stream, uint32_t n, uint32_t tile_w, uint32_t tile_h, uint8_t channels,
+                          uint8_t channels_out, const TileEncScratch& s, uint8_t* d_packed, uint64_t packed_cap,
+                          uint64_t* d_off, uint64_t* d_len, uint8_t* d_kind, int32_t* d_status) {
+  int rc;
+  const uint32_t npx = tile_w * tile_h;
+  uint8_t* tiles = (uint8_t*)ctx->tiles.ptr;
+  uint8_t* back = (uint8_t*)ctx->tile_dec.ptr;
+  uint8_t* slots = (uint8_t*)ctx->pack.ptr;
+  int32_t* dec_status = (int32_t*)ctx->tile_tab.ptr;
+  if ((rc = nice_encode_batch_dev(ctx, stream, tiles, s.tile_stride, n, tile_w, tile_h, channels, channels_out, slots,
+                                  s.slot, d_len)))
+    return rc;
+  // verify: a table header the format cannot carry (SURVEY.md Appendix A.5,
+  // DESIGN.md "Tiled images") shows as a failed or a different decode
+  if ((rc = nice::decode_batch_impl(ctx, stream, slots, s.slot, d_len, nullptr, n, tile_w, tile_h, channels, back,
+                                    s.tile_stride, NICE_DEC_TOLERANT_HEADER, dec_status)))
+    return rc;
+  if ((rc = nice::tiles_compare_launch(stream, tiles, s.tile_stride, back, s.tile_stride, channels, n, npx, dec_status,
+                                       d_kind)))
+    return rc;
+  if ((rc = nice::tiles_store_raw_launch(stream, tiles, s.tile_stride, channels, n, npx, d_kind, slots, s.slot, d_len)))
+    return rc;
+  return nice::pack_streams_launch(stream, ctx->cus, slots, s.slot, d_len, n, d_packed, packed_cap, d_off, d_status);
+}
+
+// A slot plan with its table, and where both went on the device: the callers'
+// window descriptors at `head`, the columns the merges read, the nc coded slots
+// decoded `stride` apart at `dec` with their statuses at c_st; ns: the raw
+// (colour) or the accepted (alpha) slots.  The host copies live here because
+// the uploads and the batch decode read them.
+struct DevSlots {
+  SlotPlan plan;
+  SlotTable tab;
+  uint32_t nc = 0, ns = 0;
+  const uint8_t *head = nullptr, *dec = nullptr, *s_kind = nullptr;
+  uint64_t stride = 0;
+  const int32_t* c_st = nullptr;
+  const uint32_t *c_idx = nullptr, *c_win = nullptr, *s_idx = nullptr, *s_win = nullptr;
+  const uint64_t* s_src = nullptr;
+};
+
+// What every tiled and set decode does with d.plan, up to its merges: one
+// upload of `head` (head_bytes, a multiple of 8) and the plan's columns, the
+// initial statuses, the batch decode of the coded slots (w x h at `channels`
+// bytes per pixel) from their offsets in the packed batch, and the scatter of
+// its statuses into d_status.
+int decode_planned_slots(nice_ctx* ctx, void* stream, const uint8_t* d_packed, uint64_t packed_bytes, const void* head,
+                         size_t head_bytes, uint32_t w, uint32_t h, uint8_t channels, uint32_t flags, int32_t* d_status,
+                         DevSlots& d) {
+  int rc;
+  hipStream_t st = (hipStream_t)stream;
+  const SlotPlan& p = d.plan;
+  const SlotTable& t = d.tab;
+  pack_slot_table(p, head, head_bytes, d.tab);
+  d.nc = (uint32_t)p.c_off.size();
+  d.ns = (uint32_t)p.s_idx.size();
+  d.stride = align_up((size_t)w * h * channels, 16);
+  if ((rc = ctx->tile_tab.grow(std::max<size_t>(t.bytes, 16)))) return rc;
+  if (d.nc && (rc = ctx->tile_dec.grow((size_t)d.nc * d.stride))) return rc;
+  uint8_t* dt = (uint8_t*)ctx->tile_tab.ptr;
+  int32_t* cst = (int32_t*)(dt + t.c_st);
+  d.head = dt;
+  d.dec = (const uint8_t*)ctx->tile_dec.ptr;
+  d.c_st = cst;
+  d.c_idx = (const uint32_t*)(dt + t.c_idx);
+  d.c_win = (const uint32_t*)(dt + t.c_win);
+  d.s_src = (const uint64_t*)(dt + t.s_src);
+  d.s_idx = (const uint32_t*)(dt + t.s_idx);
+  d.s_win = (const uint32_t*)(dt + t.s_win);
+  d.s_kind = dt + t.s_kind;
+  if (t.c_st) NICE_HIP(hipMemcpyAsync(dt, t.host.data(), t.c_st, hipMemcpyHostToDevice, st));
+  NICE_HIP(hipMemcpyAsync(d_status, p.init.data(), 4ull * p.init.size(), hipMemcpyHostToDevice, st));
+  if (!d.nc) return NICE_OK;
+  if ((rc = nice::decode_batch_impl(ctx, stream, d_packed, 0, (const uint64_t*)(dt + t.c_len), p.c_len.data(), d.nc, w, h,
+                                    channels, (uint8_t*)ctx->tile_dec.ptr, d.stride, flags, cst,
+                                    (const uint64_t*)(dt + t.c_off), packed_bytes)))
+    return rc;
+  return nice::tiles_scatter_status_launch(stream, cst, (const uint32_t*)(dt + t.c_pos), d.nc, d_status);
+}
+}  // namespace
 
 int nice_encode_tiled_dev(nice_ctx* ctx, void* stream, const uint8_t* d_img, uint64_t row_pitch, uint32_t w, uint32_t h,
                           uint8_t channels, uint8_t channels_out, uint32_t tile_w, uint32_t tile_h, uint8_t* d_packed,
@@ -1004,34 +1097,14 @@ int nice_encode_tiled_dev(nice_ctx* ctx, void* stream, const uint8_t* d_img, uin
   if (rc) return rc;
   if (row_pitch < (uint64_t)w * channels) return NICE_E_ARG;
   NICE_HIP(hipSetDevice(ctx->device));
-  const uint32_t n = nx * ny, npx = tile_w * tile_h;
-  const uint64_t tile_stride = align_up((size_t)npx * channels, 16);
-  const uint64_t slot = packed_slot_bytes(tile_w, tile_h);
-  if ((rc = ctx->tiles.grow((size_t)n * tile_stride))) return rc;
-  if ((rc = ctx->tile_dec.grow((size_t)n * tile_stride))) return rc;
-  if ((rc = ctx->pack.grow((size_t)n * slot))) return rc;
-  if ((rc = ctx->tile_tab.grow((size_t)n * 4))) return rc;
-  uint8_t* tiles = (uint8_t*)ctx->tiles.ptr;
-  uint8_t* back = (uint8_t*)ctx->tile_dec.ptr;
-  uint8_t* slots = (uint8_t*)ctx->pack.ptr;
-  int32_t* dec_status = (int32_t*)ctx->tile_tab.ptr;
-  if ((rc = nice::tiles_split_launch(stream, d_img, row_pitch, w, h, channels, tile_w, tile_h, nx, ny, tiles,
-                                     tile_stride)))
+  const uint32_t n = nx * ny;
+  TileEncScratch s;
+  if ((rc = tile_enc_scratch(ctx, n, tile_w, tile_h, channels, (size_t)n * 4, s))) return rc;
+  if ((rc = nice::tiles_split_launch(stream, d_img, row_pitch, w, h, channels, tile_w, tile_h, nx, ny,
+                                     (uint8_t*)ctx->tiles.ptr, s.tile_stride)))
     return rc;
-  if ((rc = nice_encode_batch_dev(ctx, stream, tiles, tile_stride, n, tile_w, tile_h, channels, channels_out, slots,
-                                  slot, d_len)))
-    return rc;
-  // verify: a table header the format cannot carry (SURVEY.md Appendix A.5,
-  // DESIGN.md "Tiled images") shows as a failed or a different decode
-  if ((rc = nice::decode_batch_impl(ctx, stream, slots, slot, d_len, nullptr, n, tile_w, tile_h, channels, back,
-                                    tile_stride, NICE_DEC_TOLERANT_HEADER, dec_status)))
-    return rc;
-  if ((rc = nice::tiles_compare_launch(stream, tiles, tile_stride, back, tile_stride, channels, n, npx, dec_status,
-                                       d_kind)))
-    return rc;
-  if ((rc = nice::tiles_store_raw_launch(stream, tiles, tile_stride, channels, n, npx, d_kind, slots, slot, d_len)))
-    return rc;
-  return nice::pack_streams_launch(stream, ctx->cus, slots, slot, d_len, n, d_packed, packed_cap, d_off, d_status);
+  return encode_tiles_verified(ctx, stream, n, tile_w, tile_h, channels, channels_out, s, d_packed, packed_cap, d_off,
+                               d_len, d_kind, d_status);
 }
 
 int nice_decode_tiled_dev(nice_ctx* ctx, void* stream, const uint8_t* d_packed, uint64_t packed_bytes,
@@ -1041,84 +1114,31 @@ int nice_decode_tiled_dev(nice_ctx* ctx, void* stream, const uint8_t* d_packed, 
   if (!ctx || !d_packed || !h_off || !h_len || !h_kind || !d_out || !d_status) return NICE_E_ARG;
   if (out_channels != 3 && out_channels != 4) return NICE_E_ARG;
   if ((flags & NICE_DEC_STRICT_REFERENCE) || ((uintptr_t)d_packed & 15)) return NICE_E_ARG;
-  uint32_t nx, ny, tx0, ty0, tx1, ty1;
-  int rc = nice_tile_select(w, h, tile_w, tile_h, x0, y0, rw, rh, &tx0, &ty0, &tx1, &ty1);
+  uint32_t nx, ny;
+  TileRange r;
+  int rc = nice::tile_select(w, h, tile_w, tile_h, x0, y0, rw, rh, &nx, &ny, &r);
   if (rc) return rc;
-  (void)nice_tile_grid(w, h, tile_w, tile_h, &nx, &ny);
   if (out_pitch < (uint64_t)rw * out_channels) return NICE_E_ARG;
   NICE_HIP(hipSetDevice(ctx->device));
-  hipStream_t st = (hipStream_t)stream;
-  const uint32_t m = (tx1 - tx0) * (ty1 - ty0);
-  const uint64_t npx = (uint64_t)tile_w * tile_h;
-  // the selected tiles by kind; a tile refused here keeps its status and is not touched
-  std::vector<uint64_t> c_off, c_len, r_off;
-  std::vector<uint32_t> c_idx, c_pos, r_idx;
-  std::vector<int32_t> init(m, NICE_OK);
-  uint32_t p = 0;
-  for (uint32_t ty = ty0; ty < ty1; ++ty) {
-    for (uint32_t tx = tx0; tx < tx1; ++tx, ++p) {
-      const uint32_t t = ty * nx + tx;
-      if (h_kind[t] == 0) {   // (its offset and length are checked on the device, as for any packed batch)
-        c_off.push_back(h_off[t]);
-        c_len.push_back(h_len[t]);
-        c_idx.push_back(t);
-        c_pos.push_back(p);
-      } else if (h_kind[t] != 1) {
-        init[p] = NICE_E_FORMAT;
-      } else if ((h_off[t] & 15) || h_off[t] > packed_bytes || h_len[t] > packed_bytes - h_off[t]) {
-        init[p] = NICE_E_ARG;
-      } else if (h_len[t] != 3 * npx) {
-        init[p] = NICE_E_FORMAT;
-      } else {
-        r_off.push_back(h_off[t]);
-        r_idx.push_back(t);
-      }
-    }
-  }
-  const uint32_t nc = (uint32_t)c_idx.size(), nr = (uint32_t)r_idx.size();
-  ctx->last_tiled_coded = nc;
-  ctx->last_tiled_raw = nr;
-  // one upload: u64 {coded offsets, coded lengths, raw offsets}, u32 {coded
-  // tile indices, coded positions, raw tile indices}, then the coded statuses
-  const size_t o_coff = 0, o_clen = o_coff + 8ull * nc, o_roff = o_clen + 8ull * nc, o_cidx = o_roff + 8ull * nr,
-               o_cpos = o_cidx + 4ull * nc, o_ridx = o_cpos + 4ull * nc, o_cst = align_up(o_ridx + 4ull * nr, 16),
-               tab_bytes = o_cst + 4ull * nc;
-  std::vector<uint8_t> tab(o_cst);
-  if (nc) {
-    memcpy(&tab[o_coff], c_off.data(), 8ull * nc);
-    memcpy(&tab[o_clen], c_len.data(), 8ull * nc);
-    memcpy(&tab[o_cidx], c_idx.data(), 4ull * nc);
-    memcpy(&tab[o_cpos], c_pos.data(), 4ull * nc);
-  }
-  if (nr) {
-    memcpy(&tab[o_roff], r_off.data(), 8ull * nr);
-    memcpy(&tab[o_ridx], r_idx.data(), 4ull * nr);
-  }
-  if ((rc = ctx->tile_tab.grow(std::max<size_t>(tab_bytes, 16)))) return rc;
-  uint8_t* dt = (uint8_t*)ctx->tile_tab.ptr;
-  if (o_cst) NICE_HIP(hipMemcpyAsync(dt, tab.data(), o_cst, hipMemcpyHostToDevice, st));
-  NICE_HIP(hipMemcpyAsync(d_status, init.data(), 4ull * m, hipMemcpyHostToDevice, st));
-  if (nc) {
-    const uint64_t stride = align_up((size_t)npx * out_channels, 16);
-    if ((rc = ctx->tile_dec.grow((size_t)nc * stride))) return rc;
-    uint8_t* dec = (uint8_t*)ctx->tile_dec.ptr;
-    int32_t* cst = (int32_t*)(dt + o_cst);
-    const uint32_t f = (flags & NICE_DEC_ALPHA_FILL_FF) | NICE_DEC_TOLERANT_HEADER;
-    if ((rc = nice::decode_batch_impl(ctx, stream, d_packed, 0, (const uint64_t*)(dt + o_clen), c_len.data(), nc, tile_w,
-                                      tile_h, out_channels, dec, stride, f, cst, (const uint64_t*)(dt + o_coff),
-                                      packed_bytes)))
-      return rc;
-    if ((rc = nice::tiles_scatter_status_launch(stream, cst, (const uint32_t*)(dt + o_cpos), nc, d_status))) return rc;
-    if ((rc = nice::tiles_merge_launch(stream, dec, stride, nullptr, (const uint32_t*)(dt + o_cidx), cst, nc, w, h,
-                                       tile_w, tile_h, nx, ny, x0, y0, rw, rh, out_channels, out_channels, 0, d_out,
-                                       out_pitch)))
+  // the one-image set with one window; a tile refused by the plan keeps its status and is not touched
+  const uint32_t first[2] = {0, nx * ny}, win[5] = {0, x0, y0, rw, rh};
+  DevSlots d;
+  plan_colour_slots(SlotTables{h_off, h_len, h_kind, nullptr, packed_bytes},
+                    SlotWindows{tile_w, tile_h, first, &nx, win, 1, false}, d.plan);
+  ctx->last_tiled_coded = d.plan.by_kind[0];
+  ctx->last_tiled_raw = d.plan.by_kind[1];
+  if ((rc = decode_planned_slots(ctx, stream, d_packed, packed_bytes, nullptr, 0, tile_w, tile_h, out_channels,
+                                 (flags & NICE_DEC_ALPHA_FILL_FF) | NICE_DEC_TOLERANT_HEADER, d_status, d)))
+    return rc;
+  if (d.nc) {
+    if ((rc = nice::tiles_merge_launch(stream, d.dec, d.stride, nullptr, d.c_idx, d.c_st, d.nc, w, h, tile_w, tile_h, nx,
+                                       ny, x0, y0, rw, rh, out_channels, out_channels, 0, d_out, out_pitch)))
       return rc;
   }
-  if (nr) {
+  if (d.ns) {
     const uint32_t fill = (flags & NICE_DEC_ALPHA_FILL_FF) ? 255u : 0u;
-    if ((rc = nice::tiles_merge_launch(stream, d_packed, 0, (const uint64_t*)(dt + o_roff),
-                                       (const uint32_t*)(dt + o_ridx), nullptr, nr, w, h, tile_w, tile_h, nx, ny, x0, y0,
-                                       rw, rh, 3, out_channels, fill, d_out, out_pitch)))
+    if ((rc = nice::tiles_merge_launch(stream, d_packed, 0, d.s_src, d.s_idx, nullptr, d.ns, w, h, tile_w, tile_h, nx, ny,
+                                       x0, y0, rw, rh, 3, out_channels, fill, d_out, out_pitch)))
       return rc;
   }
   return NICE_OK;
@@ -1152,6 +1172,95 @@ int nice_tiles_alpha_range_dev(nice_ctx* ctx, void* stream, const uint8_t* d_img
   return nice::alpha_range_launch(stream, d_img, row_pitch, w, h, tile_w, tile_h, nx, ny, d_lo, d_hi);
 }
 
+namespace {
+// The small tables of an alpha encode of n tiles, sized for every tile coded,
+// at the start of ctx->tile_tab: the stream lengths, the ranges, the list of
+// coded tiles, their decode statuses and verdicts; `end` is 16-byte aligned.
+// The host arrays live here because the copies to the device read them.
+struct AlphaEnc {
+  uint32_t n = 0, m = 0;   // tiles; tiles that are not constant
+  size_t o_mlen = 0, o_lo = 0, o_hi = 0, o_list = 0, o_st = 0, o_vk = 0, end = 0;
+  uint64_t slot = 0, trip_stride = 0;
+  std::vector<uint32_t> list;
+  std::vector<uint8_t> kind, val;
+  explicit AlphaEnc(uint32_t n_tiles) : n(n_tiles) {
+    o_lo = o_mlen + 8ull * n;
+    o_hi = o_lo + 4ull * n;
+    o_list = o_hi + 4ull * n;
+    o_st = o_list + 4ull * n;
+    o_vk = o_st + 4ull * n;
+    end = align_up(o_vk + n, 16);
+  }
+};
+
+// After the range launch: the first wait (the ranges say which tiles are coded
+// at all), then d_akind, d_aval, zero lengths, and for m > 0 the scratch of
+// the coded tiles and their list on the device, ready for the gather.
+int alpha_encode_classify(nice_ctx* ctx, hipStream_t st, uint32_t tile_w, uint32_t tile_h, AlphaEnc& a, uint64_t* d_alen,
+                          uint8_t* d_akind, uint8_t* d_aval) {
+  int rc;
+  const uint32_t n = a.n;
+  uint8_t* dt = (uint8_t*)ctx->tile_tab.ptr;
+  std::vector<uint32_t> range(2ull * n);
+  NICE_HIP(hipMemcpyAsync(range.data(), dt + a.o_lo, 8ull * n, hipMemcpyDeviceToHost, st));
+  NICE_HIP(hipStreamSynchronize(st));
+  a.kind.resize(n);
+  a.val.resize(n);
+  for (uint32_t t = 0; t < n; ++t) {
+    const bool flat = range[t] == range[n + t];
+    a.kind[t] = flat ? 2 : 0;
+    a.val[t] = flat ? (uint8_t)range[t] : 0;
+    if (!flat) a.list.push_back(t);
+  }
+  a.m = (uint32_t)a.list.size();
+  NICE_HIP(hipMemcpyAsync(d_akind, a.kind.data(), n, hipMemcpyHostToDevice, st));
+  NICE_HIP(hipMemcpyAsync(d_aval, a.val.data(), n, hipMemcpyHostToDevice, st));
+  NICE_HIP(hipMemsetAsync(d_alen, 0, 8ull * n, st));
+  a.slot = alpha_slot_bytes(tile_w, tile_h);
+  a.trip_stride = align_up((size_t)nice_tile_alpha_width(tile_w) * 3 * tile_h, 16);
+  if (!a.m) return NICE_OK;
+  if ((rc = ctx->tiles.grow((size_t)a.m * a.trip_stride))) return rc;
+  if ((rc = ctx->tile_dec.grow((size_t)a.m * a.trip_stride))) return rc;
+  if ((rc = ctx->pack.grow((size_t)a.m * a.slot))) return rc;
+  NICE_HIP(hipMemcpyAsync(dt + a.o_list, a.list.data(), 4ull * a.m, hipMemcpyHostToDevice, st));
+  return NICE_OK;
+}
+
+// After the gather launch: the m triplet images in ctx->tiles to streams or
+// raw planes (encode, decode again, compare, store), the offsets of all n
+// tiles, and the streams and planes to their places.
+int alpha_encode_finish(nice_ctx* ctx, void* stream, uint32_t tile_w, uint32_t tile_h, const AlphaEnc& a,
+                        uint8_t* d_apacked, uint64_t apacked_cap, uint64_t* d_aoff, uint64_t* d_alen, uint8_t* d_akind,
+                        int32_t* d_status) {
+  int rc;
+  const uint32_t m = a.m, aw = nice_tile_alpha_width(tile_w);
+  uint8_t* dt = (uint8_t*)ctx->tile_tab.ptr;
+  uint8_t* slots = (uint8_t*)ctx->pack.ptr;
+  uint32_t* d_list = (uint32_t*)(dt + a.o_list);
+  uint64_t* mlen = (uint64_t*)(dt + a.o_mlen);
+  if (m) {
+    uint8_t* trip = (uint8_t*)ctx->tiles.ptr;
+    uint8_t* back = (uint8_t*)ctx->tile_dec.ptr;
+    int32_t* dec_status = (int32_t*)(dt + a.o_st);
+    uint8_t* vk = dt + a.o_vk;
+    if ((rc = nice_encode_batch_dev(ctx, stream, trip, a.trip_stride, m, aw, tile_h, 3, 3, slots, a.slot, mlen)))
+      return rc;
+    // second wait: the stream lengths size the verify decode, as in encode_tiles_verified
+    if ((rc = nice::decode_batch_impl(ctx, stream, slots, a.slot, mlen, nullptr, m, aw, tile_h, 3, back, a.trip_stride,
+                                      NICE_DEC_TOLERANT_HEADER, dec_status)))
+      return rc;
+    if ((rc = nice::tiles_compare_launch(stream, trip, a.trip_stride, back, a.trip_stride, 3, m, aw * tile_h, dec_status,
+                                         vk)))
+      return rc;
+    if ((rc = nice::alpha_store_launch(stream, trip, a.trip_stride, tile_w, tile_h, d_list, m, vk, mlen, slots, a.slot,
+                                       d_akind, d_alen)))
+      return rc;
+  }
+  if ((rc = nice::pack_offsets_launch(stream, a.slot, d_alen, a.n, apacked_cap, d_aoff, d_status))) return rc;
+  return m ? nice::alpha_pack_launch(stream, slots, a.slot, mlen, d_list, m, d_aoff, d_apacked, apacked_cap) : NICE_OK;
+}
+}  // namespace
+
 int nice_encode_tiled_alpha_dev(nice_ctx* ctx, void* stream, const uint8_t* d_img, uint64_t row_pitch, uint32_t w,
                                 uint32_t h, uint32_t tile_w, uint32_t tile_h, uint8_t* d_apacked, uint64_t apacked_cap,
                                 uint64_t* d_aoff, uint64_t* d_alen, uint8_t* d_akind, uint8_t* d_aval,
@@ -1163,66 +1272,18 @@ int nice_encode_tiled_alpha_dev(nice_ctx* ctx, void* stream, const uint8_t* d_im
   if (rc) return rc;
   if (row_pitch < 4ull * w) return NICE_E_ARG;
   NICE_HIP(hipSetDevice(ctx->device));
-  hipStream_t st = (hipStream_t)stream;
-  const uint32_t n = nx * ny;
-  const uint32_t aw = nice_tile_alpha_width(tile_w);
-  // small tables, sized for every tile coded: the stream lengths, the ranges,
-  // the list of coded tiles, their decode statuses and verdicts
-  const size_t o_mlen = 0, o_lo = o_mlen + 8ull * n, o_hi = o_lo + 4ull * n, o_list = o_hi + 4ull * n,
-               o_st = o_list + 4ull * n, o_vk = o_st + 4ull * n;
-  if ((rc = ctx->tile_tab.grow(align_up(o_vk + n, 16)))) return rc;
+  AlphaEnc a(nx * ny);
+  if ((rc = ctx->tile_tab.grow(a.end))) return rc;
   uint8_t* dt = (uint8_t*)ctx->tile_tab.ptr;
-  // first wait: the ranges say which tiles are coded at all
-  if ((rc = nice::alpha_range_launch(stream, d_img, row_pitch, w, h, tile_w, tile_h, nx, ny, (uint32_t*)(dt + o_lo),
-                                     (uint32_t*)(dt + o_hi))))
+  if ((rc = nice::alpha_range_launch(stream, d_img, row_pitch, w, h, tile_w, tile_h, nx, ny, (uint32_t*)(dt + a.o_lo),
+                                     (uint32_t*)(dt + a.o_hi))))
     return rc;
-  std::vector<uint32_t> range(2ull * n), list;
-  NICE_HIP(hipMemcpyAsync(range.data(), dt + o_lo, 8ull * n, hipMemcpyDeviceToHost, st));
-  NICE_HIP(hipStreamSynchronize(st));
-  std::vector<uint8_t> kind(n), val(n);
-  for (uint32_t t = 0; t < n; ++t) {
-    const bool flat = range[t] == range[n + t];
-    kind[t] = flat ? 2 : 0;
-    val[t] = flat ? (uint8_t)range[t] : 0;
-    if (!flat) list.push_back(t);
-  }
-  const uint32_t m = (uint32_t)list.size();
-  NICE_HIP(hipMemcpyAsync(d_akind, kind.data(), n, hipMemcpyHostToDevice, st));
-  NICE_HIP(hipMemcpyAsync(d_aval, val.data(), n, hipMemcpyHostToDevice, st));
-  NICE_HIP(hipMemsetAsync(d_alen, 0, 8ull * n, st));
-  const uint64_t slot = alpha_slot_bytes(tile_w, tile_h);
-  if (m) {
-    const uint64_t trip_stride = align_up((size_t)aw * 3 * tile_h, 16);
-    if ((rc = ctx->tiles.grow((size_t)m * trip_stride))) return rc;
-    if ((rc = ctx->tile_dec.grow((size_t)m * trip_stride))) return rc;
-    if ((rc = ctx->pack.grow((size_t)m * slot))) return rc;
-    uint8_t* trip = (uint8_t*)ctx->tiles.ptr;
-    uint8_t* back = (uint8_t*)ctx->tile_dec.ptr;
-    uint8_t* slots = (uint8_t*)ctx->pack.ptr;
-    uint32_t* d_list = (uint32_t*)(dt + o_list);
-    uint64_t* mlen = (uint64_t*)(dt + o_mlen);
-    int32_t* dec_status = (int32_t*)(dt + o_st);
-    uint8_t* vk = dt + o_vk;
-    NICE_HIP(hipMemcpyAsync(d_list, list.data(), 4ull * m, hipMemcpyHostToDevice, st));
-    if ((rc = nice::alpha_gather_launch(stream, d_img, row_pitch, w, h, tile_w, tile_h, nx, d_list, m, trip,
-                                        trip_stride)))
-      return rc;
-    if ((rc = nice_encode_batch_dev(ctx, stream, trip, trip_stride, m, aw, tile_h, 3, 3, slots, slot, mlen))) return rc;
-    // second wait: the stream lengths size the verify decode, as in nice_encode_tiled_dev
-    if ((rc = nice::decode_batch_impl(ctx, stream, slots, slot, mlen, nullptr, m, aw, tile_h, 3, back, trip_stride,
-                                      NICE_DEC_TOLERANT_HEADER, dec_status)))
-      return rc;
-    if ((rc = nice::tiles_compare_launch(stream, trip, trip_stride, back, trip_stride, 3, m, aw * tile_h, dec_status,
-                                         vk)))
-      return rc;
-    if ((rc = nice::alpha_store_launch(stream, trip, trip_stride, tile_w, tile_h, d_list, m, vk, mlen, slots, slot,
-                                       d_akind, d_alen)))
-      return rc;
-  }
-  if ((rc = nice::pack_offsets_launch(stream, slot, d_alen, n, apacked_cap, d_aoff, d_status))) return rc;
-  return m ? nice::alpha_pack_launch(stream, (const uint8_t*)ctx->pack.ptr, slot, (const uint64_t*)(dt + o_mlen),
-                                     (const uint32_t*)(dt + o_list), m, d_aoff, d_apacked, apacked_cap)
-           : NICE_OK;
+  if ((rc = alpha_encode_classify(ctx, (hipStream_t)stream, tile_w, tile_h, a, d_alen, d_akind, d_aval))) return rc;
+  if (a.m && (rc = nice::alpha_gather_launch(stream, d_img, row_pitch, w, h, tile_w, tile_h, nx,
+                                             (const uint32_t*)(dt + a.o_list), a.m, (uint8_t*)ctx->tiles.ptr,
+                                             a.trip_stride)))
+    return rc;
+  return alpha_encode_finish(ctx, stream, tile_w, tile_h, a, d_apacked, apacked_cap, d_aoff, d_alen, d_akind, d_status);
 }
 
 int nice_decode_tiled_alpha_dev(nice_ctx* ctx, void* stream, const uint8_t* d_apacked, uint64_t apacked_bytes,
@@ -1232,105 +1293,28 @@ int nice_decode_tiled_alpha_dev(nice_ctx* ctx, void* stream, const uint8_t* d_ap
                                 int32_t* d_status) {
   if (!ctx || !h_aoff || !h_alen || !h_akind || !h_aval || !d_out || !d_status) return NICE_E_ARG;
   if ((!d_apacked && apacked_bytes) || ((uintptr_t)d_apacked & 15)) return NICE_E_ARG;
-  uint32_t nx, ny, tx0, ty0, tx1, ty1;
-  int rc = nice_tile_select(w, h, tile_w, tile_h, x0, y0, rw, rh, &tx0, &ty0, &tx1, &ty1);
+  uint32_t nx, ny;
+  TileRange r;
+  int rc = nice::tile_select(w, h, tile_w, tile_h, x0, y0, rw, rh, &nx, &ny, &r);
   if (rc) return rc;
-  (void)nice_tile_grid(w, h, tile_w, tile_h, &nx, &ny);
   if (out_pitch < 4ull * rw) return NICE_E_ARG;
   NICE_HIP(hipSetDevice(ctx->device));
-  hipStream_t st = (hipStream_t)stream;
-  const uint32_t m = (tx1 - tx0) * (ty1 - ty0);
-  const uint64_t npx = (uint64_t)tile_w * tile_h;
-  const uint32_t aw = nice_tile_alpha_width(tile_w);
-  // the selected tiles: the coded ones to decode, and every tile to merge with
-  // its source; a tile refused here keeps its status and is not touched
-  std::vector<uint64_t> c_off, c_len, s_src;
-  std::vector<uint32_t> c_pos, s_idx;
-  std::vector<uint8_t> s_kind;
-  std::vector<int32_t> init(m, NICE_OK);
-  uint32_t p = 0;
-  for (uint32_t ty = ty0; ty < ty1; ++ty) {
-    for (uint32_t tx = tx0; tx < tx1; ++tx, ++p) {
-      const uint32_t t = ty * nx + tx;
-      const uint64_t off = h_aoff[t], len = h_alen[t];
-      const uint8_t k = h_akind[t];
-      uint64_t src;
-      if (k > 2) {
-        init[p] = NICE_E_FORMAT;
-        continue;
-      } else if ((off & 15) || off > apacked_bytes || len > apacked_bytes - off) {
-        init[p] = NICE_E_ARG;
-        continue;
-      } else if (k == 2 ? len != 0 : k == 1 ? len != npx : len == 0) {   // (no stream is empty)
-        init[p] = NICE_E_FORMAT;
-        continue;
-      } else if (k == 2) {
-        src = h_aval[t];
-      } else if (k == 1) {
-        src = off;
-      } else {
-        src = c_off.size();
-        c_off.push_back(off);
-        c_len.push_back(len);
-        c_pos.push_back(p);
-      }
-      s_src.push_back(src);
-      s_idx.push_back(t);
-      s_kind.push_back(k);
-    }
-  }
-  const uint32_t nc = (uint32_t)c_off.size(), ns = (uint32_t)s_idx.size();
-  // one upload: u64 {coded offsets, coded lengths, sources}, u32 {coded
-  // positions, tile indices}, u8 kinds; then the coded statuses
-  const size_t o_coff = 0, o_clen = o_coff + 8ull * nc, o_src = o_clen + 8ull * nc, o_cpos = o_src + 8ull * ns,
-               o_idx = o_cpos + 4ull * nc, o_kind = o_idx + 4ull * ns, o_cst = align_up(o_kind + ns, 16),
-               tab_bytes = o_cst + 4ull * nc;
-  std::vector<uint8_t> tab(o_cst);
-  if (nc) {
-    memcpy(&tab[o_coff], c_off.data(), 8ull * nc);
-    memcpy(&tab[o_clen], c_len.data(), 8ull * nc);
-    memcpy(&tab[o_cpos], c_pos.data(), 4ull * nc);
-  }
-  if (ns) {
-    memcpy(&tab[o_src], s_src.data(), 8ull * ns);
-    memcpy(&tab[o_idx], s_idx.data(), 4ull * ns);
-    memcpy(&tab[o_kind], s_kind.data(), ns);
-  }
-  if ((rc = ctx->tile_tab.grow(std::max<size_t>(tab_bytes, 16)))) return rc;
-  uint8_t* dt = (uint8_t*)ctx->tile_tab.ptr;
-  if (o_cst) NICE_HIP(hipMemcpyAsync(dt, tab.data(), o_cst, hipMemcpyHostToDevice, st));
-  NICE_HIP(hipMemcpyAsync(d_status, init.data(), 4ull * m, hipMemcpyHostToDevice, st));
-  const uint64_t stride = align_up((size_t)aw * 3 * tile_h, 16);
-  int32_t* cst = (int32_t*)(dt + o_cst);
-  if (nc) {
-    if ((rc = ctx->tile_dec.grow((size_t)nc * stride))) return rc;
-    if ((rc = nice::decode_batch_impl(ctx, stream, d_apacked, 0, (const uint64_t*)(dt + o_clen), c_len.data(), nc, aw,
-                                      tile_h, 3, (uint8_t*)ctx->tile_dec.ptr, stride, NICE_DEC_TOLERANT_HEADER, cst,
-                                      (const uint64_t*)(dt + o_coff), apacked_bytes)))
-      return rc;
-    if ((rc = nice::tiles_scatter_status_launch(stream, cst, (const uint32_t*)(dt + o_cpos), nc, d_status))) return rc;
-  }
-  return nice::alpha_merge_launch(stream, (const uint8_t*)ctx->tile_dec.ptr, stride, cst, d_apacked,
-                                  (const uint64_t*)(dt + o_src), dt + o_kind, (const uint32_t*)(dt + o_idx), ns, w, h,
+  // the coded tiles to decode, and every accepted tile to merge with its source
+  const uint32_t first[2] = {0, nx * ny}, win[5] = {0, x0, y0, rw, rh};
+  DevSlots d;
+  plan_alpha_slots(SlotTables{h_aoff, h_alen, h_akind, h_aval, apacked_bytes},
+                   SlotWindows{tile_w, tile_h, first, &nx, win, 1, false}, d.plan);
+  if ((rc = decode_planned_slots(ctx, stream, d_apacked, apacked_bytes, nullptr, 0, nice_tile_alpha_width(tile_w), tile_h,
+                                 3, NICE_DEC_TOLERANT_HEADER, d_status, d)))
+    return rc;
+  return nice::alpha_merge_launch(stream, d.dec, d.stride, d.c_st, d_apacked, d.s_src, d.s_kind, d.s_idx, d.ns, w, h,
                                   tile_w, tile_h, nx, x0, y0, rw, rh, d_out, out_pitch);
 }
 
 // ---- image sets --------------------------------------------------------------
 int nice_set_grid(const uint32_t* h_w, const uint32_t* h_h, uint32_t K, uint32_t tile_w, uint32_t tile_h,
                   uint32_t* first) {
-  if (!h_w || !h_h || !first || K == 0) return NICE_E_ARG;
-  uint64_t n = 0;
-  for (uint32_t i = 0; i < K; ++i) {
-    uint32_t nx, ny;
-    int rc = nice_tile_grid(h_w[i], h_h[i], tile_w, tile_h, &nx, &ny);
-    if (rc) return rc;
-    first[i] = (uint32_t)n;
-    n += (uint64_t)nx * ny;
-    // the batch encoder's 32-bit work counter, over all tiles of the set
-    if (n * enc_tiles(tile_w, tile_h) >= (1ull << 32)) return NICE_E_ARG;
-  }
-  first[K] = (uint32_t)n;
-  return NICE_OK;
+  return nice::set_grid(h_w, h_h, K, tile_w, tile_h, first, nullptr);
 }
 
 uint64_t nice_set_bound(const uint32_t* h_w, const uint32_t* h_h, uint32_t K, uint32_t tile_w, uint32_t tile_h) {
@@ -1341,23 +1325,8 @@ uint64_t nice_set_bound(const uint32_t* h_w, const uint32_t* h_h, uint32_t K, ui
 
 int nice_set_select(const uint32_t* h_w, const uint32_t* h_h, uint32_t K, uint32_t tile_w, uint32_t tile_h,
                     const uint32_t* h_win, uint32_t M, uint32_t* slot_first) {
-  if (!h_win || !slot_first || M == 0) return NICE_E_ARG;
-  std::vector<uint32_t> first((size_t)K + 1);
-  int rc = nice_set_grid(h_w, h_h, K, tile_w, tile_h, first.data());
-  if (rc) return rc;
-  uint64_t s = 0;
-  for (uint32_t j = 0; j < M; ++j) {
-    const uint32_t* q = h_win + 5ull * j;
-    if (q[0] >= K) return NICE_E_ARG;
-    uint32_t tx0, ty0, tx1, ty1;
-    if ((rc = nice_tile_select(h_w[q[0]], h_h[q[0]], tile_w, tile_h, q[1], q[2], q[3], q[4], &tx0, &ty0, &tx1, &ty1)))
-      return rc;
-    slot_first[j] = (uint32_t)s;
-    s += (uint64_t)(tx1 - tx0) * (ty1 - ty0);
-    if (s >= (1ull << 32)) return NICE_E_ARG;
-  }
-  slot_first[M] = (uint32_t)s;
-  return NICE_OK;
+  std::vector<uint32_t> first, nx;
+  return nice::set_select(h_w, h_h, K, tile_w, tile_h, h_win, M, first, nx, slot_first);
 }
 
 namespace {
@@ -1450,149 +1419,35 @@ int nice_encode_set_dev(nice_ctx* ctx, void* stream, const uint8_t* const* h_img
   std::vector<SetImage> tab;
   if ((rc = set_image_table(h_img, h_pitch, h_w, h_h, K, channels, tile_w, first.data(), tab))) return rc;
   NICE_HIP(hipSetDevice(ctx->device));
-  const uint32_t n = first[K], npx = tile_w * tile_h;
-  const uint64_t tile_stride = align_up((size_t)npx * channels, 16);
-  const uint64_t slot = packed_slot_bytes(tile_w, tile_h);
+  const uint32_t n = first[K];
   // the small tables: the verify decode's statuses, then the image descriptors
   const size_t o_img = align_up((size_t)n * 4, 16);
-  if ((rc = ctx->tiles.grow((size_t)n * tile_stride))) return rc;
-  if ((rc = ctx->tile_dec.grow((size_t)n * tile_stride))) return rc;
-  if ((rc = ctx->pack.grow((size_t)n * slot))) return rc;
-  if ((rc = ctx->tile_tab.grow(o_img + K * sizeof(SetImage)))) return rc;
-  uint8_t* tiles = (uint8_t*)ctx->tiles.ptr;
-  uint8_t* back = (uint8_t*)ctx->tile_dec.ptr;
-  uint8_t* slots = (uint8_t*)ctx->pack.ptr;
-  int32_t* dec_status = (int32_t*)ctx->tile_tab.ptr;
+  TileEncScratch s;
+  if ((rc = tile_enc_scratch(ctx, n, tile_w, tile_h, channels, o_img + K * sizeof(SetImage), s))) return rc;
   const SetImage* d_imgs = (const SetImage*)((uint8_t*)ctx->tile_tab.ptr + o_img);
   NICE_HIP(hipMemcpyAsync((void*)d_imgs, tab.data(), K * sizeof(SetImage), hipMemcpyHostToDevice, (hipStream_t)stream));
-  if ((rc = nice::set_split_launch(stream, d_imgs, K, n, channels, tile_w, tile_h, tiles, tile_stride))) return rc;
-  // from here on exactly nice_encode_tiled_dev's sequence, over the tiles of all images
-  if ((rc = nice_encode_batch_dev(ctx, stream, tiles, tile_stride, n, tile_w, tile_h, channels, channels_out, slots,
-                                  slot, d_len)))
+  if ((rc = nice::set_split_launch(stream, d_imgs, K, n, channels, tile_w, tile_h, (uint8_t*)ctx->tiles.ptr,
+                                   s.tile_stride)))
     return rc;
-  if ((rc = nice::decode_batch_impl(ctx, stream, slots, slot, d_len, nullptr, n, tile_w, tile_h, channels, back,
-                                    tile_stride, NICE_DEC_TOLERANT_HEADER, dec_status)))
-    return rc;
-  if ((rc = nice::tiles_compare_launch(stream, tiles, tile_stride, back, tile_stride, channels, n, npx, dec_status,
-                                       d_kind)))
-    return rc;
-  if ((rc = nice::tiles_store_raw_launch(stream, tiles, tile_stride, channels, n, npx, d_kind, slots, slot, d_len)))
-    return rc;
-  return nice::pack_streams_launch(stream, ctx->cus, slots, slot, d_len, n, d_packed, packed_cap, d_off, d_status);
+  return encode_tiles_verified(ctx, stream, n, tile_w, tile_h, channels, channels_out, s, d_packed, packed_cap, d_off,
+                               d_len, d_kind, d_status);
 }
 
 namespace {
-// The slots of a set decode on the device: the decoded coded slots with their
-// tables and statuses, the tables of the raw slots, the window descriptors.
-struct SetSlots {
-  uint32_t nc = 0, nr = 0;
-  const uint8_t* d_wins = nullptr;
-  const uint8_t* dec = nullptr;    // coded slot i decoded at dec + i * stride
-  uint64_t stride = 0;
-  const int32_t* d_cst = nullptr;
-  const uint32_t *d_cwin = nullptr, *d_cidx = nullptr, *d_rwin = nullptr, *d_ridx = nullptr;
-  const uint64_t* d_roff = nullptr;
-};
-
 // What nice_decode_set_dev and nice_decode_set_tensor_dev share, up to their
-// merges: the m slots of the M windows by kind (checked: set and windows, by
-// the caller), one upload of the window descriptors (`wins`, wins_bytes, a
-// multiple of 8) and the gathered tables, the initial statuses, the batch
-// decode of the coded slots at dec_channels bytes per pixel and the scatter of
-// its statuses into d_status.
-int set_decode_slots(nice_ctx* ctx, void* stream, const uint8_t* d_packed, uint64_t packed_bytes, const uint64_t* h_off,
-                     const uint64_t* h_len, const uint8_t* h_kind, const uint32_t* h_w, uint32_t tile_w, uint32_t tile_h,
-                     const uint32_t* h_win, uint32_t M, const uint32_t* first, uint32_t m, const void* wins,
-                     size_t wins_bytes, uint32_t dec_channels, uint32_t flags, int32_t* d_status, SetSlots& s) {
-  int rc;
-  hipStream_t st = (hipStream_t)stream;
-  const uint64_t npx = (uint64_t)tile_w * tile_h;
-  // every (window, tile) pair is a slot; the slots by kind.  A slot refused
-  // here keeps its status and is not touched.
-  std::vector<uint64_t> c_off, c_len, r_off;
-  std::vector<uint32_t> c_idx, c_win, c_pos, r_idx, r_win;
-  std::vector<int32_t> init(m, NICE_OK);
-  uint32_t p = 0;
-  for (uint32_t j = 0; j < M; ++j) {
-    const uint32_t* q = h_win + 5ull * j;
-    const uint32_t nx = (h_w[q[0]] + tile_w - 1) / tile_w;
-    const uint32_t tx0 = q[1] / tile_w, ty0 = q[2] / tile_h;
-    const uint32_t tx1 = (q[1] + q[3] - 1) / tile_w + 1, ty1 = (q[2] + q[4] - 1) / tile_h + 1;
-    for (uint32_t ty = ty0; ty < ty1; ++ty) {
-      for (uint32_t tx = tx0; tx < tx1; ++tx, ++p) {
-        const uint32_t ti = ty * nx + tx, t = first[q[0]] + ti;
-        if (h_kind[t] == 0) {   // (its offset and length are checked on the device, as for any packed batch)
-          c_off.push_back(h_off[t]);
-          c_len.push_back(h_len[t]);
-          c_idx.push_back(ti);
-          c_win.push_back(j);
-          c_pos.push_back(p);
-        } else if (h_kind[t] != 1) {
-          init[p] = NICE_E_FORMAT;
-        } else if ((h_off[t] & 15) || h_off[t] > packed_bytes || h_len[t] > packed_bytes - h_off[t]) {
-          init[p] = NICE_E_ARG;
-        } else if (h_len[t] != 3 * npx) {
-          init[p] = NICE_E_FORMAT;
-        } else {
-          r_off.push_back(h_off[t]);
-          r_idx.push_back(ti);
-          r_win.push_back(j);
-        }
-      }
-    }
-  }
-  const uint32_t nc = (uint32_t)c_idx.size(), nr = (uint32_t)r_idx.size();
-  ctx->last_set_coded = nc;
-  ctx->last_set_raw = nr;
-  // one upload: the window descriptors, u64 {coded offsets, coded lengths, raw
-  // offsets}, u32 {coded tile indices, windows, positions, raw tile indices,
-  // windows}; then the coded statuses
-  const size_t o_win = 0, o_coff = o_win + wins_bytes, o_clen = o_coff + 8ull * nc,
-               o_roff = o_clen + 8ull * nc, o_cidx = o_roff + 8ull * nr, o_cwin = o_cidx + 4ull * nc,
-               o_cpos = o_cwin + 4ull * nc, o_ridx = o_cpos + 4ull * nc, o_rwin = o_ridx + 4ull * nr,
-               o_cst = align_up(o_rwin + 4ull * nr, 16), tab_bytes = o_cst + 4ull * nc;
-  std::vector<uint8_t> tab(o_cst);
-  memcpy(&tab[o_win], wins, wins_bytes);
-  if (nc) {
-    memcpy(&tab[o_coff], c_off.data(), 8ull * nc);
-    memcpy(&tab[o_clen], c_len.data(), 8ull * nc);
-    memcpy(&tab[o_cidx], c_idx.data(), 4ull * nc);
-    memcpy(&tab[o_cwin], c_win.data(), 4ull * nc);
-    memcpy(&tab[o_cpos], c_pos.data(), 4ull * nc);
-  }
-  if (nr) {
-    memcpy(&tab[o_roff], r_off.data(), 8ull * nr);
-    memcpy(&tab[o_ridx], r_idx.data(), 4ull * nr);
-    memcpy(&tab[o_rwin], r_win.data(), 4ull * nr);
-  }
-  const uint64_t stride = align_up((size_t)npx * dec_channels, 16);
-  if ((rc = ctx->tile_tab.grow(tab_bytes))) return rc;
-  if (nc && (rc = ctx->tile_dec.grow((size_t)nc * stride))) return rc;
-  uint8_t* dt = (uint8_t*)ctx->tile_tab.ptr;
-  NICE_HIP(hipMemcpyAsync(dt, tab.data(), o_cst, hipMemcpyHostToDevice, st));
-  NICE_HIP(hipMemcpyAsync(d_status, init.data(), 4ull * m, hipMemcpyHostToDevice, st));
-  s.nc = nc;
-  s.nr = nr;
-  s.d_wins = dt + o_win;
-  s.dec = (const uint8_t*)ctx->tile_dec.ptr;
-  s.stride = stride;
-  s.d_cst = (const int32_t*)(dt + o_cst);
-  s.d_cwin = (const uint32_t*)(dt + o_cwin);
-  s.d_cidx = (const uint32_t*)(dt + o_cidx);
-  s.d_rwin = (const uint32_t*)(dt + o_rwin);
-  s.d_ridx = (const uint32_t*)(dt + o_ridx);
-  s.d_roff = (const uint64_t*)(dt + o_roff);
-  if (nc) {
-    uint8_t* dec = (uint8_t*)ctx->tile_dec.ptr;
-    int32_t* cst = (int32_t*)(dt + o_cst);
-    const uint32_t f = (flags & NICE_DEC_ALPHA_FILL_FF) | NICE_DEC_TOLERANT_HEADER;
-    if ((rc = nice::decode_batch_impl(ctx, stream, d_packed, 0, (const uint64_t*)(dt + o_clen), c_len.data(), nc, tile_w,
-                                      tile_h, (uint8_t)dec_channels, dec, stride, f, cst, (const uint64_t*)(dt + o_coff),
-                                      packed_bytes)))
-      return rc;
-    if ((rc = nice::tiles_scatter_status_launch(stream, cst, (const uint32_t*)(dt + o_cpos), nc, d_status))) return rc;
-  }
-  return NICE_OK;
+// merges (checked: set and windows, by the caller): the colour plan of the M
+// windows, its table behind the window descriptors (`wins`, wins_bytes, a
+// multiple of 8), and decode_planned_slots at dec_channels bytes per pixel.
+int set_decode_colour(nice_ctx* ctx, void* stream, const uint8_t* d_packed, uint64_t packed_bytes, const uint64_t* h_off,
+                      const uint64_t* h_len, const uint8_t* h_kind, uint32_t tile_w, uint32_t tile_h,
+                      const uint32_t* first, const uint32_t* nx, const uint32_t* h_win, uint32_t M, const void* wins,
+                      size_t wins_bytes, uint8_t dec_channels, uint32_t flags, int32_t* d_status, DevSlots& d) {
+  plan_colour_slots(SlotTables{h_off, h_len, h_kind, nullptr, packed_bytes},
+                    SlotWindows{tile_w, tile_h, first, nx, h_win, M, true}, d.plan);
+  ctx->last_set_coded = d.plan.by_kind[0];
+  ctx->last_set_raw = d.plan.by_kind[1];
+  return decode_planned_slots(ctx, stream, d_packed, packed_bytes, wins, wins_bytes, tile_w, tile_h, dec_channels,
+                              (flags & NICE_DEC_ALPHA_FILL_FF) | NICE_DEC_TOLERANT_HEADER, d_status, d);
 }
 }  // namespace
 
@@ -1604,27 +1459,25 @@ int nice_decode_set_dev(nice_ctx* ctx, void* stream, const uint8_t* d_packed, ui
   if (!ctx || !d_packed || !h_off || !h_len || !h_kind || !d_status) return NICE_E_ARG;
   if (out_channels != 3 && out_channels != 4) return NICE_E_ARG;
   if ((flags & NICE_DEC_STRICT_REFERENCE) || ((uintptr_t)d_packed & 15)) return NICE_E_ARG;
-  std::vector<uint32_t> first((size_t)K + 1), slot_first((size_t)M + 1);
-  int rc = nice_set_select(h_w, h_h, K, tile_w, tile_h, h_win, M, slot_first.data());
+  std::vector<uint32_t> first, nx, slot_first((size_t)M + 1);
+  int rc = nice::set_select(h_w, h_h, K, tile_w, tile_h, h_win, M, first, nx, slot_first.data());
   if (rc) return rc;
-  (void)nice_set_grid(h_w, h_h, K, tile_w, tile_h, first.data());
   std::vector<SetWindow> wins;
   if ((rc = set_window_table(h_w, h_h, K, tile_w, tile_h, h_win, h_out, h_out_pitch, M, out_channels, wins))) return rc;
   NICE_HIP(hipSetDevice(ctx->device));
-  SetSlots s;
-  if ((rc = set_decode_slots(ctx, stream, d_packed, packed_bytes, h_off, h_len, h_kind, h_w, tile_w, tile_h, h_win, M,
-                             first.data(), slot_first[M], wins.data(), M * sizeof(SetWindow), out_channels, flags,
-                             d_status, s)))
+  DevSlots d;
+  if ((rc = set_decode_colour(ctx, stream, d_packed, packed_bytes, h_off, h_len, h_kind, tile_w, tile_h, first.data(),
+                              nx.data(), h_win, M, wins.data(), M * sizeof(SetWindow), out_channels, flags, d_status, d)))
     return rc;
-  const SetWindow* d_wins = (const SetWindow*)s.d_wins;
-  if (s.nc) {
-    if ((rc = nice::set_merge_launch(stream, s.dec, s.stride, nullptr, s.d_cwin, s.d_cidx, s.d_cst, s.nc, d_wins, M,
-                                     tile_w, tile_h, out_channels, out_channels, 0)))
+  const SetWindow* d_wins = (const SetWindow*)d.head;
+  if (d.nc) {
+    if ((rc = nice::set_merge_launch(stream, d.dec, d.stride, nullptr, d.c_win, d.c_idx, d.c_st, d.nc, d_wins, M, tile_w,
+                                     tile_h, out_channels, out_channels, 0)))
       return rc;
   }
-  if (s.nr) {
+  if (d.ns) {
     const uint32_t fill = (flags & NICE_DEC_ALPHA_FILL_FF) ? 255u : 0u;
-    if ((rc = nice::set_merge_launch(stream, d_packed, 0, s.d_roff, s.d_rwin, s.d_ridx, nullptr, s.nr, d_wins, M, tile_w,
+    if ((rc = nice::set_merge_launch(stream, d_packed, 0, d.s_src, d.s_win, d.s_idx, nullptr, d.ns, d_wins, M, tile_w,
                                      tile_h, 3, out_channels, fill)))
       return rc;
   }
@@ -1709,28 +1562,26 @@ int nice_decode_set_tensor_dev(nice_ctx* ctx, void* stream, const uint8_t* d_pac
   if ((flags & NICE_DEC_STRICT_REFERENCE) || ((uintptr_t)d_packed & 15)) return NICE_E_ARG;
   int rc = set_tensor_check(dtype, layout, scale, bias);
   if (rc) return rc;
-  std::vector<uint32_t> first((size_t)K + 1), slot_first((size_t)M + 1);
-  if ((rc = nice_set_select(h_w, h_h, K, tile_w, tile_h, h_win, M, slot_first.data()))) return rc;
-  (void)nice_set_grid(h_w, h_h, K, tile_w, tile_h, first.data());
+  std::vector<uint32_t> first, nx, slot_first((size_t)M + 1);
+  if ((rc = nice::set_select(h_w, h_h, K, tile_w, tile_h, h_win, M, first, nx, slot_first.data()))) return rc;
   std::vector<SetTensorWindow> wins;
   if ((rc = set_tensor_window_table(h_w, h_h, tile_w, tile_h, h_win, h_flip, h_out, h_row_pitch, h_plane_pitch, M, dtype,
                                     layout, wins)))
     return rc;
   NICE_HIP(hipSetDevice(ctx->device));
   // the coded slots at 4 bytes per pixel, whatever the set's channels: a lane loads dwords
-  SetSlots s;
-  if ((rc = set_decode_slots(ctx, stream, d_packed, packed_bytes, h_off, h_len, h_kind, h_w, tile_w, tile_h, h_win, M,
-                             first.data(), slot_first[M], wins.data(), M * sizeof(SetTensorWindow), 4, flags, d_status,
-                             s)))
+  DevSlots d;
+  if ((rc = set_decode_colour(ctx, stream, d_packed, packed_bytes, h_off, h_len, h_kind, tile_w, tile_h, first.data(),
+                              nx.data(), h_win, M, wins.data(), M * sizeof(SetTensorWindow), 4, flags, d_status, d)))
     return rc;
-  const SetTensorWindow* d_wins = (const SetTensorWindow*)s.d_wins;
-  if (s.nc) {
-    if ((rc = nice::set_merge_tensor_launch(stream, s.dec, s.stride, nullptr, s.d_cwin, s.d_cidx, s.d_cst, s.nc, d_wins,
-                                            M, tile_w, tile_h, 4, dtype, layout, scale, bias)))
+  const SetTensorWindow* d_wins = (const SetTensorWindow*)d.head;
+  if (d.nc) {
+    if ((rc = nice::set_merge_tensor_launch(stream, d.dec, d.stride, nullptr, d.c_win, d.c_idx, d.c_st, d.nc, d_wins, M,
+                                            tile_w, tile_h, 4, dtype, layout, scale, bias)))
       return rc;
   }
-  if (s.nr) {
-    if ((rc = nice::set_merge_tensor_launch(stream, d_packed, 0, s.d_roff, s.d_rwin, s.d_ridx, nullptr, s.nr, d_wins, M,
+  if (d.ns) {
+    if ((rc = nice::set_merge_tensor_launch(stream, d_packed, 0, d.s_src, d.s_win, d.s_idx, nullptr, d.ns, d_wins, M,
                                             tile_w, tile_h, 3, dtype, layout, scale, bias)))
       return rc;
   }
@@ -1776,67 +1627,20 @@ int nice_encode_set_alpha_dev(nice_ctx* ctx, void* stream, const uint8_t* const*
   if ((rc = set_image_table(h_img, h_pitch, h_w, h_h, K, 4, tile_w, first.data(), imgs))) return rc;
   NICE_HIP(hipSetDevice(ctx->device));
   hipStream_t st = (hipStream_t)stream;
-  const uint32_t n = first[K];
-  const uint32_t aw = nice_tile_alpha_width(tile_w);
-  // small tables, sized for every tile coded, as in nice_encode_tiled_alpha_dev
-  // (stream lengths, ranges, the list of coded tiles, their decode statuses and
-  // verdicts), then the image descriptors
-  const size_t o_mlen = 0, o_lo = o_mlen + 8ull * n, o_hi = o_lo + 4ull * n, o_list = o_hi + 4ull * n,
-               o_st = o_list + 4ull * n, o_vk = o_st + 4ull * n, o_img = align_up(o_vk + n, 16);
-  if ((rc = ctx->tile_tab.grow(o_img + K * sizeof(SetImage)))) return rc;
+  // the small tables of the alpha encode, then the image descriptors
+  AlphaEnc a(first[K]);
+  if ((rc = ctx->tile_tab.grow(a.end + K * sizeof(SetImage)))) return rc;
   uint8_t* dt = (uint8_t*)ctx->tile_tab.ptr;
-  const SetImage* d_imgs = (const SetImage*)(dt + o_img);
+  const SetImage* d_imgs = (const SetImage*)(dt + a.end);
   NICE_HIP(hipMemcpyAsync((void*)d_imgs, imgs.data(), K * sizeof(SetImage), hipMemcpyHostToDevice, st));
-  // first wait: the ranges say which tiles are coded at all
-  if ((rc = nice::set_alpha_range_launch(stream, d_imgs, K, n, tile_w, tile_h, (uint32_t*)(dt + o_lo),
-                                         (uint32_t*)(dt + o_hi))))
+  if ((rc = nice::set_alpha_range_launch(stream, d_imgs, K, a.n, tile_w, tile_h, (uint32_t*)(dt + a.o_lo),
+                                         (uint32_t*)(dt + a.o_hi))))
     return rc;
-  std::vector<uint32_t> range(2ull * n), list;
-  NICE_HIP(hipMemcpyAsync(range.data(), dt + o_lo, 8ull * n, hipMemcpyDeviceToHost, st));
-  NICE_HIP(hipStreamSynchronize(st));
-  std::vector<uint8_t> kind(n), val(n);
-  for (uint32_t t = 0; t < n; ++t) {
-    const bool flat = range[t] == range[n + t];
-    kind[t] = flat ? 2 : 0;
-    val[t] = flat ? (uint8_t)range[t] : 0;
-    if (!flat) list.push_back(t);
-  }
-  const uint32_t m = (uint32_t)list.size();
-  NICE_HIP(hipMemcpyAsync(d_akind, kind.data(), n, hipMemcpyHostToDevice, st));
-  NICE_HIP(hipMemcpyAsync(d_aval, val.data(), n, hipMemcpyHostToDevice, st));
-  NICE_HIP(hipMemsetAsync(d_alen, 0, 8ull * n, st));
-  const uint64_t slot = alpha_slot_bytes(tile_w, tile_h);
-  if (m) {
-    const uint64_t trip_stride = align_up((size_t)aw * 3 * tile_h, 16);
-    if ((rc = ctx->tiles.grow((size_t)m * trip_stride))) return rc;
-    if ((rc = ctx->tile_dec.grow((size_t)m * trip_stride))) return rc;
-    if ((rc = ctx->pack.grow((size_t)m * slot))) return rc;
-    uint8_t* trip = (uint8_t*)ctx->tiles.ptr;
-    uint8_t* back = (uint8_t*)ctx->tile_dec.ptr;
-    uint8_t* slots = (uint8_t*)ctx->pack.ptr;
-    uint32_t* d_list = (uint32_t*)(dt + o_list);
-    uint64_t* mlen = (uint64_t*)(dt + o_mlen);
-    int32_t* dec_status = (int32_t*)(dt + o_st);
-    uint8_t* vk = dt + o_vk;
-    NICE_HIP(hipMemcpyAsync(d_list, list.data(), 4ull * m, hipMemcpyHostToDevice, st));
-    if ((rc = nice::set_alpha_gather_launch(stream, d_imgs, K, tile_w, tile_h, d_list, m, trip, trip_stride))) return rc;
-    // from here on exactly nice_encode_tiled_alpha_dev's sequence, over the non-constant tiles of all images
-    if ((rc = nice_encode_batch_dev(ctx, stream, trip, trip_stride, m, aw, tile_h, 3, 3, slots, slot, mlen))) return rc;
-    // second wait: the stream lengths size the verify decode
-    if ((rc = nice::decode_batch_impl(ctx, stream, slots, slot, mlen, nullptr, m, aw, tile_h, 3, back, trip_stride,
-                                      NICE_DEC_TOLERANT_HEADER, dec_status)))
-      return rc;
-    if ((rc = nice::tiles_compare_launch(stream, trip, trip_stride, back, trip_stride, 3, m, aw * tile_h, dec_status,
-                                         vk)))
-      return rc;
-    if ((rc = nice::alpha_store_launch(stream, trip, trip_stride, tile_w, tile_h, d_list, m, vk, mlen, slots, slot,
-                                       d_akind, d_alen)))
-      return rc;
-  }
-  if ((rc = nice::pack_offsets_launch(stream, slot, d_alen, n, apacked_cap, d_aoff, d_status))) return rc;
-  return m ? nice::alpha_pack_launch(stream, (const uint8_t*)ctx->pack.ptr, slot, (const uint64_t*)(dt + o_mlen),
-                                     (const uint32_t*)(dt + o_list), m, d_aoff, d_apacked, apacked_cap)
-           : NICE_OK;
+  if ((rc = alpha_encode_classify(ctx, st, tile_w, tile_h, a, d_alen, d_akind, d_aval))) return rc;
+  if (a.m && (rc = nice::set_alpha_gather_launch(stream, d_imgs, K, tile_w, tile_h, (const uint32_t*)(dt + a.o_list),
+                                                 a.m, (uint8_t*)ctx->tiles.ptr, a.trip_stride)))
+    return rc;
+  return alpha_encode_finish(ctx, stream, tile_w, tile_h, a, d_apacked, apacked_cap, d_aoff, d_alen, d_akind, d_status);
 }
 
 int nice_decode_set_alpha_dev(nice_ctx* ctx, void* stream, const uint8_t* d_apacked, uint64_t apacked_bytes,
@@ -1846,105 +1650,25 @@ int nice_decode_set_alpha_dev(nice_ctx* ctx, void* stream, const uint8_t* d_apac
                               const uint64_t* h_out_pitch, uint32_t M, int32_t* d_status) {
   if (!ctx || !h_aoff || !h_alen || !h_akind || !h_aval || !d_status) return NICE_E_ARG;
   if ((!d_apacked && apacked_bytes) || ((uintptr_t)d_apacked & 15)) return NICE_E_ARG;
-  std::vector<uint32_t> first((size_t)K + 1), slot_first((size_t)M + 1);
-  int rc = nice_set_select(h_w, h_h, K, tile_w, tile_h, h_win, M, slot_first.data());
+  std::vector<uint32_t> first, nx, slot_first((size_t)M + 1);
+  int rc = nice::set_select(h_w, h_h, K, tile_w, tile_h, h_win, M, first, nx, slot_first.data());
   if (rc) return rc;
-  (void)nice_set_grid(h_w, h_h, K, tile_w, tile_h, first.data());
   std::vector<SetWindow> wins;
   if ((rc = set_window_table(h_w, h_h, K, tile_w, tile_h, h_win, h_out, h_out_pitch, M, 4, wins))) return rc;
   NICE_HIP(hipSetDevice(ctx->device));
-  hipStream_t st = (hipStream_t)stream;
-  const uint32_t m = slot_first[M];
-  const uint64_t npx = (uint64_t)tile_w * tile_h;
-  const uint32_t aw = nice_tile_alpha_width(tile_w);
   // every (window, tile) pair is a slot: the coded ones to decode, and every
-  // slot to merge with its source; a slot refused here keeps its status and is
-  // not touched
-  std::vector<uint64_t> c_off, c_len, s_src;
-  std::vector<uint32_t> c_pos, s_win, s_idx;
-  std::vector<uint8_t> s_kind;
-  std::vector<int32_t> init(m, NICE_OK);
-  uint32_t by_kind[3] = {0, 0, 0};
-  uint32_t p = 0;
-  for (uint32_t j = 0; j < M; ++j) {
-    const uint32_t* q = h_win + 5ull * j;
-    const uint32_t nx = wins[j].nx;
-    const uint32_t tx0 = q[1] / tile_w, ty0 = q[2] / tile_h;
-    const uint32_t tx1 = (q[1] + q[3] - 1) / tile_w + 1, ty1 = (q[2] + q[4] - 1) / tile_h + 1;
-    for (uint32_t ty = ty0; ty < ty1; ++ty) {
-      for (uint32_t tx = tx0; tx < tx1; ++tx, ++p) {
-        const uint32_t ti = ty * nx + tx, t = first[q[0]] + ti;
-        const uint64_t off = h_aoff[t], len = h_alen[t];
-        const uint8_t k = h_akind[t];
-        uint64_t src;
-        if (k > 2) {
-          init[p] = NICE_E_FORMAT;
-          continue;
-        } else if ((off & 15) || off > apacked_bytes || len > apacked_bytes - off) {
-          init[p] = NICE_E_ARG;
-          continue;
-        } else if (k == 2 ? len != 0 : k == 1 ? len != npx : len == 0) {   // (no stream is empty)
-          init[p] = NICE_E_FORMAT;
-          continue;
-        } else if (k == 2) {
-          src = h_aval[t];
-        } else if (k == 1) {
-          src = off;
-        } else {
-          src = c_off.size();
-          c_off.push_back(off);
-          c_len.push_back(len);
-          c_pos.push_back(p);
-        }
-        s_src.push_back(src);
-        s_win.push_back(j);
-        s_idx.push_back(ti);
-        s_kind.push_back(k);
-        ++by_kind[k];
-      }
-    }
-  }
-  const uint32_t nc = (uint32_t)c_off.size(), ns = (uint32_t)s_idx.size();
-  ctx->last_set_alpha_coded = by_kind[0];
-  ctx->last_set_alpha_raw = by_kind[1];
-  ctx->last_set_alpha_const = by_kind[2];
-  // one upload: the window descriptors, u64 {coded offsets, coded lengths,
-  // sources}, u32 {coded positions, windows, tile indices}, u8 kinds; then the
-  // coded statuses
-  const size_t o_win = 0, o_coff = o_win + M * sizeof(SetWindow), o_clen = o_coff + 8ull * nc, o_src = o_clen + 8ull * nc,
-               o_cpos = o_src + 8ull * ns, o_swin = o_cpos + 4ull * nc, o_idx = o_swin + 4ull * ns,
-               o_kind = o_idx + 4ull * ns, o_cst = align_up(o_kind + ns, 16), tab_bytes = o_cst + 4ull * nc;
-  std::vector<uint8_t> tab(o_cst);
-  memcpy(&tab[o_win], wins.data(), M * sizeof(SetWindow));
-  if (nc) {
-    memcpy(&tab[o_coff], c_off.data(), 8ull * nc);
-    memcpy(&tab[o_clen], c_len.data(), 8ull * nc);
-    memcpy(&tab[o_cpos], c_pos.data(), 4ull * nc);
-  }
-  if (ns) {
-    memcpy(&tab[o_src], s_src.data(), 8ull * ns);
-    memcpy(&tab[o_swin], s_win.data(), 4ull * ns);
-    memcpy(&tab[o_idx], s_idx.data(), 4ull * ns);
-    memcpy(&tab[o_kind], s_kind.data(), ns);
-  }
-  const uint64_t stride = align_up((size_t)aw * 3 * tile_h, 16);
-  if ((rc = ctx->tile_tab.grow(std::max<size_t>(tab_bytes, 16)))) return rc;
-  if (nc && (rc = ctx->tile_dec.grow((size_t)nc * stride))) return rc;
-  uint8_t* dt = (uint8_t*)ctx->tile_tab.ptr;
-  NICE_HIP(hipMemcpyAsync(dt, tab.data(), o_cst, hipMemcpyHostToDevice, st));
-  NICE_HIP(hipMemcpyAsync(d_status, init.data(), 4ull * m, hipMemcpyHostToDevice, st));
-  int32_t* cst = (int32_t*)(dt + o_cst);
-  if (nc) {
-    if ((rc = nice::decode_batch_impl(ctx, stream, d_apacked, 0, (const uint64_t*)(dt + o_clen), c_len.data(), nc, aw,
-                                      tile_h, 3, (uint8_t*)ctx->tile_dec.ptr, stride, NICE_DEC_TOLERANT_HEADER, cst,
-                                      (const uint64_t*)(dt + o_coff), apacked_bytes)))
-      return rc;
-    if ((rc = nice::tiles_scatter_status_launch(stream, cst, (const uint32_t*)(dt + o_cpos), nc, d_status))) return rc;
-  }
-  return nice::set_alpha_merge_launch(stream, (const uint8_t*)ctx->tile_dec.ptr, stride, cst, d_apacked,
-                                      (const uint64_t*)(dt + o_src), dt + o_kind, (const uint32_t*)(dt + o_swin),
-                                      (const uint32_t*)(dt + o_idx), ns, (const SetWindow*)(dt + o_win), M, tile_w,
-                                      tile_h);
+  // accepted slot to merge with its source
+  DevSlots d;
+  plan_alpha_slots(SlotTables{h_aoff, h_alen, h_akind, h_aval, apacked_bytes},
+                   SlotWindows{tile_w, tile_h, first.data(), nx.data(), h_win, M, true}, d.plan);
+  ctx->last_set_alpha_coded = d.plan.by_kind[0];
+  ctx->last_set_alpha_raw = d.plan.by_kind[1];
+  ctx->last_set_alpha_const = d.plan.by_kind[2];
+  if ((rc = decode_planned_slots(ctx, stream, d_apacked, apacked_bytes, wins.data(), M * sizeof(SetWindow),
+                                 nice_tile_alpha_width(tile_w), tile_h, 3, NICE_DEC_TOLERANT_HEADER, d_status, d)))
+    return rc;
+  return nice::set_alpha_merge_launch(stream, d.dec, d.stride, d.c_st, d_apacked, d.s_src, d.s_kind, d.s_win, d.s_idx,
+                                      d.ns, (const SetWindow*)d.head, M, tile_w, tile_h);
 }
 
 // ---- one image sharded over ranks ------------------------

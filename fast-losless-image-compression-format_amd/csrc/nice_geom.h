@@ -1,7 +1,8 @@
 // nice_geom.h -- the one definition of every constant and LDS layout that both
 // a kernel and the host's launch planning (nice_enc_plan.hpp, nice_dec_plan.hpp,
 // nice_capi.hip) depend on.  No HIP: a plain C++ compiler reads it too
-// (tests/test_enc_plan.py, tests/test_dec_plan.py).
+// (tests/test_enc_plan.py, tests/test_classify_routes.py, tests/test_dec_plan.py,
+// tests/test_dec_route.py; through nice_slot_plan.hpp, tests/test_slot_plan.py).
 #pragma once
 #include <stddef.h>
 #include <stdint.h>

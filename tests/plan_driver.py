@@ -1,5 +1,5 @@
-"""The launch planners on the CPU (tools/dec_plan_check.cpp and
-tools/enc_plan_check.cpp, built here with g++ once per session) and the
+"""The planners on the CPU (tools/dec_plan_check.cpp, tools/enc_plan_check.cpp
+and tools/slot_plan_check.cpp, built here with g++ once per session) and the
 library's reports of what it took (nice_test_last_dec_route,
 nice_test_last_classify), for the tests that compare the two."""
 import atexit
@@ -39,6 +39,10 @@ def exe():
 
 def enc_exe():
     return _build("enc_plan_check")
+
+
+def slot_exe():
+    return _build("slot_plan_check")
 
 
 def plan(w, h, n_frames, cus, **options):

@@ -526,6 +526,47 @@ def test_damaged_alpha_tile_fails_alone(nice, O, ctx):
     assert np.array_equal(got, want) and np.array_equal(e.value.out[1].cpu().numpy(), r.imgs[3])
 
 
+def test_nothing_left_to_decode(nice, O, ctx):
+    """Every tile's kind outside the format, in both batches ({100 x 70,
+    33 x 20} at 64 x 48, 5 tiles): decode_set's two passes and
+    decode_set_tensor refuse every slot on the host, nothing but the window
+    descriptors is uploaded, nothing is decoded, the outputs keep their poison,
+    the counters are zero, and the context then decodes the sound set exactly."""
+    import torch
+    from test_sets import last_set
+    shapes, tw, th, n = [(100, 70), (33, 20)], 64, 48, 5
+    rng = np.random.default_rng(6)
+    imgs = [rng.integers(0, 256, (h, w, 4), dtype=np.uint8) for w, h in shapes]
+    iset = nice.encode_set(_cuda(torch, imgs), tile=(tw, th), ctx=ctx, alpha=True)
+    assert iset.first == [0, 4, 5]
+    hurt = dataclasses.replace(iset, kind=torch.full((n,), 7, dtype=torch.uint8),
+                               alpha=dataclasses.replace(iset.alpha, kind=torch.full((n,), 3, dtype=torch.uint8)))
+    whole = [(i, 0, 0, w, h) for i, (w, h) in enumerate(shapes)]
+    for windows, m in ((whole, 5), ([(0, 60, 40, 30, 20), (1, 3, 2, 9, 11), (0, 60, 40, 30, 20)], 9), ([(1, 0, 0, 1, 1)], 1)):
+        outs = [torch.full((rh, rw, 4), POISON, dtype=torch.uint8, device="cuda") for _, _, _, rw, rh in windows]
+        nice.decode_set(iset, images=[1], ctx=ctx)                # (the counters start from a sound decode's)
+        assert sum(last_set(nice, ctx)) == 1 and sum(last_set_alpha(nice, ctx)) == 1
+        with pytest.raises(nice.NiceError) as e:
+            nice.decode_set(hurt, windows=windows, out=outs, ctx=ctx)
+        assert e.value.statuses == [E_FORMAT] * m and e.value.alpha_statuses == [E_FORMAT] * m
+        assert all(bool((o == POISON).all()) for o in outs)
+        assert last_set(nice, ctx) == (0, 0) and last_set_alpha(nice, ctx) == (0, 0, 0)
+        touts = [torch.full((3, rh, rw), -768.0, dtype=torch.float16, device="cuda") for _, _, _, rw, rh in windows]
+        nice.decode_set_tensor(iset, images=[1], ctx=ctx)
+        assert sum(last_set(nice, ctx)) == 1
+        with pytest.raises(nice.NiceError) as e:
+            nice.decode_set_tensor(hurt, windows=windows, out=touts, ctx=ctx)
+        assert e.value.statuses == [E_FORMAT] * m
+        assert all(bool((o == -768.0).all()) for o in touts)
+        assert last_set(nice, ctx) == (0, 0)
+    for got, im in zip(nice.decode_set(iset, ctx=ctx), imgs):
+        assert np.array_equal(got.cpu().numpy(), im)
+    assert sum(last_set(nice, ctx)) == n and sum(last_set_alpha(nice, ctx)) == n
+    scale = (1.0, 1.0, 1.0)
+    for got, im in zip(nice.decode_set_tensor(iset, dtype=torch.float32, scale=scale, ctx=ctx), imgs):
+        assert np.array_equal(got.cpu().numpy(), im[:, :, :3].transpose(2, 0, 1).astype(np.float32))
+
+
 # ---- 12. container and command line -------------------------------------------------------------------
 def test_container_round_trip(nice, O, ctx, tmp_path):
     import torch

@@ -411,6 +411,33 @@ def test_damaged_alpha_tile_fails_alone(nice, O, ctx):
     assert e.value.statuses == [0] * 8
 
 
+def test_nothing_left_to_decode(nice, O, ctx):
+    """Every tile's kind outside the format, in both batches (100 x 70 at
+    64 x 48, 4 tiles): both passes refuse every slot on the host, nothing is
+    uploaded or decoded, the output keeps its poison, the counters are zero,
+    and the context then decodes the sound image exactly."""
+    import torch
+    from test_tiled import last_tiled
+    w, h, tw, th, n = 100, 70, 64, 48, 4
+    img = np.random.default_rng(5).integers(0, 256, (h, w, 4), dtype=np.uint8)
+    timg = nice.encode_tiled(torch.from_numpy(img).cuda(), tile=(tw, th), ctx=ctx, alpha=True)
+    assert timg.kind.numel() == n
+    hurt = dataclasses.replace(timg, kind=torch.full((n,), 7, dtype=torch.uint8),
+                               alpha=dataclasses.replace(timg.alpha, kind=torch.full((n,), 3, dtype=torch.uint8)))
+    for roi, m in ((None, 4), ((60, 40, 30, 20), 4), ((70, 50, 20, 10), 1)):
+        rh, rw = (h, w) if roi is None else (roi[3], roi[2])
+        out = torch.full((rh, rw, 4), POISON, dtype=torch.uint8, device="cuda")
+        nice.decode_tiled(timg, roi=(0, 0, 1, 1), ctx=ctx)        # (the counters start from a sound decode's)
+        assert sum(last_tiled(nice, ctx)) == 1
+        with pytest.raises(nice.NiceError) as e:
+            nice.decode_tiled(hurt, roi=roi, out=out, ctx=ctx)
+        assert e.value.statuses == [nice.E_FORMAT] * m and e.value.alpha_statuses == [nice.E_FORMAT] * m
+        assert bool((out == POISON).all())
+        assert last_tiled(nice, ctx) == (0, 0)
+    assert np.array_equal(nice.decode_tiled(timg, ctx=ctx).cpu().numpy(), img)
+    assert sum(last_tiled(nice, ctx)) == n
+
+
 # ---- 5. the opaque image -----------------------------------------------------------
 def _timing(nice, ctx):
     L = nice.lib()
