@@ -94,93 +94,73 @@ def lib():
     except ImportError:
         pass
     L = ctypes.CDLL(LIB_PATH)
-    u8p = ctypes.c_void_p
-    sz = ctypes.c_size_t
-    u32 = ctypes.c_uint32
-    u64 = ctypes.c_uint64
-    L.nice_version.restype = ctypes.c_char_p
-    L.nice_encode_bound.restype = sz
-    L.nice_encode_bound.argtypes = [u32, u32]
-    L.nice_encode.argtypes = [u8p, sz, u32, u32, ctypes.c_uint8, ctypes.c_uint8, u8p, sz,
-                              ctypes.POINTER(sz)]
-    L.nice_peek_header.argtypes = [u8p, sz, ctypes.POINTER(u32), ctypes.POINTER(u32),
-                                   ctypes.POINTER(ctypes.c_uint8)]
-    L.nice_decode.argtypes = [u8p, sz, u8p, sz, u32, ctypes.POINTER(sz)]
-    L.nice_ctx_create.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]
-    L.nice_ctx_destroy.argtypes = [ctypes.c_void_p]
-    L.nice_ctx_reserve.argtypes = [ctypes.c_void_p, u32, u32, u32]
-    L.nice_encode_batch_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, u8p, u64, u32, u32, u32,
-                                        ctypes.c_uint8, ctypes.c_uint8, u8p, u64, u8p]
-    L.nice_decode_batch_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, u8p, u64, u8p, u32, u32,
-                                        u32, ctypes.c_uint8, u8p, u64, u32, u8p]
-    L.nice_decode_batch_dev_hl.argtypes = [ctypes.c_void_p, ctypes.c_void_p, u8p, u64, u8p, ctypes.c_void_p, u32,
-                                           u32, u32, ctypes.c_uint8, u8p, u64, u32, u8p]
-    L.nice_packed_bound.restype = u64
-    L.nice_packed_bound.argtypes = [u32, u32, u32]
-    L.nice_pack_streams_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, u8p, u64, u8p, u32, u8p, u64, u8p, u8p]
-    L.nice_encode_batch_packed_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, u8p, u64, u32, u32, u32,
-                                               ctypes.c_uint8, ctypes.c_uint8, u8p, u64, u8p, u8p, u8p]
-    L.nice_decode_packed_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, u8p, u64, u8p, u8p, ctypes.c_void_p,
-                                         u32, u32, u32, ctypes.c_uint8, u8p, u64, u32, u8p]
-    u8 = ctypes.c_uint8
-    u32p = ctypes.POINTER(u32)
-    L.nice_tile_grid.argtypes = [u32, u32, u32, u32, u32p, u32p]
-    L.nice_tiled_bound.restype = u64
-    L.nice_tiled_bound.argtypes = [u32, u32, u32, u32]
-    L.nice_tile_select.argtypes = [u32] * 8 + [u32p] * 4
-    L.nice_tiles_split_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, u8p, u64, u32, u32, u8, u32, u32, u8p, u64]
-    L.nice_tiles_merge_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, u8p, u64, u8p, u32, u8, u32, u32, u32, u32,
-                                       u32, u32, u32, u32, u8, u8, u8p, u64]
-    L.nice_encode_tiled_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, u8p, u64, u32, u32, u8, u8, u32, u32, u8p,
-                                        u64, u8p, u8p, u8p, u8p]
-    L.nice_decode_tiled_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, u8p, u64, ctypes.c_void_p, ctypes.c_void_p,
-                                        ctypes.c_void_p, u32, u32, u32, u32, u32, u32, u32, u32, u8, u8p, u64, u32,
-                                        u8p]
-    L.nice_tile_alpha_width.restype = u32
-    L.nice_tile_alpha_width.argtypes = [u32]
-    L.nice_tiled_alpha_bound.restype = u64
-    L.nice_tiled_alpha_bound.argtypes = [u32, u32, u32, u32]
-    L.nice_tiles_alpha_range_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, u8p, u64, u32, u32, u32, u32, u8p, u8p]
-    L.nice_encode_tiled_alpha_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, u8p, u64, u32, u32, u32, u32, u8p, u64,
-                                              u8p, u8p, u8p, u8p, u8p]
-    L.nice_decode_tiled_alpha_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, u8p, u64, ctypes.c_void_p,
-                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, u32, u32, u32, u32, u32,
-                                              u32, u32, u32, u8p, u64, u8p]
-    vp = ctypes.c_void_p
-    L.nice_set_grid.argtypes = [vp, vp, u32, u32, u32, vp]
-    L.nice_set_bound.restype = u64
-    L.nice_set_bound.argtypes = [vp, vp, u32, u32, u32]
-    L.nice_set_select.argtypes = [vp, vp, u32, u32, u32, vp, u32, vp]
-    L.nice_set_split_dev.argtypes = [vp, vp, vp, vp, vp, vp, u32, u8, u32, u32, u8p, u64]
-    L.nice_set_merge_dev.argtypes = [vp, vp, u8p, u64, vp, vp, vp, vp, u32, u8, vp, vp, u32, u32, u32, vp, vp, vp, u32,
-                                     u8, u8]
-    L.nice_encode_set_dev.argtypes = [vp, vp, vp, vp, vp, vp, u32, u8, u8, u32, u32, u8p, u64, u8p, u8p, u8p, u8p]
-    L.nice_decode_set_dev.argtypes = [vp, vp, u8p, u64, vp, vp, vp, vp, vp, u32, u32, u32, vp, vp, vp, u32, u8, u32,
-                                      u8p]
-    L.nice_set_alpha_bound.restype = u64
-    L.nice_set_alpha_bound.argtypes = [vp, vp, u32, u32, u32]
-    L.nice_set_alpha_range_dev.argtypes = [vp, vp, vp, vp, vp, vp, u32, u32, u32, u8p, u8p]
-    L.nice_encode_set_alpha_dev.argtypes = [vp, vp, vp, vp, vp, vp, u32, u32, u32, u8p, u64, u8p, u8p, u8p, u8p, u8p]
-    L.nice_decode_set_alpha_dev.argtypes = [vp, vp, u8p, u64, vp, vp, vp, vp, vp, vp, u32, u32, u32, vp, vp, vp, u32,
-                                            u8p]
-    L.nice_set_merge_tensor_dev.argtypes = [vp, vp, u8p, u64, vp, vp, vp, vp, u32, u8, vp, vp, u32, u32, u32, vp, vp, vp,
-                                            vp, vp, u32, u32, u32, vp, vp]
-    L.nice_decode_set_tensor_dev.argtypes = [vp, vp, u8p, u64, vp, vp, vp, vp, vp, u32, u32, u32, vp, vp, vp, vp, vp, u32,
-                                             u32, u32, vp, vp, u32, u8p]
-    L.nice_pipe_create.argtypes = [ctypes.c_int, u32, u32, ctypes.c_uint8, u32, u32,
-                                   ctypes.POINTER(ctypes.c_void_p)]
-    L.nice_pipe_destroy.argtypes = [ctypes.c_void_p]
-    L.nice_pipe_stream_stride.restype = u64
-    L.nice_pipe_stream_stride.argtypes = [ctypes.c_void_p]
-    L.nice_pipe_encode.argtypes = [ctypes.c_void_p, ctypes.c_void_p, u32, ctypes.c_uint8,
-                                   ctypes.c_void_p, u64, ctypes.c_void_p]
-    L.nice_pipe_decode.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, u32,
-                                   ctypes.c_uint8, ctypes.c_void_p, u32, ctypes.c_void_p]
-    L.nice_pipe_set_checksums.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
-    L.nice_subblock_positions_dev.argtypes = [ctypes.c_int, ctypes.c_void_p, u32, u32, u64, u64,
-                                              ctypes.c_void_p]
+    for name, (restype, argtypes) in _signatures().items():
+        fn = getattr(L, name)
+        fn.restype = restype
+        if argtypes is not None:
+            fn.argtypes = argtypes
     _lib = L
     return L
+
+
+def _signatures():
+    """{entry point: (restype, argtypes)} of what this module calls, as
+    include/nice.h declares it (tests/test_abi.py holds each against its
+    prototype); ``argtypes`` None: no parameters."""
+    i, z, u8, u32, u64, p = (ctypes.c_int, ctypes.c_size_t, ctypes.c_uint8, ctypes.c_uint32, ctypes.c_uint64,
+                             ctypes.c_void_p)
+    pz, pu8, pu32, pp = ctypes.POINTER(z), ctypes.POINTER(u8), ctypes.POINTER(u32), ctypes.POINTER(p)
+    return {
+        "nice_version": (ctypes.c_char_p, None),
+        "nice_encode_bound": (z, [u32, u32]),
+        "nice_encode": (i, [p, z, u32, u32, u8, u8, p, z, pz]),
+        "nice_peek_header": (i, [p, z, pu32, pu32, pu8]),
+        "nice_decode": (i, [p, z, p, z, u32, pz]),
+        "nice_ctx_create": (i, [i, pp]),
+        "nice_ctx_destroy": (None, [p]),
+        "nice_ctx_reserve": (i, [p, u32, u32, u32]),
+        "nice_encode_batch_dev": (i, [p, p, p, u64, u32, u32, u32, u8, u8, p, u64, p]),
+        "nice_decode_batch_dev": (i, [p, p, p, u64, p, u32, u32, u32, u8, p, u64, u32, p]),
+        "nice_decode_batch_dev_hl": (i, [p, p, p, u64, p, p, u32, u32, u32, u8, p, u64, u32, p]),
+        "nice_packed_bound": (u64, [u32, u32, u32]),
+        "nice_pack_streams_dev": (i, [p, p, p, u64, p, u32, p, u64, p, p]),
+        "nice_encode_batch_packed_dev": (i, [p, p, p, u64, u32, u32, u32, u8, u8, p, u64, p, p, p]),
+        "nice_decode_packed_dev": (i, [p, p, p, u64, p, p, p, u32, u32, u32, u8, p, u64, u32, p]),
+        "nice_tile_grid": (i, [u32, u32, u32, u32, pu32, pu32]),
+        "nice_tiled_bound": (u64, [u32] * 4),
+        "nice_tile_select": (i, [u32] * 8 + [pu32] * 4),
+        "nice_tiles_split_dev": (i, [p, p, p, u64, u32, u32, u8, u32, u32, p, u64]),
+        "nice_tiles_merge_dev": (i, [p, p, p, u64, p, u32, u8] + [u32] * 8 + [u8, u8, p, u64]),
+        "nice_encode_tiled_dev": (i, [p, p, p, u64, u32, u32, u8, u8, u32, u32, p, u64, p, p, p, p]),
+        "nice_decode_tiled_dev": (i, [p, p, p, u64, p, p, p] + [u32] * 8 + [u8, p, u64, u32, p]),
+        "nice_tile_alpha_width": (u32, [u32]),
+        "nice_tiled_alpha_bound": (u64, [u32] * 4),
+        "nice_tiles_alpha_range_dev": (i, [p, p, p, u64, u32, u32, u32, u32, p, p]),
+        "nice_encode_tiled_alpha_dev": (i, [p, p, p, u64, u32, u32, u32, u32, p, u64, p, p, p, p, p]),
+        "nice_decode_tiled_alpha_dev": (i, [p, p, p, u64, p, p, p, p] + [u32] * 8 + [p, u64, p]),
+        "nice_set_grid": (i, [p, p, u32, u32, u32, p]),
+        "nice_set_bound": (u64, [p, p, u32, u32, u32]),
+        "nice_set_select": (i, [p, p, u32, u32, u32, p, u32, p]),
+        "nice_set_split_dev": (i, [p, p, p, p, p, p, u32, u8, u32, u32, p, u64]),
+        "nice_set_merge_dev": (i, [p, p, p, u64, p, p, p, p, u32, u8, p, p, u32, u32, u32, p, p, p, u32, u8, u8]),
+        "nice_encode_set_dev": (i, [p, p, p, p, p, p, u32, u8, u8, u32, u32, p, u64, p, p, p, p]),
+        "nice_decode_set_dev": (i, [p, p, p, u64, p, p, p, p, p, u32, u32, u32, p, p, p, u32, u8, u32, p]),
+        "nice_set_alpha_bound": (u64, [p, p, u32, u32, u32]),
+        "nice_set_alpha_range_dev": (i, [p, p, p, p, p, p, u32, u32, u32, p, p]),
+        "nice_encode_set_alpha_dev": (i, [p, p, p, p, p, p, u32, u32, u32, p, u64, p, p, p, p, p]),
+        "nice_decode_set_alpha_dev": (i, [p, p, p, u64, p, p, p, p, p, p, u32, u32, u32, p, p, p, u32, p]),
+        "nice_set_merge_tensor_dev": (i, [p, p, p, u64, p, p, p, p, u32, u8, p, p, u32, u32, u32, p, p, p, p, p, u32,
+                                          u32, u32, p, p]),
+        "nice_decode_set_tensor_dev": (i, [p, p, p, u64, p, p, p, p, p, u32, u32, u32, p, p, p, p, p, u32, u32, u32, p,
+                                           p, u32, p]),
+        "nice_pipe_create": (i, [i, u32, u32, u8, u32, u32, pp]),
+        "nice_pipe_destroy": (None, [p]),
+        "nice_pipe_stream_stride": (u64, [p]),
+        "nice_pipe_encode": (i, [p, p, u32, u8, p, u64, p]),
+        "nice_pipe_decode": (i, [p, p, p, u32, u8, p, u32, p]),
+        "nice_pipe_set_checksums": (i, [p, p, p]),
+        "nice_subblock_positions_dev": (i, [i, p, u32, u32, u64, u64, p]),
+    }
 
 
 def _check(rc: int, what: str):
@@ -210,7 +190,7 @@ class Image:
         if out.numel() < n or out.dtype != torch.int64 or not out.is_contiguous():
             raise NiceError(E_ARG, "out: contiguous int64 with >= count elements")
         rc = lib().nice_subblock_positions_dev(device, _stream_ptr(torch, out.device), self.width, self.height,
-                                               index0, n, ctypes.c_void_p(out.data_ptr()))
+                                               index0, n, _p(out))
         _check(rc, "nice_subblock_positions_dev")
         return out
 
@@ -310,6 +290,29 @@ def _stream_ptr(torch, device):
     return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
+def _stream_of(torch, stream, device):
+    return ctypes.c_void_p(stream.cuda_stream) if stream is not None else _stream_ptr(torch, device)
+
+
+def _p(t):
+    """The address a tensor's data begins at, as the C ABI takes it."""
+    return ctypes.c_void_p(t.data_ptr())
+
+
+def _launch(torch, device, stream, ctx):
+    """(context, stream): what every device entry point's arguments begin with."""
+    return (ctx or _ctx(device.index or 0)).ptr, _stream_of(torch, stream, device)
+
+
+def _host_len(host_len, n: int):
+    """``host_len`` (n lengths on the host) as the uint64 array the C ABI reads;
+    never an empty one."""
+    hl = [int(x) for x in host_len]
+    if len(hl) != n:   # a short list would be zero padded: lengths the device does not hold
+        raise NiceError(E_ARG, f"host_len has {len(hl)} entries for {n} frames")
+    return ctypes.cast((ctypes.c_uint64 * max(n, 1))(*hl), ctypes.c_void_p)
+
+
 class Context(_Ctx):
     """A device context with its own scratch arena: calls on different torch
     streams need different contexts to run concurrently."""
@@ -322,13 +325,9 @@ def encode_batch(px, width: int, height: int, channels: int, out, out_len,
     ``out_len`` (int64 cuda tensor [n_frames]).  Asynchronous on the current
     torch stream (or ``stream``: a torch.cuda.Stream)."""
     import torch
-    dev = px.device.index or 0
-    n = px.shape[0]
-    st = ctypes.c_void_p(stream.cuda_stream) if stream is not None else _stream_ptr(torch, px.device)
     rc = lib().nice_encode_batch_dev(
-        (ctx or _ctx(dev)).ptr, st, ctypes.c_void_p(px.data_ptr()), px.stride(0), n, width, height,
-        channels, channels if channels_out is None else channels_out,
-        ctypes.c_void_p(out.data_ptr()), out.stride(0), ctypes.c_void_p(out_len.data_ptr()))
+        *_launch(torch, px.device, stream, ctx), _p(px), px.stride(0), px.shape[0], width, height,
+        channels, channels if channels_out is None else channels_out, _p(out), out.stride(0), _p(out_len))
     _check(rc, "nice_encode_batch_dev")
 
 
@@ -342,21 +341,13 @@ def decode_batch(streams, stream_len, width: int, height: int, out_channels: int
     numpy array or CPU tensor) spares the call its one device read (the lengths
     size the scratch), so it never waits for earlier work on the stream."""
     import torch
-    dev = streams.device.index or 0
     n = streams.shape[0]
-    st = ctypes.c_void_p(stream.cuda_stream) if stream is not None else _stream_ptr(torch, streams.device)
-    args = ((ctx or _ctx(dev)).ptr, st, ctypes.c_void_p(streams.data_ptr()), streams.stride(0),
-            ctypes.c_void_p(stream_len.data_ptr()))
-    tail = (n, width, height, out_channels, ctypes.c_void_p(px.data_ptr()), px.stride(0), flags,
-            ctypes.c_void_p(status.data_ptr()))
+    args = (*_launch(torch, streams.device, stream, ctx), _p(streams), streams.stride(0), _p(stream_len))
+    tail = (n, width, height, out_channels, _p(px), px.stride(0), flags, _p(status))
     if host_len is None:
         rc = lib().nice_decode_batch_dev(*args, *tail)
     else:
-        hl_list = [int(x) for x in host_len]
-        if len(hl_list) != n:   # a short list would be zero padded: lengths the device does not hold
-            raise NiceError(E_ARG, f"host_len has {len(hl_list)} entries for {n} frames")
-        hl = (ctypes.c_uint64 * n)(*hl_list)
-        rc = lib().nice_decode_batch_dev_hl(*args, ctypes.cast(hl, ctypes.c_void_p), *tail)
+        rc = lib().nice_decode_batch_dev_hl(*args, _host_len(host_len, n), *tail)
     _check(rc, "nice_decode_batch_dev")
 
 
@@ -364,10 +355,6 @@ def decode_batch(streams, stream_len, width: int, height: int, out_channels: int
 def packed_bound(n_frames: int, width: int, height: int) -> int:
     """Worst-case size of a packed batch of ``n_frames`` width x height streams."""
     return int(lib().nice_packed_bound(n_frames, width, height))
-
-
-def _stream_of(torch, stream, device):
-    return ctypes.c_void_p(stream.cuda_stream) if stream is not None else _stream_ptr(torch, device)
 
 
 def pack_streams(streams, stream_len, packed, off, status, stream=None, ctx: "_Ctx | None" = None) -> None:
@@ -379,15 +366,12 @@ def pack_streams(streams, stream_len, packed, off, status, stream=None, ctx: "_C
     ``packed.numel()``; nothing is written past it) or E_ARG (a length above
     the stride).  Asynchronous, never waits for the device."""
     import torch
-    dev = streams.device.index or 0
     n = streams.shape[0]
     if stream_len.numel() < n or off.numel() < n + 1:
         raise NiceError(E_ARG, "pack_streams: stream_len needs n entries, off n + 1")
     rc = lib().nice_pack_streams_dev(
-        (ctx or _ctx(dev)).ptr, _stream_of(torch, stream, streams.device), ctypes.c_void_p(streams.data_ptr()),
-        streams.stride(0), ctypes.c_void_p(stream_len.data_ptr()), n,
-        ctypes.c_void_p(packed.data_ptr()), packed.numel(), ctypes.c_void_p(off.data_ptr()),
-        ctypes.c_void_p(status.data_ptr()))
+        *_launch(torch, streams.device, stream, ctx), _p(streams), streams.stride(0), _p(stream_len), n,
+        _p(packed), packed.numel(), _p(off), _p(status))
     _check(rc, "nice_pack_streams_dev")
 
 
@@ -400,15 +384,13 @@ def encode_batch_packed(px, width: int, height: int, channels: int, packed, off,
     ``packed_bound(n, width, height)`` bytes always suffice; a smaller buffer
     gives E_CAPACITY in ``status`` and the needed size in ``off[n]``."""
     import torch
-    dev = px.device.index or 0
     n = px.shape[0]
     if out_len.numel() < n or off.numel() < n + 1:
         raise NiceError(E_ARG, "encode_batch_packed: out_len needs n entries, off n + 1")
     rc = lib().nice_encode_batch_packed_dev(
-        (ctx or _ctx(dev)).ptr, _stream_of(torch, stream, px.device), ctypes.c_void_p(px.data_ptr()), px.stride(0),
-        n, width, height, channels, channels if channels_out is None else channels_out,
-        ctypes.c_void_p(packed.data_ptr()), packed.numel(), ctypes.c_void_p(off.data_ptr()),
-        ctypes.c_void_p(out_len.data_ptr()), ctypes.c_void_p(status.data_ptr()))
+        *_launch(torch, px.device, stream, ctx), _p(px), px.stride(0), n, width, height, channels,
+        channels if channels_out is None else channels_out, _p(packed), packed.numel(), _p(off), _p(out_len),
+        _p(status))
     _check(rc, "nice_encode_batch_packed_dev")
 
 
@@ -424,7 +406,6 @@ def decode_batch_packed(packed, off, stream_len, width: int, height: int, out_ch
     or with an offset that is not a multiple of 16 gets E_ARG in ``status``
     (int32 cuda [n]), the others decode.  ``host_len`` as for ``decode_batch``."""
     import torch
-    dev = packed.device.index or 0
     n = stream_len.numel()
     if off.numel() < n or status.numel() < n:
         raise NiceError(E_ARG, "decode_batch_packed: off and status need one entry per frame")
@@ -433,16 +414,10 @@ def decode_batch_packed(packed, off, stream_len, width: int, height: int, out_ch
     pb = packed.numel() if packed_bytes is None else int(packed_bytes)
     if pb > packed.numel():
         raise NiceError(E_ARG, "decode_batch_packed: packed_bytes exceeds the buffer")
-    hl = None
-    if host_len is not None:
-        hl_list = [int(x) for x in host_len]
-        if len(hl_list) != n:
-            raise NiceError(E_ARG, f"host_len has {len(hl_list)} entries for {n} frames")
-        hl = ctypes.cast((ctypes.c_uint64 * max(n, 1))(*hl_list), ctypes.c_void_p)
+    hl = None if host_len is None else _host_len(host_len, n)   # (null: the lengths are read from the device)
     rc = lib().nice_decode_packed_dev(
-        (ctx or _ctx(dev)).ptr, _stream_of(torch, stream, packed.device), ctypes.c_void_p(packed.data_ptr()), pb,
-        ctypes.c_void_p(off.data_ptr()), ctypes.c_void_p(stream_len.data_ptr()), hl, n, width, height,
-        out_channels, ctypes.c_void_p(px.data_ptr()), px.stride(0), flags, ctypes.c_void_p(status.data_ptr()))
+        *_launch(torch, packed.device, stream, ctx), _p(packed), pb, _p(off), _p(stream_len), hl, n, width, height,
+        out_channels, _p(px), px.stride(0), flags, _p(status))
     _check(rc, "nice_decode_packed_dev")
 
 
@@ -455,25 +430,80 @@ _PACK_VERSION = 1
 _PACK_HEADER = "<8sIIIIIIQ"
 
 
+def _batch_chunks(who: str, packed, off, stream_len, kind=None, value=None, n=None, pre=""):
+    """One batch as every container stores it: ``(n, size, chunks)``, ``size``
+    being ``off[n]`` and ``chunks`` the byte strings to write: n x u64 lengths,
+    (n + 1) x u64 offsets, n x u8 kinds and n x u8 values where the batch has
+    them, each zero-padded to a multiple of 8 bytes, then ``packed[:size]`` (one
+    device-to-host copy).  ``n``: the entries the tables must have (default: as
+    many as there are lengths).  ``pre`` ("alpha " or none) words the refusals
+    (NiceError(E_ARG), in ``who``'s name)."""
+    import numpy as np
+    lens, offs = (np.asarray(t.detach().cpu().numpy(), dtype=np.int64).reshape(-1) for t in (stream_len, off))
+    bytes_ = [np.asarray(t.detach().cpu().numpy(), dtype=np.uint8).reshape(-1) for t in (kind, value) if t is not None]
+    n = lens.size if n is None else n
+    if lens.size != n or offs.size != n + 1 or any(t.size != n for t in bytes_):
+        raise NiceError(E_ARG, f"{who}: {pre}tables do not match: off has {offs.size} entries for {n} "
+                               f"{'tiles' if bytes_ else 'streams'}")
+    size = int(offs[n])
+    if size < 0 or size > packed.numel():
+        raise NiceError(E_ARG, f"{who}: {pre}off[n] exceeds the {pre}packed buffer")
+    blob = packed.detach().reshape(-1)[:size].cpu().numpy()
+    return n, size, ([lens.astype("<u8").tobytes(), offs.astype("<u8").tobytes()]
+                     + [t.tobytes() + bytes(-n % 8) for t in bytes_] + [blob.tobytes()])
+
+
+def _read_batch(fh, bad, n: int, size: int, max_kind=None, raw_len: int = 0, pre="", device=None):
+    """Reads one batch of a container, written as by ``_batch_chunks`` (the
+    file's size has been checked against ``n`` and ``size``), and validates
+    it: the offsets 16-byte aligned from 0 to ``size``, monotone, no stream
+    running into the next; the kinds (read where ``max_kind`` is given) at most
+    ``max_kind`` and their padding zero; a raw tile (kind 1) of ``raw_len``
+    bytes; with ``max_kind`` 2 the values are read too, a constant tile (kind
+    2) has no bytes and only a constant tile a value; nothing truncated.
+    ``bad(why)`` makes the error, ``pre`` ("alpha " or none) words it.  Returns
+    (packed, off, stream_len[, kind[, value]]): uint8 ``packed`` on ``device``
+    (None: the CPU), the tables as int64 / int64 / uint8 / uint8 CPU tensors."""
+    import numpy as np
+    import torch
+    kpad = n + (-n % 8)
+    lens = np.frombuffer(fh.read(8 * n), "<u8")
+    offs = np.frombuffer(fh.read(8 * (n + 1)), "<u8")
+    bytes_ = [np.frombuffer(fh.read(kpad), np.uint8) for _ in range((max_kind is not None) + (max_kind == 2))]
+    if lens.size != n or offs.size != n + 1 or any(t.size != kpad for t in bytes_):
+        raise bad("truncated")
+    if offs[0] != 0 or offs[n] != size or (offs % 16).any():
+        raise bad(f"{pre}offsets not 16-byte aligned from 0 to the {pre}packed size")
+    if (offs[1:] < offs[:-1]).any():
+        raise bad(f"{pre}offsets not monotone")
+    if (lens > offs[1:] - offs[:-1]).any():
+        raise bad(f"one of the {pre}streams overlaps the next")
+    if bytes_:
+        kinds = bytes_[0][:n]
+        if any(t[n:].any() for t in bytes_) or (kinds > max_kind).any():
+            raise bad(f"{pre}tile kinds")
+        if (lens[kinds == 1] != raw_len).any():
+            raise bad(f"raw {pre}tile length")
+        if max_kind == 2 and (lens[kinds == 2] != 0).any():
+            raise bad(f"constant {pre}tile with a length")
+        if max_kind == 2 and bytes_[1][:n][kinds != 2].any():
+            raise bad(f"{pre}value of a tile that is not constant")
+    blob = np.frombuffer(fh.read(size), np.uint8)
+    if blob.size != size:
+        raise bad("truncated")
+    packed = torch.from_numpy(blob.copy())
+    return (packed if device is None else packed.to(device), torch.from_numpy(offs.astype(np.int64)),
+            torch.from_numpy(lens.astype(np.int64)), *[torch.from_numpy(t[:n].copy()) for t in bytes_])
+
+
 def save_packed(path, packed, off, stream_len, width: int, height: int, channels: int) -> None:
     """Write a packed batch (tensors on the GPU or the CPU) to ``path``: one
     device-to-host copy of ``packed[:off[n]]``."""
     import struct
-    import numpy as np
-    lens = np.asarray(stream_len.detach().cpu().numpy(), dtype=np.int64).reshape(-1)
-    n = lens.size
-    offs = np.asarray(off.detach().cpu().numpy(), dtype=np.int64).reshape(-1)
-    if offs.size != n + 1:
-        raise NiceError(E_ARG, f"save_packed: off has {offs.size} entries for {n} streams")
-    size = int(offs[n])
-    if size < 0 or size > packed.numel():
-        raise NiceError(E_ARG, "save_packed: off[n] exceeds the packed buffer")
-    blob = packed.detach().reshape(-1)[:size].cpu().numpy()
+    n, size, chunks = _batch_chunks("save_packed", packed, off, stream_len)
     with open(path, "wb") as fh:
         fh.write(struct.pack(_PACK_HEADER, _PACK_MAGIC, _PACK_VERSION, n, width, height, channels, 0, size))
-        fh.write(lens.astype("<u8").tobytes())
-        fh.write(offs.astype("<u8").tobytes())
-        fh.write(blob.tobytes())
+        fh.writelines(chunks)
 
 
 def load_packed(path, device=None):
@@ -483,8 +513,6 @@ def load_packed(path, device=None):
     GPU needed).  A file that is not a consistent packed batch raises
     NiceError(E_FORMAT)."""
     import struct
-    import numpy as np
-    import torch
 
     def bad(why):
         return NiceError(E_FORMAT, f"load_packed({path}): {why}")
@@ -504,22 +532,9 @@ def load_packed(path, device=None):
             raise bad("packed size")
         if fsize != hsz + 8 * n + 8 * (n + 1) + size:
             raise bad("file size does not match the header")
-        lens = np.frombuffer(fh.read(8 * n), "<u8")
-        offs = np.frombuffer(fh.read(8 * (n + 1)), "<u8")
-        if offs[0] != 0 or offs[n] != size or (offs % 16).any():
-            raise bad("offsets not 16-byte aligned from 0 to the packed size")
-        if (offs[1:] < offs[:-1]).any():
-            raise bad("offsets not monotone")
-        if (lens > offs[1:] - offs[:-1]).any():
-            raise bad("a stream overlaps the next")
-        blob = np.frombuffer(fh.read(size), np.uint8)
-        if blob.size != size:
-            raise bad("truncated")
-    packed = torch.from_numpy(blob.copy())
-    off = torch.from_numpy(offs.astype(np.int64))
-    stream_len = torch.from_numpy(lens.astype(np.int64))
+        packed, off, stream_len = _read_batch(fh, bad, n, size, device=device)
     if device is not None:
-        packed, off, stream_len = packed.to(device), off.to(device), stream_len.to(device)
+        off, stream_len = off.to(device), stream_len.to(device)
     return packed, off, stream_len, width, height, channels
 
 
@@ -625,27 +640,38 @@ def tiled_alpha_bound(width: int, height: int, tile_w: int, tile_h: int) -> int:
     return int(lib().nice_tiled_alpha_bound(width, height, tile_w, tile_h))
 
 
+def _encode_tables(torch, n: int, dev, value: bool = False):
+    """``(tables, status)`` for a tiled or set encode to fill on ``dev``: the
+    tables are off (n + 1, int64), stream_len (n, int64), kind (n, uint8) and,
+    for an alpha batch, value (n, uint8); ``status`` is the int32 word."""
+    tables = [torch.empty(n + 1, dtype=torch.int64, device=dev), torch.empty(n, dtype=torch.int64, device=dev)]
+    tables += [torch.empty(n, dtype=torch.uint8, device=dev) for _ in range(2 if value else 1)]
+    return tables, torch.full((1,), 99, dtype=torch.int32, device=dev)
+
+
+def _encode_tail(rc: int, what: str, stream, status, packed, tables, n: int):
+    """What follows the launch of a tiled or set encode: the call's and, after
+    the wait, the device's verdict in ``what``'s name, then the tables to the
+    host.  Returns ``packed[:off[n]]`` (a view) and the host tables, in the
+    order the dataclasses take them."""
+    _check(rc, what)
+    if stream is not None:
+        stream.synchronize()
+    _check(int(status.cpu()[0]), what)
+    host = [t.cpu() for t in tables]
+    return (packed[:int(host[0][n])], *host)
+
+
 def _encode_tiled_alpha(torch, img, pitch, tw, th, n, stream, ctx) -> TiledAlpha:
     h, w, _ = img.shape
     dev = img.device
     packed = torch.empty(tiled_alpha_bound(w, h, tw, th), dtype=torch.uint8, device=dev)
-    off = torch.empty(n + 1, dtype=torch.int64, device=dev)
-    lens = torch.empty(n, dtype=torch.int64, device=dev)
-    kind = torch.empty(n, dtype=torch.uint8, device=dev)
-    val = torch.empty(n, dtype=torch.uint8, device=dev)
-    status = torch.full((1,), 99, dtype=torch.int32, device=dev)
-    rc = lib().nice_encode_tiled_alpha_dev(
-        (ctx or _ctx(dev.index or 0)).ptr, _stream_of(torch, stream, dev), ctypes.c_void_p(img.data_ptr()), pitch,
-        w, h, tw, th, ctypes.c_void_p(packed.data_ptr()), packed.numel(), ctypes.c_void_p(off.data_ptr()),
-        ctypes.c_void_p(lens.data_ptr()), ctypes.c_void_p(kind.data_ptr()), ctypes.c_void_p(val.data_ptr()),
-        ctypes.c_void_p(status.data_ptr()))
-    _check(rc, "nice_encode_tiled_alpha_dev")
-    if stream is not None:
-        stream.synchronize()
-    _check(int(status.cpu()[0]), "nice_encode_tiled_alpha_dev")
-    off_h = off.cpu()
+    tables, status = _encode_tables(torch, n, dev, value=True)
+    rc = lib().nice_encode_tiled_alpha_dev(*_launch(torch, dev, stream, ctx), _p(img), pitch, w, h, tw, th, _p(packed),
+                                           packed.numel(), *map(_p, tables), _p(status))
+    trimmed, *host = _encode_tail(rc, "nice_encode_tiled_alpha_dev", stream, status, packed, tables, n)
     # (a copy: the alpha of a mostly opaque image is far smaller than its bound)
-    return TiledAlpha(packed[:int(off_h[n])].clone(), off_h, lens.cpu(), kind.cpu(), val.cpu())
+    return TiledAlpha(trimmed.clone(), *host)
 
 
 def encode_tiled(img, tile=None, channels_out: int | None = None, stream=None, ctx: "_Ctx | None" = None,
@@ -672,24 +698,62 @@ def encode_tiled(img, tile=None, channels_out: int | None = None, stream=None, c
     dev = img.device
     if packed is None:
         packed = torch.empty(tiled_bound(w, h, tw, th), dtype=torch.uint8, device=dev)
-    off = torch.empty(n + 1, dtype=torch.int64, device=dev)
-    lens = torch.empty(n, dtype=torch.int64, device=dev)
-    kind = torch.empty(n, dtype=torch.uint8, device=dev)
-    status = torch.full((1,), 99, dtype=torch.int32, device=dev)
+    tables, status = _encode_tables(torch, n, dev)
     rc = lib().nice_encode_tiled_dev(
-        (ctx or _ctx(dev.index or 0)).ptr, _stream_of(torch, stream, dev), ctypes.c_void_p(img.data_ptr()), pitch,
-        w, h, c, c if channels_out is None else channels_out, tw, th, ctypes.c_void_p(packed.data_ptr()),
-        packed.numel(), ctypes.c_void_p(off.data_ptr()), ctypes.c_void_p(lens.data_ptr()),
-        ctypes.c_void_p(kind.data_ptr()), ctypes.c_void_p(status.data_ptr()))
-    _check(rc, "nice_encode_tiled_dev")
-    if stream is not None:
-        stream.synchronize()
-    _check(int(status.cpu()[0]), "nice_encode_tiled_dev")
-    off_h = off.cpu()
-    timg = TiledImage(w, h, c, tw, th, packed[:int(off_h[n])], off_h, lens.cpu(), kind.cpu())
+        *_launch(torch, dev, stream, ctx), _p(img), pitch, w, h, c, c if channels_out is None else channels_out, tw, th,
+        _p(packed), packed.numel(), *map(_p, tables), _p(status))
+    timg = TiledImage(w, h, c, tw, th, *_encode_tail(rc, "nice_encode_tiled_dev", stream, status, packed, tables, n))
     if alpha:
         timg.alpha = _encode_tiled_alpha(torch, img, pitch, tw, th, n, stream, ctx)
     return timg
+
+
+def _host_tables(torch, who: str, batch, n: int, colour_dev=None):
+    """The tables of ``batch`` (a TiledImage or an ImageSet, or, with
+    ``colour_dev`` the device of the colour batch, its TiledAlpha) as the
+    contiguous CPU tensors a decode reads: [off, stream_len, kind], and value
+    for an alpha batch.  They must fit the ``n`` tiles and ``batch.packed``,
+    which must be on the GPU, an alpha batch's on ``colour_dev``; else
+    NiceError(E_ARG) in the name of ``who``, the public function."""
+    alpha = colour_dev is not None
+    if not batch.packed.is_cuda or (alpha and batch.packed.device != colour_dev):
+        raise NiceError(E_ARG, f"{who}: alpha.packed must be on the GPU, with the colour packed" if alpha else
+                        f"{who}: packed must be on the GPU (load_tiled / load_set(path, device=...))")
+    tables = [batch.off.to("cpu", torch.int64).contiguous(), batch.stream_len.to("cpu", torch.int64).contiguous(),
+              batch.kind.to("cpu", torch.uint8).contiguous()]
+    if alpha:
+        tables.append(batch.value.to("cpu", torch.uint8).contiguous())
+    if (tables[0].numel() < n + 1 or any(t.numel() != n for t in tables[1:])
+            or int(tables[0][n]) > batch.packed.numel()):
+        raise NiceError(E_ARG, f"{who}: {'alpha ' if alpha else ''}tables do not match the {n} tiles")
+    return tables
+
+
+def _alpha_packed(al: TiledAlpha, tables, n: int):
+    """(address, bytes) of an alpha batch's packed bytes: null and 0 where every tile is constant."""
+    size = int(tables[0][n])
+    return (_p(al.packed) if size else None), size
+
+
+def _decode_tail(stream, passes, out, alpha_field: bool = True):
+    """What follows the launches of a tiled or set decode: the wait, one copy
+    of each pass's statuses (``passes``: [(entry point, status tensor)], the
+    colour pass first), and, if any slot failed, NiceError with ``.statuses``,
+    ``.alpha_statuses`` (None without that pass; absent where ``alpha_field``
+    is false) and ``.out``.  Returns ``out``."""
+    if stream is not None:
+        stream.synchronize()
+    sts = [status.cpu().tolist() for _, status in passes]
+    bad = [s for st in sts for s in st if s != OK]
+    if bad:
+        err = NiceError(bad[0], f"{' + '.join(what for what, _ in passes)}: {len(bad)} of {sum(map(len, sts))} "
+                                "tiles failed")
+        err.statuses = sts[0]
+        if alpha_field:
+            err.alpha_statuses = sts[1] if len(sts) > 1 else None
+        err.out = out
+        raise err
+    return out
 
 
 def decode_tiled(timg: TiledImage, roi=None, out=None, out_channels: int | None = None,
@@ -713,13 +777,7 @@ def decode_tiled(timg: TiledImage, roi=None, out=None, out_channels: int | None 
     nx, ny = tile_grid(timg.width, timg.height, tw, th)
     n = nx * ny
     packed = timg.packed
-    if not packed.is_cuda:
-        raise NiceError(E_ARG, "decode_tiled: timg.packed must be on the GPU (load_tiled(path, device=...))")
-    off = timg.off.to("cpu", torch.int64).contiguous()
-    lens = timg.stream_len.to("cpu", torch.int64).contiguous()
-    kind = timg.kind.to("cpu", torch.uint8).contiguous()
-    if off.numel() < n + 1 or lens.numel() != n or kind.numel() != n or int(off[n]) > packed.numel():
-        raise NiceError(E_ARG, "decode_tiled: tables do not match the grid")
+    tables = _host_tables(torch, "decode_tiled", timg, n)
     dev = packed.device
     if out is None:
         oc = timg.channels if out_channels is None else out_channels
@@ -732,44 +790,20 @@ def decode_tiled(timg: TiledImage, roi=None, out=None, out_channels: int | None 
     pitch = _rows_view(out, "decode_tiled: out")
     m = (tx1 - tx0) * (ty1 - ty0)
     status = torch.full((m,), 99, dtype=torch.int32, device=dev)
-    rc = lib().nice_decode_tiled_dev(
-        (ctx or _ctx(dev.index or 0)).ptr, _stream_of(torch, stream, dev), ctypes.c_void_p(packed.data_ptr()),
-        int(off[n]), ctypes.c_void_p(off.data_ptr()), ctypes.c_void_p(lens.data_ptr()),
-        ctypes.c_void_p(kind.data_ptr()), timg.width, timg.height, tw, th, x0, y0, rw, rh, out.shape[2],
-        ctypes.c_void_p(out.data_ptr()), pitch, flags, ctypes.c_void_p(status.data_ptr()))
+    geom = (timg.width, timg.height, tw, th, x0, y0, rw, rh)
+    rc = lib().nice_decode_tiled_dev(*_launch(torch, dev, stream, ctx), _p(packed), int(tables[0][n]),
+                                     *map(_p, tables), *geom, out.shape[2], _p(out), pitch, flags, _p(status))
     _check(rc, "nice_decode_tiled_dev")
-    al = timg.alpha if out.shape[2] == 4 else None
-    if al is not None:   # the stored alpha over byte +3 of what the colour pass wrote
-        if not al.packed.is_cuda or al.packed.device != dev:
-            raise NiceError(E_ARG, "decode_tiled: timg.alpha.packed must be on the GPU, with timg.packed")
-        aoff = al.off.to("cpu", torch.int64).contiguous()
-        alens = al.stream_len.to("cpu", torch.int64).contiguous()
-        akind = al.kind.to("cpu", torch.uint8).contiguous()
-        aval = al.value.to("cpu", torch.uint8).contiguous()
-        if (aoff.numel() < n + 1 or alens.numel() != n or akind.numel() != n or aval.numel() != n
-                or int(aoff[n]) > al.packed.numel()):
-            raise NiceError(E_ARG, "decode_tiled: alpha tables do not match the grid")
+    passes = [("nice_decode_tiled_dev", status)]
+    if timg.alpha is not None and out.shape[2] == 4:   # the stored alpha over byte +3 of what the colour pass wrote
+        atables = _host_tables(torch, "decode_tiled", timg.alpha, n, colour_dev=dev)
         astatus = torch.full((m,), 99, dtype=torch.int32, device=dev)
         rc = lib().nice_decode_tiled_alpha_dev(
-            (ctx or _ctx(dev.index or 0)).ptr, _stream_of(torch, stream, dev),
-            ctypes.c_void_p(al.packed.data_ptr() if int(aoff[n]) else None), int(aoff[n]),
-            ctypes.c_void_p(aoff.data_ptr()), ctypes.c_void_p(alens.data_ptr()), ctypes.c_void_p(akind.data_ptr()),
-            ctypes.c_void_p(aval.data_ptr()), timg.width, timg.height, tw, th, x0, y0, rw, rh,
-            ctypes.c_void_p(out.data_ptr()), pitch, ctypes.c_void_p(astatus.data_ptr()))
+            *_launch(torch, dev, stream, ctx), *_alpha_packed(timg.alpha, atables, n), *map(_p, atables), *geom,
+            _p(out), pitch, _p(astatus))
         _check(rc, "nice_decode_tiled_alpha_dev")
-    if stream is not None:
-        stream.synchronize()
-    st = status.cpu().tolist()
-    ast = astatus.cpu().tolist() if al is not None else None
-    bad = [s for s in st + (ast or []) if s != OK]
-    if bad:
-        what = "nice_decode_tiled_dev" if al is None else "nice_decode_tiled_dev + nice_decode_tiled_alpha_dev"
-        err = NiceError(bad[0], f"{what}: {len(bad)} of {m if al is None else 2 * m} tiles failed")
-        err.statuses = st
-        err.alpha_statuses = ast
-        err.out = out
-        raise err
-    return out
+        passes.append(("nice_decode_tiled_alpha_dev", astatus))
+    return _decode_tail(stream, passes, out)
 
 
 # Host-side container of a tiled image: one file, little-endian throughout
@@ -794,87 +828,49 @@ _TILE_HEADER = "<8sIIIIIIIIIQ"
 def save_tiled(path, timg: TiledImage) -> None:
     """Write ``timg`` (tensors on the GPU or the CPU) to ``path``."""
     import struct
-    import numpy as np
-    n = timg.nx * timg.ny
-    lens = np.asarray(timg.stream_len.detach().cpu().numpy(), dtype=np.int64).reshape(-1)
-    offs = np.asarray(timg.off.detach().cpu().numpy(), dtype=np.int64).reshape(-1)
-    kinds = np.asarray(timg.kind.detach().cpu().numpy(), dtype=np.uint8).reshape(-1)
-    if lens.size != n or offs.size != n + 1 or kinds.size != n:
-        raise NiceError(E_ARG, f"save_tiled: tables do not match the {timg.nx} x {timg.ny} grid")
-    size = int(offs[n])
-    if size < 0 or size > timg.packed.numel():
-        raise NiceError(E_ARG, "save_tiled: off[n] exceeds the packed buffer")
-    blob = timg.packed.detach().reshape(-1)[:size].cpu().numpy()
     al = timg.alpha
-    if al is not None:
-        apart = _alpha_part(al, n, "save_tiled")
+    n, size, chunks = _tiles_chunks("save_tiled", timg, timg.nx * timg.ny)
     with open(path, "wb") as fh:
         fh.write(struct.pack(_TILE_HEADER, _TILE_MAGIC, _TILE_VERSION if al is None else _TILE_VERSION_ALPHA,
                              timg.width, timg.height, timg.channels, timg.tile_w, timg.tile_h, timg.nx, timg.ny,
                              0 if al is None else _TILE_FLAG_ALPHA, size))
-        fh.write(lens.astype("<u8").tobytes())
-        fh.write(offs.astype("<u8").tobytes())
-        fh.write(kinds.tobytes() + bytes(-n % 8))
-        fh.write(blob.tobytes())
-        if al is not None:
-            fh.write(apart)
+        fh.writelines(chunks)
 
 
-def _alpha_part(al: TiledAlpha, n: int, who: str) -> bytes:
-    """The alpha part of a version 2 container (NICETILE and NICESETS alike)."""
+def _tiles_chunks(who: str, batch, n: int):
+    """``_batch_chunks`` of the n tiles of a TiledImage or an ImageSet; where it
+    has an alpha batch, the alpha part of a version 2 container (NICETILE and
+    NICESETS alike) follows: the u64 alpha packed size, then its chunks."""
     import struct
-    import numpy as np
-    alens = np.asarray(al.stream_len.detach().cpu().numpy(), dtype=np.int64).reshape(-1)
-    aoffs = np.asarray(al.off.detach().cpu().numpy(), dtype=np.int64).reshape(-1)
-    akinds = np.asarray(al.kind.detach().cpu().numpy(), dtype=np.uint8).reshape(-1)
-    avals = np.asarray(al.value.detach().cpu().numpy(), dtype=np.uint8).reshape(-1)
-    if alens.size != n or aoffs.size != n + 1 or akinds.size != n or avals.size != n:
-        raise NiceError(E_ARG, f"{who}: alpha tables do not match the {n} tiles")
-    asize = int(aoffs[n])
-    if asize < 0 or asize > al.packed.numel():
-        raise NiceError(E_ARG, f"{who}: alpha off[n] exceeds the alpha packed buffer")
-    ablob = al.packed.detach().reshape(-1)[:asize].cpu().numpy()
-    return b"".join([struct.pack("<Q", asize), alens.astype("<u8").tobytes(), aoffs.astype("<u8").tobytes(),
-                     akinds.tobytes() + bytes(-n % 8), avals.tobytes() + bytes(-n % 8), ablob.tobytes()])
+    n, size, chunks = _batch_chunks(who, batch.packed, batch.off, batch.stream_len, batch.kind, n=n)
+    al = batch.alpha
+    if al is not None:
+        _, asize, achunks = _batch_chunks(who, al.packed, al.off, al.stream_len, al.kind, al.value, n=n, pre="alpha ")
+        chunks += [struct.pack("<Q", asize)] + achunks
+    return n, size, chunks
 
 
-def _load_alpha_part(fh, fsize: int, start: int, n: int, tw: int, th: int, bad, device) -> TiledAlpha:
-    """Reads and validates, as strictly as the colour tables, the alpha part
-    that begins at byte ``start`` of a version 2 container and must end the file."""
+def _read_tiles(fh, bad, fsize: int, start: int, n: int, size: int, tw: int, th: int, has_alpha: bool, device):
+    """What follows the header fields of a NICETILE or NICESETS container, from
+    byte ``start`` on: the colour batch of n tiles and ``size`` packed bytes,
+    which ends a version 1 file, and in a version 2 file the alpha part, read
+    and validated as strictly, which must end it.  Returns (packed, off,
+    stream_len, kind, alpha), ``alpha`` a TiledAlpha or None."""
     import struct
-    import numpy as np
-    import torch
     kpad = n + (-n % 8)
+    colour_end = start + 8 * n + 8 * (n + 1) + kpad + size
+    if (fsize < colour_end + 8) if has_alpha else (fsize != colour_end):
+        raise bad("file size does not match the header")
+    colour = _read_batch(fh, bad, n, size, max_kind=1, raw_len=tw * th * 3, device=device)
+    if not has_alpha:
+        return (*colour, None)
     (asize,) = struct.unpack("<Q", fh.read(8))
     if asize % 16 or asize >= 1 << 62:
         raise bad("alpha packed size")
-    if fsize != start + 8 + 8 * n + 8 * (n + 1) + 2 * kpad + asize:
+    if fsize != colour_end + 8 + 8 * n + 8 * (n + 1) + 2 * kpad + asize:
         raise bad("file size does not match the alpha tables")
-    alens = np.frombuffer(fh.read(8 * n), "<u8")
-    aoffs = np.frombuffer(fh.read(8 * (n + 1)), "<u8")
-    akinds = np.frombuffer(fh.read(kpad), np.uint8)
-    avals = np.frombuffer(fh.read(kpad), np.uint8)
-    if aoffs[0] != 0 or aoffs[n] != asize or (aoffs % 16).any():
-        raise bad("alpha offsets not 16-byte aligned from 0 to the alpha packed size")
-    if (aoffs[1:] < aoffs[:-1]).any():
-        raise bad("alpha offsets not monotone")
-    if (alens > aoffs[1:] - aoffs[:-1]).any():
-        raise bad("an alpha tile overlaps the next")
-    if akinds[n:].any() or avals[n:].any() or (akinds[:n] > 2).any():
-        raise bad("alpha tile kinds")
-    if (alens[akinds[:n] == 1] != tw * th).any():
-        raise bad("raw alpha tile length")
-    if (alens[akinds[:n] == 2] != 0).any():
-        raise bad("constant alpha tile with a length")
-    if avals[:n][akinds[:n] != 2].any():
-        raise bad("alpha value of a tile that is not constant")
-    ablob = np.frombuffer(fh.read(asize), np.uint8)
-    if ablob.size != asize:
-        raise bad("truncated")
-    apacked = torch.from_numpy(ablob.copy())
-    return TiledAlpha(apacked if device is None else apacked.to(device),
-                      torch.from_numpy(aoffs.astype(np.int64)), torch.from_numpy(alens.astype(np.int64)),
-                      torch.from_numpy(akinds[:n].copy()), torch.from_numpy(avals[:n].copy()))
+    alpha = _read_batch(fh, bad, n, asize, max_kind=2, raw_len=tw * th, pre="alpha ", device=device)
+    return (*colour, TiledAlpha(*alpha))
 
 
 def load_tiled(path, device=None) -> TiledImage:
@@ -883,8 +879,6 @@ def load_tiled(path, device=None) -> TiledImage:
     no libnice_hip.so needed); the tables are CPU tensors.  A file that is not
     a consistent tiled image raises NiceError(E_FORMAT)."""
     import struct
-    import numpy as np
-    import torch
 
     def bad(why):
         return NiceError(E_FORMAT, f"load_tiled({path}): {why}")
@@ -915,36 +909,7 @@ def load_tiled(path, device=None) -> TiledImage:
             raise bad("too many tiles")
         if size % 16 or size >= 1 << 62:
             raise bad("packed size")
-        kpad = n + (-n % 8)
-        colour_end = hsz + 8 * n + 8 * (n + 1) + kpad + size
-        if (fsize < colour_end + 8) if has_alpha else (fsize != colour_end):
-            raise bad("file size does not match the header")
-        lens = np.frombuffer(fh.read(8 * n), "<u8")
-        offs = np.frombuffer(fh.read(8 * (n + 1)), "<u8")
-        kinds = np.frombuffer(fh.read(kpad), np.uint8)
-        if lens.size != n or offs.size != n + 1 or kinds.size != kpad:
-            raise bad("truncated")
-        if offs[0] != 0 or offs[n] != size or (offs % 16).any():
-            raise bad("offsets not 16-byte aligned from 0 to the packed size")
-        if (offs[1:] < offs[:-1]).any():
-            raise bad("offsets not monotone")
-        if (lens > offs[1:] - offs[:-1]).any():
-            raise bad("a tile overlaps the next")
-        if kinds[n:].any() or (kinds[:n] > 1).any():
-            raise bad("tile kinds")
-        if (lens[kinds[:n] == 1] != tw * th * 3).any():
-            raise bad("raw tile length")
-        blob = np.frombuffer(fh.read(size), np.uint8)
-        if blob.size != size:
-            raise bad("truncated")
-        alpha = None
-        if has_alpha:
-            alpha = _load_alpha_part(fh, fsize, colour_end, n, tw, th, bad, device)
-    packed = torch.from_numpy(blob.copy())
-    if device is not None:
-        packed = packed.to(device)
-    return TiledImage(w, h, c, tw, th, packed, torch.from_numpy(offs.astype(np.int64)),
-                      torch.from_numpy(lens.astype(np.int64)), torch.from_numpy(kinds[:n].copy()), alpha)
+        return TiledImage(w, h, c, tw, th, *_read_tiles(fh, bad, fsize, hsz, n, size, tw, th, has_alpha, device))
 
 
 # ---- image sets (include/nice.h, "image sets") --------------------------------
@@ -992,15 +957,25 @@ def _u32_array(vals):
     return (ctypes.c_uint32 * max(len(vals), 1))(*vals)
 
 
+def _set_geom(widths, heights, tile_w: int, tile_h: int):
+    """A set's geometry as the C ABI takes it: (h_w, h_h, K, tile_w, tile_h)."""
+    return _u32_array(widths), _u32_array(heights), len(widths), tile_w, tile_h
+
+
+def _images(tensors, pitches):
+    """Per-image (or per-window) base addresses and row pitches, as two host arrays."""
+    k = len(tensors)
+    return (ctypes.c_void_p * k)(*[t.data_ptr() for t in tensors]), (ctypes.c_uint64 * k)(*pitches)
+
+
 def set_grid(widths, heights, tile_w: int, tile_h: int):
     """``first`` (K + 1 ints): the scan of the images' tile counts, ``first[K]``
     the set's n; NiceError(E_ARG) for an empty set or one outside the limits."""
-    k = len(widths)
-    if len(heights) != k:
+    if len(heights) != len(widths):
         raise NiceError(E_ARG, "set_grid: widths and heights differ in length")
     _u32_args(tile_w, tile_h)
-    first = (ctypes.c_uint32 * (k + 1))()
-    _check(lib().nice_set_grid(_u32_array(widths), _u32_array(heights), k, tile_w, tile_h, first), "nice_set_grid")
+    first = (ctypes.c_uint32 * (len(widths) + 1))()
+    _check(lib().nice_set_grid(*_set_geom(widths, heights, tile_w, tile_h), first), "nice_set_grid")
     return list(first)
 
 
@@ -1008,37 +983,26 @@ def set_bound(widths, heights, tile_w: int, tile_h: int) -> int:
     """Worst-case packed size of the set (0: bad set)."""
     if len(heights) != len(widths):
         return 0
-    return int(lib().nice_set_bound(_u32_array(widths), _u32_array(heights), len(widths), tile_w, tile_h))
+    return int(lib().nice_set_bound(*_set_geom(widths, heights, tile_w, tile_h)))
 
 
 def set_alpha_bound(widths, heights, tile_w: int, tile_h: int) -> int:
     """Worst-case packed size of the set's alpha batch (0: bad set)."""
     if len(heights) != len(widths):
         return 0
-    return int(lib().nice_set_alpha_bound(_u32_array(widths), _u32_array(heights), len(widths), tile_w, tile_h))
+    return int(lib().nice_set_alpha_bound(*_set_geom(widths, heights, tile_w, tile_h)))
 
 
 def _encode_set_alpha(torch, images, pitches, widths, heights, tw, th, n, stream, ctx) -> TiledAlpha:
-    k, dev = len(images), images[0].device
+    dev = images[0].device
     packed = torch.empty(set_alpha_bound(widths, heights, tw, th), dtype=torch.uint8, device=dev)
-    off = torch.empty(n + 1, dtype=torch.int64, device=dev)
-    lens = torch.empty(n, dtype=torch.int64, device=dev)
-    kind = torch.empty(n, dtype=torch.uint8, device=dev)
-    val = torch.empty(n, dtype=torch.uint8, device=dev)
-    status = torch.full((1,), 99, dtype=torch.int32, device=dev)
+    tables, status = _encode_tables(torch, n, dev, value=True)
     rc = lib().nice_encode_set_alpha_dev(
-        (ctx or _ctx(dev.index or 0)).ptr, _stream_of(torch, stream, dev),
-        (ctypes.c_void_p * k)(*[t.data_ptr() for t in images]), (ctypes.c_uint64 * k)(*pitches),
-        _u32_array(widths), _u32_array(heights), k, tw, th, ctypes.c_void_p(packed.data_ptr()), packed.numel(),
-        ctypes.c_void_p(off.data_ptr()), ctypes.c_void_p(lens.data_ptr()), ctypes.c_void_p(kind.data_ptr()),
-        ctypes.c_void_p(val.data_ptr()), ctypes.c_void_p(status.data_ptr()))
-    _check(rc, "nice_encode_set_alpha_dev")
-    if stream is not None:
-        stream.synchronize()
-    _check(int(status.cpu()[0]), "nice_encode_set_alpha_dev")
-    off_h = off.cpu()
+        *_launch(torch, dev, stream, ctx), *_images(images, pitches), *_set_geom(widths, heights, tw, th), _p(packed),
+        packed.numel(), *map(_p, tables), _p(status))
+    trimmed, *host = _encode_tail(rc, "nice_encode_set_alpha_dev", stream, status, packed, tables, n)
     # (a copy: the alpha of mostly opaque images is far smaller than its bound)
-    return TiledAlpha(packed[:int(off_h[n])].clone(), off_h, lens.cpu(), kind.cpu(), val.cpu())
+    return TiledAlpha(trimmed.clone(), *host)
 
 
 def _win_array(windows):
@@ -1055,13 +1019,13 @@ def set_select(widths, heights, tile_w: int, tile_h: int, windows):
     window j's slots, the tiles it touches inside its image in row-major order,
     are ``slot_first[j] : slot_first[j + 1]``.  NiceError(E_ARG) for an image
     index past the set, an empty window or one that leaves its image."""
-    k, m = len(widths), len(windows)
-    if len(heights) != k:
+    m = len(windows)
+    if len(heights) != len(widths):
         raise NiceError(E_ARG, "set_select: widths and heights differ in length")
     _u32_args(tile_w, tile_h)
     sf = (ctypes.c_uint32 * (m + 1))()
-    _check(lib().nice_set_select(_u32_array(widths), _u32_array(heights), k, tile_w, tile_h, _win_array(windows), m,
-                                 sf), "nice_set_select")
+    _check(lib().nice_set_select(*_set_geom(widths, heights, tile_w, tile_h), _win_array(windows), m, sf),
+           "nice_set_select")
     return list(sf)
 
 
@@ -1093,28 +1057,58 @@ def encode_set(images, tile=None, channels_out: int | None = None, stream=None, 
         raise NiceError(E_ARG, "encode_set: alpha=True needs 4-channel images")
     widths, heights = [t.shape[1] for t in images], [t.shape[0] for t in images]
     first = set_grid(widths, heights, tw, th)
-    k, n = len(images), first[-1]
+    n = first[-1]
     if packed is None:
         packed = torch.empty(set_bound(widths, heights, tw, th), dtype=torch.uint8, device=dev)
-    off = torch.empty(n + 1, dtype=torch.int64, device=dev)
-    lens = torch.empty(n, dtype=torch.int64, device=dev)
-    kind = torch.empty(n, dtype=torch.uint8, device=dev)
-    status = torch.full((1,), 99, dtype=torch.int32, device=dev)
-    rc = lib().nice_encode_set_dev(
-        (ctx or _ctx(dev.index or 0)).ptr, _stream_of(torch, stream, dev),
-        (ctypes.c_void_p * k)(*[t.data_ptr() for t in images]), (ctypes.c_uint64 * k)(*pitches),
-        _u32_array(widths), _u32_array(heights), k, c, c if channels_out is None else channels_out, tw, th,
-        ctypes.c_void_p(packed.data_ptr()), packed.numel(), ctypes.c_void_p(off.data_ptr()),
-        ctypes.c_void_p(lens.data_ptr()), ctypes.c_void_p(kind.data_ptr()), ctypes.c_void_p(status.data_ptr()))
-    _check(rc, "nice_encode_set_dev")
-    if stream is not None:
-        stream.synchronize()
-    _check(int(status.cpu()[0]), "nice_encode_set_dev")
-    off_h = off.cpu()
-    iset = ImageSet(widths, heights, c, tw, th, first, packed[:int(off_h[n])], off_h, lens.cpu(), kind.cpu())
+    tables, status = _encode_tables(torch, n, dev)
+    rc = lib().nice_encode_set_dev(   # (the channels stand between K and the tile size)
+        *_launch(torch, dev, stream, ctx), *_images(images, pitches), _u32_array(widths), _u32_array(heights),
+        len(images), c, c if channels_out is None else channels_out, tw, th, _p(packed), packed.numel(),
+        *map(_p, tables), _p(status))
+    iset = ImageSet(widths, heights, c, tw, th, first,
+                    *_encode_tail(rc, "nice_encode_set_dev", stream, status, packed, tables, n))
     if alpha:
         iset.alpha = _encode_set_alpha(torch, images, pitches, widths, heights, tw, th, n, stream, ctx)
     return iset
+
+
+def _set_windows(who: str, iset: ImageSet, images, windows):
+    """What a set decode is to produce, from its ``images`` / ``windows``
+    arguments (not both; neither: every image): ``(windows, m, slot_first, n)``
+    with the M windows as int quintuples, their slots (``set_select``) and the
+    set's tile count."""
+    if images is not None and windows is not None:
+        raise NiceError(E_ARG, f"{who}: images or windows, not both")
+    k = len(iset.widths)
+    if windows is None:
+        idx = range(k) if images is None else [int(i) for i in images]
+        if any(i < 0 or i >= k for i in idx):
+            raise NiceError(E_ARG, f"{who}: image index outside the set")
+        windows = [(i, 0, 0, iset.widths[i], iset.heights[i]) for i in idx]
+    windows = [tuple(int(v) for v in wdw) for wdw in windows]
+    slot_first = set_select(iset.widths, iset.heights, iset.tile_w, iset.tile_h, windows)
+    n = set_grid(iset.widths, iset.heights, iset.tile_w, iset.tile_h)[-1]
+    return windows, len(windows), slot_first, n
+
+
+def _set_outputs(out, windows, new, msg: str):
+    """``(outs, result)`` of a set decode: the per-window tensors to write and
+    what the call returns.  ``out`` None: ``new(window)`` for every window;
+    one batch tensor of M windows: its ``out[j]``; else a list of M tensors.
+    Another count is NiceError(E_ARG, ``msg``); what each output must look
+    like is the caller's to check."""
+    m = len(windows)
+    if out is None:
+        outs = [new(wdw) for wdw in windows]
+        return outs, outs
+    if hasattr(out, "dim"):
+        if out.dim() != 4 or out.shape[0] != m:
+            raise NiceError(E_ARG, msg)
+        return [out[j] for j in range(m)], out
+    outs = list(out)
+    if len(outs) != m:
+        raise NiceError(E_ARG, msg)
+    return outs, out
 
 
 def decode_set(iset: ImageSet, images=None, windows=None, out=None, out_channels: int | None = None,
@@ -1137,41 +1131,17 @@ def decode_set(iset: ImageSet, images=None, windows=None, out=None, out_channels
     that pass), and a failed alpha slot keeps what the colour pass wrote
     there.  Waits for the device (the statuses come back)."""
     import torch
-    if images is not None and windows is not None:
-        raise NiceError(E_ARG, "decode_set: images or windows, not both")
-    k = len(iset.widths)
-    tw, th = iset.tile_w, iset.tile_h
-    if windows is None:
-        idx = range(k) if images is None else [int(i) for i in images]
-        if any(i < 0 or i >= k for i in idx):
-            raise NiceError(E_ARG, "decode_set: image index outside the set")
-        windows = [(i, 0, 0, iset.widths[i], iset.heights[i]) for i in idx]
-    windows = [tuple(int(v) for v in wdw) for wdw in windows]
-    m = len(windows)
-    slot_first = set_select(iset.widths, iset.heights, tw, th, windows)
-    first = set_grid(iset.widths, iset.heights, tw, th)
-    n = first[-1]
+    windows, m, slot_first, n = _set_windows("decode_set", iset, images, windows)
     packed = iset.packed
-    if not packed.is_cuda:
-        raise NiceError(E_ARG, "decode_set: iset.packed must be on the GPU (load_set(path, device=...))")
-    off = iset.off.to("cpu", torch.int64).contiguous()
-    lens = iset.stream_len.to("cpu", torch.int64).contiguous()
-    kind = iset.kind.to("cpu", torch.uint8).contiguous()
-    if off.numel() < n + 1 or lens.numel() != n or kind.numel() != n or int(off[n]) > packed.numel():
-        raise NiceError(E_ARG, "decode_set: tables do not match the set")
+    tables = _host_tables(torch, "decode_set", iset, n)
     dev = packed.device
-    result = out
-    if out is None:
-        oc = iset.channels if out_channels is None else out_channels
-        outs = result = [torch.empty((wdw[4], wdw[3], oc), dtype=torch.uint8, device=dev) for wdw in windows]
-    elif hasattr(out, "dim"):
-        if out.dim() != 4 or out.shape[0] != m:
-            raise NiceError(E_ARG, "decode_set: out must be [M, rh, rw, out_channels] or a list of M tensors")
-        outs = [out[j] for j in range(m)]
-    else:
-        outs = list(out)
-        if len(outs) != m:
-            raise NiceError(E_ARG, "decode_set: out must be [M, rh, rw, out_channels] or a list of M tensors")
+
+    def new(wdw):
+        return torch.empty((wdw[4], wdw[3], iset.channels if out_channels is None else out_channels),
+                           dtype=torch.uint8, device=dev)
+
+    outs, result = _set_outputs(out, windows, new, "decode_set: out must be [M, rh, rw, out_channels] or a list of M "
+                                                   "tensors")
     oc = outs[0].shape[-1] if outs[0].dim() == 3 else 0
     for wdw, o in zip(windows, outs):
         if o.dim() != 3 or tuple(o.shape) != (wdw[4], wdw[3], oc) or out_channels not in (None, oc):
@@ -1179,47 +1149,21 @@ def decode_set(iset: ImageSet, images=None, windows=None, out=None, out_channels
         if o.device != dev:
             raise NiceError(E_ARG, "decode_set: out on another device")
     pitches = [_rows_view(o, "decode_set: out") for o in outs]
+    geom = _set_geom(iset.widths, iset.heights, iset.tile_w, iset.tile_h)
     status = torch.full((slot_first[m],), 99, dtype=torch.int32, device=dev)
-    rc = lib().nice_decode_set_dev(
-        (ctx or _ctx(dev.index or 0)).ptr, _stream_of(torch, stream, dev), ctypes.c_void_p(packed.data_ptr()),
-        int(off[n]), ctypes.c_void_p(off.data_ptr()), ctypes.c_void_p(lens.data_ptr()),
-        ctypes.c_void_p(kind.data_ptr()), _u32_array(iset.widths), _u32_array(iset.heights), k, tw, th,
-        _win_array(windows), (ctypes.c_void_p * m)(*[o.data_ptr() for o in outs]), (ctypes.c_uint64 * m)(*pitches), m,
-        oc, flags, ctypes.c_void_p(status.data_ptr()))
+    rc = lib().nice_decode_set_dev(*_launch(torch, dev, stream, ctx), _p(packed), int(tables[0][n]), *map(_p, tables),
+                                   *geom, _win_array(windows), *_images(outs, pitches), m, oc, flags, _p(status))
     _check(rc, "nice_decode_set_dev")
-    al = iset.alpha if oc == 4 else None
-    if al is not None:   # the stored alpha over byte +3 of what the colour pass wrote
-        if not al.packed.is_cuda or al.packed.device != dev:
-            raise NiceError(E_ARG, "decode_set: iset.alpha.packed must be on the GPU, with iset.packed")
-        aoff = al.off.to("cpu", torch.int64).contiguous()
-        alens = al.stream_len.to("cpu", torch.int64).contiguous()
-        akind = al.kind.to("cpu", torch.uint8).contiguous()
-        aval = al.value.to("cpu", torch.uint8).contiguous()
-        if (aoff.numel() < n + 1 or alens.numel() != n or akind.numel() != n or aval.numel() != n
-                or int(aoff[n]) > al.packed.numel()):
-            raise NiceError(E_ARG, "decode_set: alpha tables do not match the set")
+    passes = [("nice_decode_set_dev", status)]
+    if iset.alpha is not None and oc == 4:   # the stored alpha over byte +3 of what the colour pass wrote
+        atables = _host_tables(torch, "decode_set", iset.alpha, n, colour_dev=dev)
         astatus = torch.full((slot_first[m],), 99, dtype=torch.int32, device=dev)
         rc = lib().nice_decode_set_alpha_dev(
-            (ctx or _ctx(dev.index or 0)).ptr, _stream_of(torch, stream, dev),
-            ctypes.c_void_p(al.packed.data_ptr() if int(aoff[n]) else None), int(aoff[n]),
-            ctypes.c_void_p(aoff.data_ptr()), ctypes.c_void_p(alens.data_ptr()), ctypes.c_void_p(akind.data_ptr()),
-            ctypes.c_void_p(aval.data_ptr()), _u32_array(iset.widths), _u32_array(iset.heights), k, tw, th,
-            _win_array(windows), (ctypes.c_void_p * m)(*[o.data_ptr() for o in outs]), (ctypes.c_uint64 * m)(*pitches),
-            m, ctypes.c_void_p(astatus.data_ptr()))
+            *_launch(torch, dev, stream, ctx), *_alpha_packed(iset.alpha, atables, n), *map(_p, atables), *geom,
+            _win_array(windows), *_images(outs, pitches), m, _p(astatus))
         _check(rc, "nice_decode_set_alpha_dev")
-    if stream is not None:
-        stream.synchronize()
-    st = status.cpu().tolist()
-    ast = astatus.cpu().tolist() if al is not None else None
-    bad = [s for s in st + (ast or []) if s != OK]
-    if bad:
-        what = "nice_decode_set_dev" if al is None else "nice_decode_set_dev + nice_decode_set_alpha_dev"
-        err = NiceError(bad[0], f"{what}: {len(bad)} of {len(st) + len(ast or [])} tiles failed")
-        err.statuses = st
-        err.alpha_statuses = ast
-        err.out = result
-        raise err
-    return result
+        passes.append(("nice_decode_set_alpha_dev", astatus))
+    return _decode_tail(stream, passes, result)
 
 
 def _f32(v) -> float:
@@ -1282,27 +1226,9 @@ def decode_set_tensor(iset: ImageSet, images=None, windows=None, out=None, dtype
     dt = {torch.float32: TENSOR_F32, torch.float16: TENSOR_F16, torch.bfloat16: TENSOR_BF16}.get(dtype)
     if dt is None:
         raise NiceError(E_ARG, "decode_set_tensor: dtype must be torch.float32, torch.float16 or torch.bfloat16")
-    if images is not None and windows is not None:
-        raise NiceError(E_ARG, "decode_set_tensor: images or windows, not both")
-    k = len(iset.widths)
-    tw, th = iset.tile_w, iset.tile_h
-    if windows is None:
-        idx = range(k) if images is None else [int(i) for i in images]
-        if any(i < 0 or i >= k for i in idx):
-            raise NiceError(E_ARG, "decode_set_tensor: image index outside the set")
-        windows = [(i, 0, 0, iset.widths[i], iset.heights[i]) for i in idx]
-    windows = [tuple(int(v) for v in wdw) for wdw in windows]
-    m = len(windows)
-    slot_first = set_select(iset.widths, iset.heights, tw, th, windows)
-    n = set_grid(iset.widths, iset.heights, tw, th)[-1]
+    windows, m, slot_first, n = _set_windows("decode_set_tensor", iset, images, windows)
     packed = iset.packed
-    if not packed.is_cuda:
-        raise NiceError(E_ARG, "decode_set_tensor: iset.packed must be on the GPU (load_set(path, device=...))")
-    off = iset.off.to("cpu", torch.int64).contiguous()
-    lens = iset.stream_len.to("cpu", torch.int64).contiguous()
-    kind = iset.kind.to("cpu", torch.uint8).contiguous()
-    if off.numel() < n + 1 or lens.numel() != n or kind.numel() != n or int(off[n]) > packed.numel():
-        raise NiceError(E_ARG, "decode_set_tensor: tables do not match the set")
+    tables = _host_tables(torch, "decode_set_tensor", iset, n)
     scale, bias = [_f32(v) for v in scale], [_f32(v) for v in bias]
     if len(scale) != 3 or len(bias) != 3:
         raise NiceError(E_ARG, "decode_set_tensor: scale and bias have three entries each")
@@ -1310,22 +1236,14 @@ def decode_set_tensor(iset: ImageSet, images=None, windows=None, out=None, dtype
     if len(flips) != m:
         raise NiceError(E_ARG, "decode_set_tensor: flip must have one entry per window")
     dev = packed.device
-    result = out
     shape_msg = "decode_set_tensor: out must be [M, 3, rh, rw] or a list of M tensors [3, rh, rw] of their windows"
-    if out is None:
+
+    def new(wdw):
         if channels_last:
-            outs = [torch.empty((wdw[4], wdw[3], 3), dtype=dtype, device=dev).permute(2, 0, 1) for wdw in windows]
-        else:
-            outs = [torch.empty((3, wdw[4], wdw[3]), dtype=dtype, device=dev) for wdw in windows]
-        result = outs
-    elif hasattr(out, "dim"):
-        if out.dim() != 4 or out.shape[0] != m:
-            raise NiceError(E_ARG, shape_msg)
-        outs = [out[j] for j in range(m)]
-    else:
-        outs = list(out)
-        if len(outs) != m:
-            raise NiceError(E_ARG, shape_msg)
+            return torch.empty((wdw[4], wdw[3], 3), dtype=dtype, device=dev).permute(2, 0, 1)
+        return torch.empty((3, wdw[4], wdw[3]), dtype=dtype, device=dev)
+
+    outs, result = _set_outputs(out, windows, new, shape_msg)
     for wdw, o in zip(windows, outs):
         if not hasattr(o, "dim") or o.dim() != 3 or tuple(o.shape) != (3, wdw[4], wdw[3]):
             raise NiceError(E_ARG, shape_msg)
@@ -1341,24 +1259,13 @@ def decode_set_tensor(iset: ImageSet, images=None, windows=None, out=None, dtype
                                "interleaved (channel stride 1, innermost 3)")
     status = torch.full((slot_first[m],), 99, dtype=torch.int32, device=dev)
     rc = lib().nice_decode_set_tensor_dev(
-        (ctx or _ctx(dev.index or 0)).ptr, _stream_of(torch, stream, dev), ctypes.c_void_p(packed.data_ptr()),
-        int(off[n]), ctypes.c_void_p(off.data_ptr()), ctypes.c_void_p(lens.data_ptr()),
-        ctypes.c_void_p(kind.data_ptr()), _u32_array(iset.widths), _u32_array(iset.heights), k, tw, th,
-        _win_array(windows), (ctypes.c_uint8 * m)(*flips), (ctypes.c_void_p * m)(*[o.data_ptr() for o in outs]),
-        (ctypes.c_uint64 * m)(*[v[0] for v in pitches]), (ctypes.c_uint64 * m)(*[v[1] for v in pitches]), m,
-        dt, layout, (ctypes.c_float * 3)(*scale), (ctypes.c_float * 3)(*bias), flags,
-        ctypes.c_void_p(status.data_ptr()))
+        *_launch(torch, dev, stream, ctx), _p(packed), int(tables[0][n]), *map(_p, tables),
+        *_set_geom(iset.widths, iset.heights, iset.tile_w, iset.tile_h), _win_array(windows),
+        (ctypes.c_uint8 * m)(*flips), *_images(outs, [v[0] for v in pitches]),
+        (ctypes.c_uint64 * m)(*[v[1] for v in pitches]), m, dt, layout, (ctypes.c_float * 3)(*scale),
+        (ctypes.c_float * 3)(*bias), flags, _p(status))
     _check(rc, "nice_decode_set_tensor_dev")
-    if stream is not None:
-        stream.synchronize()
-    st = status.cpu().tolist()
-    bad = [s for s in st if s != OK]
-    if bad:
-        err = NiceError(bad[0], f"nice_decode_set_tensor_dev: {len(bad)} of {len(st)} tiles failed")
-        err.statuses = st
-        err.out = result
-        raise err
-    return result
+    return _decode_tail(stream, [("nice_decode_set_tensor_dev", status)], result, alpha_field=False)
 
 
 # Host-side container of an image set: one file, little-endian throughout
@@ -1392,33 +1299,19 @@ def save_set(path, iset: ImageSet) -> None:
     """Write ``iset`` (tensors on the GPU or the CPU) to ``path``."""
     import struct
     import numpy as np
-    k = len(iset.widths)
-    n = _set_first(iset.widths, iset.heights, iset.tile_w, iset.tile_h)[-1] if k == len(iset.heights) else -1
-    lens = np.asarray(iset.stream_len.detach().cpu().numpy(), dtype=np.int64).reshape(-1)
-    offs = np.asarray(iset.off.detach().cpu().numpy(), dtype=np.int64).reshape(-1)
-    kinds = np.asarray(iset.kind.detach().cpu().numpy(), dtype=np.uint8).reshape(-1)
-    if k == 0 or lens.size != n or offs.size != n + 1 or kinds.size != n:
-        raise NiceError(E_ARG, f"save_set: tables do not match the {k} images")
-    size = int(offs[n])
-    if size < 0 or size > iset.packed.numel():
-        raise NiceError(E_ARG, "save_set: off[n] exceeds the packed buffer")
-    blob = iset.packed.detach().reshape(-1)[:size].cpu().numpy()
-    al = iset.alpha
-    if al is not None:
-        if iset.channels != 4:
-            raise NiceError(E_ARG, "save_set: an alpha batch needs a 4-channel set")
-        apart = _alpha_part(al, n, "save_set")
+    k, al = len(iset.widths), iset.alpha
+    if k == 0 or k != len(iset.heights):
+        raise NiceError(E_ARG, f"save_set: no images, or {k} widths for {len(iset.heights)} heights")
+    if al is not None and iset.channels != 4:
+        raise NiceError(E_ARG, "save_set: an alpha batch needs a 4-channel set")
+    n, size, chunks = _tiles_chunks("save_set", iset, _set_first(iset.widths, iset.heights, iset.tile_w,
+                                                                 iset.tile_h)[-1])
     with open(path, "wb") as fh:
         fh.write(struct.pack(_SET_HEADER, _SET_MAGIC, _SET_VERSION if al is None else _SET_VERSION_ALPHA,
                              iset.channels, iset.tile_w, iset.tile_h, k, 0 if al is None else _SET_FLAG_ALPHA, n,
                              size))
         fh.write(np.stack([np.asarray(iset.widths, "<u4"), np.asarray(iset.heights, "<u4")], axis=1).tobytes())
-        fh.write(lens.astype("<u8").tobytes())
-        fh.write(offs.astype("<u8").tobytes())
-        fh.write(kinds.tobytes() + bytes(-n % 8))
-        fh.write(blob.tobytes())
-        if al is not None:
-            fh.write(apart)
+        fh.writelines(chunks)
 
 
 def load_set(path, device=None) -> ImageSet:
@@ -1428,7 +1321,6 @@ def load_set(path, device=None) -> ImageSet:
     a consistent image set raises NiceError(E_FORMAT)."""
     import struct
     import numpy as np
-    import torch
 
     def bad(why):
         return NiceError(E_FORMAT, f"load_set({path}): {why}")
@@ -1465,34 +1357,8 @@ def load_set(path, device=None) -> ImageSet:
             raise bad("tile count does not match the image and tile sizes")
         if n * (-(-tw * th // 1024)) >= 1 << 32:
             raise bad("too many tiles")
-        kpad = n + (-n % 8)
-        colour_end = hsz + 8 * k + 8 * n + 8 * (n + 1) + kpad + size
-        if (fsize < colour_end + 8) if has_alpha else (fsize != colour_end):
-            raise bad("file size does not match the header")
-        lens = np.frombuffer(fh.read(8 * n), "<u8")
-        offs = np.frombuffer(fh.read(8 * (n + 1)), "<u8")
-        kinds = np.frombuffer(fh.read(kpad), np.uint8)
-        if lens.size != n or offs.size != n + 1 or kinds.size != kpad:
-            raise bad("truncated")
-        if offs[0] != 0 or offs[n] != size or (offs % 16).any():
-            raise bad("offsets not 16-byte aligned from 0 to the packed size")
-        if (offs[1:] < offs[:-1]).any():
-            raise bad("offsets not monotone")
-        if (lens > offs[1:] - offs[:-1]).any():
-            raise bad("a tile overlaps the next")
-        if kinds[n:].any() or (kinds[:n] > 1).any():
-            raise bad("tile kinds")
-        if (lens[kinds[:n] == 1] != tw * th * 3).any():
-            raise bad("raw tile length")
-        blob = np.frombuffer(fh.read(size), np.uint8)
-        if blob.size != size:
-            raise bad("truncated")
-        alpha = _load_alpha_part(fh, fsize, colour_end, n, tw, th, bad, device) if has_alpha else None
-    packed = torch.from_numpy(blob.copy())
-    if device is not None:
-        packed = packed.to(device)
-    return ImageSet(widths, heights, c, tw, th, first, packed, torch.from_numpy(offs.astype(np.int64)),
-                    torch.from_numpy(lens.astype(np.int64)), torch.from_numpy(kinds[:n].copy()), alpha)
+        return ImageSet(widths, heights, c, tw, th, first,
+                        *_read_tiles(fh, bad, fsize, hsz + 8 * k, n, size, tw, th, has_alpha, device))
 
 
 def checksum64(buf) -> int:

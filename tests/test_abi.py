@@ -29,6 +29,79 @@ def test_library_exports_every_declared_symbol():
     assert set(pkg.EXPORTS) <= set(_declared())
 
 
+_WIDTH = {"uint8_t": 1, "uint32_t": 4, "int": 4, "int32_t": 4, "float": 4, "uint64_t": 8, "size_t": 8, "int64_t": 8}
+
+
+def _c_class(text):
+    """A C parameter or return type as "void", "ptr" or its width in bytes."""
+    if "*" in text:
+        return "ptr"
+    words = [w for w in text.split() if w != "const"]
+    if words[0] == "void":
+        return "void"
+    return _WIDTH[words[0]]
+
+
+def _prototypes():
+    """{name: (return class, [parameter classes])} of every nice_* prototype in the two headers."""
+    hdr = "".join(open(os.path.join(ROOT, "include", h)).read() for h in ("nice.h", "nice_test.h"))
+    hdr = re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S)
+    hdr = re.sub(r"//[^\n]*", " ", hdr)
+    hdr = re.sub(r"^\s*#[^\n]*", " ", hdr, flags=re.M)
+    protos = {}
+    for chunk in hdr.split(";"):
+        chunk = re.split(r"[{}]", chunk)[-1].strip()
+        m = re.fullmatch(r"(.*?)\b(nice_[a-z_0-9]+)\s*\((.*)\)", chunk, flags=re.S)
+        if not m or chunk.startswith("typedef"):
+            continue
+        params = [p.strip() for p in m.group(3).split(",")]
+        protos[m.group(2)] = (_c_class(m.group(1)), [] if params == ["void"] else [_c_class(p) for p in params])
+    return protos
+
+
+def _ctypes_class(t):
+    if t is None:
+        return "void"
+    if t in (ctypes.c_void_p, ctypes.c_char_p) or issubclass(t, ctypes._Pointer):
+        return "ptr"
+    return ctypes.sizeof(t)
+
+
+def test_ctypes_signatures_match_header(monkeypatch):
+    """Every function the package annotates (``argtypes``, or a ``restype``
+    other than ctypes' default int) agrees with its prototype in include/nice.h
+    or include/nice_test.h: the parameter count, and position by position, as
+    for the return type, pointer against pointer or the byte width of the
+    scalar.  Beside ``lib()``'s block this covers what png.py and sharded.py
+    annotate: ``png._unfilter`` and ``sharded.tile_pixels`` run on the host;
+    ``sharded.HipBands`` creates a device context before it annotates, so here
+    it is given a stand-in for ``_ctx`` and only its annotations are used."""
+    import importlib
+    pkg = nice_pkg()
+    L = pkg.lib()
+    protos = _prototypes()
+    assert set(pkg.EXPORTS) <= set(protos) and set(protos) == set(_declared())
+    importlib.import_module(pkg.__name__ + ".png")._unfilter(b"\0\x07", 1, 1, 1)
+    sharded = importlib.import_module(pkg.__name__ + ".sharded")
+    assert sharded.tile_pixels() > 0
+    monkeypatch.setattr(pkg, "_ctx", lambda device: None)
+    sharded.HipBands(0)
+    checked = 0
+    for name, (ret, params) in sorted(protos.items()):
+        fn = getattr(L, name)
+        if fn.argtypes is None and fn.restype is ctypes.c_int:
+            continue
+        checked += 1
+        assert _ctypes_class(fn.restype) == ret, f"{name}: restype {fn.restype} against {ret}"
+        if fn.argtypes is not None:
+            got = [_ctypes_class(t) for t in fn.argtypes]
+            assert got == params, f"{name}: argtypes {got} against {params}"
+    assert checked >= 50 and L.nice_ctx_destroy.restype is None and L.nice_pipe_destroy.restype is None
+    for name in ("nice_decode_set_tensor_dev", "nice_png_unfilter", "nice_tile_pixels", "nice_band_assemble"):
+        fn = getattr(L, name)
+        assert fn.argtypes is not None or fn.restype is not ctypes.c_int, name
+
+
 def test_encode_bound_and_header_parse():
     pkg = nice_pkg()
     L = pkg.lib()
