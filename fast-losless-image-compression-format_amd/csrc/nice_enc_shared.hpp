@@ -1,13 +1,14 @@
-// nice_enc_shared.hpp -- what the classify kernels (nice_classify.hip) and the
-// rest of the encoder (nice_encode.hip) both use: the "no pixel" value, the
-// tile mask scan, the mode prefixes' identifying streams and the work-item
-// iterator.  Device code.
+// nice_enc_shared.hpp -- what more than one of the encoder's files
+// (nice_classify.hip, nice_pack.hip, nice_encode.hip) use: the "no pixel"
+// value, the tile mask scan, the mode prefixes' identifying streams, the
+// work-item iterator and the wrapped write.  Device code.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "nice_format.h"
 #include "nice_kernels.h"
+#include "nice_pack.hpp"
 
 namespace nice {
 
@@ -56,5 +57,18 @@ struct TileIter {
   __device__ __forceinline__ uint32_t tt() const { return lo + k; }
   __device__ __forceinline__ uint64_t tile() const { return (uint64_t)f * T + lo + k; }
 };
+
+// A write the reference's u32 cache wraps (nice_pack.hpp pack_wrapped_window;
+// nice_pack.hip "Long codes"): the 32-bit window at the byte of stream bit p,
+// read and written back byte by byte (enc_pack_long phase 1, enc_band_fix).
+__device__ __forceinline__ void wrapped_write(uint8_t* out, uint64_t p, uint32_t v, uint32_t n) {
+  const uint64_t B = p >> 3;
+  const uint32_t w = ((uint32_t)out[B] << 24) | ((uint32_t)out[B + 1] << 16) | ((uint32_t)out[B + 2] << 8) | out[B + 3];
+  const uint32_t r = pack_wrapped_window(w, (uint32_t)(p & 7u), v, n);
+  out[B] = (uint8_t)(r >> 24);
+  out[B + 1] = (uint8_t)(r >> 16);
+  out[B + 2] = (uint8_t)(r >> 8);
+  out[B + 3] = (uint8_t)r;
+}
 
 }  // namespace nice

@@ -39,7 +39,7 @@ static_assert(CLS_RING2_MAX_W == 10239, "32K ring");
 static_assert(CLS_PAIR_MAX_W == 4095, "16K ring, two tiles per iteration");
 constexpr int RUNDIGITS_THREADS = 256;   // enc_rundigits
 
-// ---- encoder scans, tables and pack (nice_encode.hip) -----------------------
+// ---- encoder scans, tables (nice_encode.hip) and pack (nice_pack.hip) -------
 // the per-frame tile scans (enc_tailruns, enc_tilescan) run as blocks of
 // ENC_GROUP_TILES tiles; enc_group_reduce gives each group's aggregate
 constexpr uint32_t ENC_GROUP_TILES = 8192;

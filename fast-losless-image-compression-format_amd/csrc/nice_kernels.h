@@ -76,7 +76,8 @@ struct EncArgs {
   uint2* over_list;          // n_frames * ceil((tile_hi - tile_lo) / PACK_SUB)
 };
 
-// the classify family and enc_rundigits: nice_classify.hip; from enc_group_reduce on: nice_encode.hip
+// the classify family and enc_rundigits: nice_classify.hip; enc_tilebits, enc_tilescan, enc_packtab, enc_pack*,
+// enc_edges: nice_pack.hip; the rest from enc_group_reduce on: nice_encode.hip
 __global__ void enc_classify(EncArgs a);        // W >= 3
 __global__ void enc_classify_tiny(EncArgs a);   // W < 3
 __global__ void enc_classify_ring(EncArgs a);    // RGBA, 16K-pixel ring (W <= CLS_RING_MAX_W)

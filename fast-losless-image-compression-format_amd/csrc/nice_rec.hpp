@@ -26,16 +26,14 @@
 #include <stdint.h>
 
 #include "nice_format.h"
+#include "nice_pack.hpp"
 
 namespace nice {
 
 constexpr uint32_t C0_RGB = 0, C0_BR = 256, C0_SD = 261, C0_L2 = 604, C0_LUMA = 668, C0_UNC = 1372,
                    C0_N = 1436;
 constexpr uint32_t SX_RGB = 0, SX_L2 = 256, SX_LUMA = 288, SX_ABS = 320, SX_N = 384;
-// run digits (prefixes 5..12, code.rs:391-406) after a coded pixel, m = run - 1:
-// entries 0..63 the natural digits of m, 64 + x the two digits (x & 7, x >> 3)
-// of a longer run's first two, 128 no run
-constexpr uint32_t RC_TWO = 64, RC_NONE = 128, RC_N = 130;
+// (the run-digit entries RC_TWO, RC_NONE, RC_N: nice_pack.hpp, with rc_index)
 
 __host__ __device__ constexpr uint32_t rec2_abs(uint32_t lane) {
   return ((SX_ABS + lane) << 14) | ((SX_ABS + lane) << 23);

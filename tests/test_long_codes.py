@@ -15,14 +15,19 @@ import numpy as np
 import pytest
 
 # (w, h, channels, K): K Fibonacci-weighted symbols
-DEEP = [(2048, 2048, 4, 30), (2048, 1280, 3, 29), (2560, 2400, 4, 31)]
+# The last shape has W * H % 4 == 1 and a partial last tile of 521 pixels (the
+# others are whole tiles): the scalar record loads and the partial tile of
+# enc_tilebits / enc_pack_long.  Its counts are its own (below).
+DEEP = [(2048, 2048, 4, 30), (2048, 1280, 3, 29), (2560, 2400, 4, 31), (1539, 1027, 4, 28)]
+WHOLE, PARTIAL = DEEP[:3], DEEP[3]
+_IDS = [f"{w}x{h}x{c}k{k}" for w, h, c, k in DEEP]
 
 
 def _deep(O, w, h, c, k, seed=1):
     return O.gen_deep_codes(w, h, c, seed, k)
 
 
-@pytest.mark.parametrize("case", DEEP, ids=[f"{w}x{h}x{c}k{k}" for w, h, c, k in DEEP])
+@pytest.mark.parametrize("case", WHOLE, ids=_IDS[:3])
 def test_oracle_emits_long_and_wrapped_codes(O, case):
     w, h, c, k = case
     s, st = O.encode(_deep(O, w, h, c, k), w, h, c, with_stats=True)
@@ -34,8 +39,21 @@ def test_oracle_emits_long_and_wrapped_codes(O, case):
     assert st.max_aob[5] > 128
 
 
+def test_oracle_partial_tile_shape_emits_long_and_wrapped_codes(O):
+    """The partial-tile shape: fewer long codes than the whole-tile shapes, but
+    a long-code frame (over the 25 bits of the one-pass packer) with a wrapped
+    write, ending in a partial tile with a pixel count that is no multiple of 4."""
+    w, h, c, k = PARTIAL
+    assert (w * h) % 4 == 1 and (w * h) % 1024 == 521
+    s, st = O.encode(_deep(O, w, h, c, k), w, h, c, with_stats=True)
+    assert st.max_emitted_aob == 28
+    assert st.n_long_emits == 6
+    assert st.n_wrapped_emits == 1
+    assert st.max_aob[5] > 128
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize("case", DEEP, ids=[f"{w}x{h}x{c}k{k}" for w, h, c, k in DEEP])
+@pytest.mark.parametrize("case", DEEP, ids=_IDS)
 def test_long_codes_single_frame(nice, O, case):
     w, h, c, k = case
     px = _deep(O, w, h, c, k)

@@ -7,7 +7,7 @@ the prefetch and the stores ("waits").
 Usage: python tools/isa_audit.py [source.hip ...]"""
 import re, subprocess, sys, os
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-srcs = sys.argv[1:] or ["nice_encode.hip", "nice_classify.hip", "nice_decode.hip", "nice_rows.hip"]
+srcs = sys.argv[1:] or ["nice_encode.hip", "nice_pack.hip", "nice_classify.hip", "nice_decode.hip", "nice_rows.hip"]
 for src in srcs:
     path = os.path.join(root, "fast-losless-image-compression-format_amd", "csrc", os.path.basename(src))
     asm = subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC",
