@@ -30,7 +30,7 @@ __all__ = [
     "TiledImage", "TiledAlpha", "tiled_alpha_bound", "tile_grid", "tile_select", "tiled_bound", "encode_tiled", "decode_tiled", "save_tiled",
     "load_tiled", "DEFAULT_TILE",
     "ImageSet", "set_grid", "set_select", "set_bound", "set_alpha_bound", "encode_set", "decode_set", "save_set",
-    "load_set", "DEFAULT_SET_TILE", "decode_set_tensor", "normalize_affine",
+    "load_set", "DEFAULT_SET_TILE", "decode_set_tensor", "normalize_affine", "decode_set_resized",
     "DEC_STRICT_REFERENCE", "DEC_ALPHA_FILL_FF", "DEC_TOLERANT_HEADER",
 ]
 
@@ -65,9 +65,11 @@ EXPORTS = [
     "nice_encode_set_dev", "nice_decode_set_dev",
     "nice_set_alpha_bound", "nice_set_alpha_range_dev", "nice_encode_set_alpha_dev", "nice_decode_set_alpha_dev",
     "nice_set_merge_tensor_dev", "nice_decode_set_tensor_dev",
+    "nice_set_resize_tensor_dev", "nice_decode_set_resized_dev",
 ]
 TENSOR_F32, TENSOR_F16, TENSOR_BF16 = 0, 1, 2
 TENSOR_PLANAR, TENSOR_INTERLEAVED = 0, 1
+RESIZE_MAX = 8192
 
 
 class NiceError(RuntimeError):
@@ -153,6 +155,10 @@ def _signatures():
                                           u32, u32, p, p]),
         "nice_decode_set_tensor_dev": (i, [p, p, p, u64, p, p, p, p, p, u32, u32, u32, p, p, p, p, p, u32, u32, u32, p,
                                            p, u32, p]),
+        "nice_set_resize_tensor_dev": (i, [p, p, p, u64, p, p, p, p, p, u32, u32, u32, p, p, u32, u32, p, p, p, u32, u32,
+                                           u32, p, p]),
+        "nice_decode_set_resized_dev": (i, [p, p, p, u64, p, p, p, p, p, u32, u32, u32, p, p, u32, u32, p, p, p, u32, u32,
+                                            u32, p, p, u32, p]),
         "nice_pipe_create": (i, [i, u32, u32, u8, u32, u32, pp]),
         "nice_pipe_destroy": (None, [p]),
         "nice_pipe_stream_stride": (u64, [p]),
@@ -1266,6 +1272,96 @@ def decode_set_tensor(iset: ImageSet, images=None, windows=None, out=None, dtype
         (ctypes.c_float * 3)(*bias), flags, _p(status))
     _check(rc, "nice_decode_set_tensor_dev")
     return _decode_tail(stream, [("nice_decode_set_tensor_dev", status)], result, alpha_field=False)
+
+
+def decode_set_resized(iset: ImageSet, windows=None, images=None, size=None, out=None, dtype=None,
+                       scale=(1 / 255,) * 3, bias=(0.,) * 3, flip=None, channels_last: bool = False,
+                       flags: int = DEC_ALPHA_FILL_FF, stream=None, ctx: "_Ctx | None" = None):
+    """``decode_set_tensor`` with every window resampled to one ``size`` =
+    (oh, ow), whatever its own size: a random resized crop per window, from the
+    packed set to one cuda tensor [M, 3, oh, ow] of ``dtype`` (float16 by
+    default) that the call allocates, or ``out``: such a batch tensor or a list
+    of M tensors [3, oh, ow], whose strides decide the layout exactly as in
+    ``decode_set_tensor``.  ``windows`` / ``images``, ``scale``, ``bias``,
+    ``flip``, ``channels_last`` and ``flags`` are ``decode_set_tensor``'s; each
+    of ``oh``, ``ow`` is 1..8192.
+
+    The value is defined exactly and compares bit for bit: fixed-point
+    bilinear sampling with 8 fractional bits of position, and no antialiasing
+    (a strong reduction aliases, as ``interpolate(antialias=False)`` does).
+    For an output axis of ``n_out`` elements over a window axis of ``n_in``
+    pixels, output index ``x`` samples at the integer ``q`` (in 1/256 pixel;
+    integer arithmetic, floor division)::
+
+        t  = ((2x + 1) * n_in * 256 + n_out) // (2 * n_out)
+        q  = min(max(t - 128, 0), (n_in - 1) * 256)
+        i0 = q >> 8;  f = q & 255;  i1 = min(i0 + (f != 0), n_in - 1)
+
+    Indices are relative to the window and clamp to the window, not the image;
+    a mirrored window takes the column position of ``ow - 1 - x``.  With
+    (i0, i1, fx) of the column, (j0, j1, fy) of the row and b the byte of
+    channel c::
+
+        acc = (256 - fy) * ((256 - fx) * b[j0][i0] + fx * b[j0][i1]) + fy * ((256 - fx) * b[j1][i0] + fx * b[j1][i1])
+        v   = fmaf(float32(acc) * 2**-16, scale[c], bias[c])
+
+    in float32 with the one rounding of the fmaf, stored as float32 or rounded
+    to nearest even to ``dtype``.  A window of the output's size gives
+    ``decode_set_tensor``'s bits; an exact halving gives the mean of each
+    2 x 2 block.  The sampling happens in the one merge launch: no uint8 crop
+    and no float32 temporary exist, and the number of launches does not depend
+    on M.  An element is written iff every tile one of its taps falls in
+    decoded; errors, ``.statuses``, ``.out`` and the wait are
+    ``decode_set_tensor``'s."""
+    import torch
+    who = "decode_set_resized"
+    dtype = torch.float16 if dtype is None else dtype
+    dt = {torch.float32: TENSOR_F32, torch.float16: TENSOR_F16, torch.bfloat16: TENSOR_BF16}.get(dtype)
+    if dt is None:
+        raise NiceError(E_ARG, f"{who}: dtype must be torch.float32, torch.float16 or torch.bfloat16")
+    try:
+        oh, ow = (int(v) for v in size)
+    except (TypeError, ValueError):
+        raise NiceError(E_ARG, f"{who}: size must be (oh, ow)") from None
+    if not (1 <= oh <= RESIZE_MAX and 1 <= ow <= RESIZE_MAX):
+        raise NiceError(E_ARG, f"{who}: size must be within 1..{RESIZE_MAX} on both axes")
+    windows, m, slot_first, n = _set_windows(who, iset, images, windows)
+    packed = iset.packed
+    tables = _host_tables(torch, who, iset, n)
+    scale, bias = [_f32(v) for v in scale], [_f32(v) for v in bias]
+    if len(scale) != 3 or len(bias) != 3:
+        raise NiceError(E_ARG, f"{who}: scale and bias have three entries each")
+    flips = [0] * m if flip is None else [1 if f else 0 for f in flip]
+    if len(flips) != m:
+        raise NiceError(E_ARG, f"{who}: flip must have one entry per window")
+    dev = packed.device
+    shape_msg = f"{who}: out must be [M, 3, oh, ow] or a list of M tensors [3, oh, ow]"
+    if out is None:   # one batch tensor, in the memory format asked for
+        out = (torch.empty((m, oh, ow, 3), dtype=dtype, device=dev).permute(0, 3, 1, 2) if channels_last else
+               torch.empty((m, 3, oh, ow), dtype=dtype, device=dev))
+    outs, result = _set_outputs(out, windows, None, shape_msg)
+    for o in outs:
+        if not hasattr(o, "dim") or o.dim() != 3 or tuple(o.shape) != (3, oh, ow):
+            raise NiceError(E_ARG, shape_msg)
+        if o.dtype != dtype or not o.is_cuda or o.device != dev:
+            raise NiceError(E_ARG, f"{who}: out must have the dtype asked for, on the set's device")
+    # one layout per call: the first that every output's strides fit
+    for layout in (TENSOR_PLANAR, TENSOR_INTERLEAVED):
+        pitches = [_tensor_pitches(o, layout) for o in outs]
+        if all(v is not None for v in pitches):
+            break
+    else:
+        raise NiceError(E_ARG, f"{who}: the outputs' strides must all be planar (innermost 1) or all interleaved "
+                               "(channel stride 1, innermost 3)")
+    status = torch.full((slot_first[m],), 99, dtype=torch.int32, device=dev)
+    rc = lib().nice_decode_set_resized_dev(
+        *_launch(torch, dev, stream, ctx), _p(packed), int(tables[0][n]), *map(_p, tables),
+        *_set_geom(iset.widths, iset.heights, iset.tile_w, iset.tile_h), _win_array(windows),
+        (ctypes.c_uint8 * m)(*flips), ow, oh, *_images(outs, [v[0] for v in pitches]),
+        (ctypes.c_uint64 * m)(*[v[1] for v in pitches]), m, dt, layout, (ctypes.c_float * 3)(*scale),
+        (ctypes.c_float * 3)(*bias), flags, _p(status))
+    _check(rc, "nice_decode_set_resized_dev")
+    return _decode_tail(stream, [("nice_decode_set_resized_dev", status)], result, alpha_field=False)
 
 
 # Host-side container of an image set: one file, little-endian throughout

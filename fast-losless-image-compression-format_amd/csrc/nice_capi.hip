@@ -21,6 +21,8 @@
 #include "nice_enc_plan.hpp"
 #include "nice_slot_plan.hpp"
 #include "nice_rec.hpp"
+#include "nice_resize.hpp"
+#include "nice_tiles.hpp"
 #include "nice_internal.h"
 
 using namespace nice;
@@ -173,6 +175,7 @@ struct nice_ctx {
   Arena tiles, tile_dec, tile_tab;
   uint32_t last_tiled_coded = 0, last_tiled_raw = 0;   // test hook nice_test_last_tiled
   uint32_t last_set_coded = 0, last_set_raw = 0;       // test hook nice_test_last_set
+  uint32_t last_set_merges = 0;                         // test hook nice_test_last_set_merges
   uint32_t last_set_alpha_coded = 0, last_set_alpha_raw = 0, last_set_alpha_const = 0;   // nice_test_last_set_alpha
   PhaseTimer timer;
   BandState bs;
@@ -1575,6 +1578,7 @@ int nice_decode_set_tensor_dev(nice_ctx* ctx, void* stream, const uint8_t* d_pac
                               nx.data(), h_win, M, wins.data(), M * sizeof(SetTensorWindow), 4, flags, d_status, d)))
     return rc;
   const SetTensorWindow* d_wins = (const SetTensorWindow*)d.head;
+  ctx->last_set_merges = (d.nc ? 1u : 0u) + (d.ns ? 1u : 0u);
   if (d.nc) {
     if ((rc = nice::set_merge_tensor_launch(stream, d.dec, d.stride, nullptr, d.c_win, d.c_idx, d.c_st, d.nc, d_wins, M,
                                             tile_w, tile_h, 4, dtype, layout, scale, bias)))
@@ -1586,6 +1590,102 @@ int nice_decode_set_tensor_dev(nice_ctx* ctx, void* stream, const uint8_t* d_pac
       return rc;
   }
   return NICE_OK;
+}
+
+// ---- image sets: resized tensor output ------------------------------------------
+namespace {
+// The resize windows of M windows (set and windows checked: set_select, which
+// gave slot_first): outputs of out_h x out_w per channel, checked as
+// set_tensor_window_table checks its own.
+int set_resize_window_table(const uint32_t* h_w, const uint32_t* h_h, uint32_t tile_w, uint32_t tile_h,
+                            const uint32_t* h_win, const uint8_t* h_flip, const uint32_t* slot_first, uint32_t out_w,
+                            uint32_t out_h, void* const* h_out, const uint64_t* h_row_pitch,
+                            const uint64_t* h_plane_pitch, uint32_t M, uint32_t dtype, uint32_t layout,
+                            std::vector<SetResizeWindow>& tab) {
+  const uint32_t es = nice::set_tensor_elem_bytes(dtype);
+  const bool planar = layout == NICE_TENSOR_PLANAR;
+  if (out_w == 0 || out_h == 0 || out_w > nice::RESIZE_MAX_OUT || out_h > nice::RESIZE_MAX_OUT) return NICE_E_ARG;
+  if (!h_out || !h_row_pitch || (planar && !h_plane_pitch)) return NICE_E_ARG;
+  tab.resize(M);
+  for (uint32_t j = 0; j < M; ++j) {
+    const uint32_t* q = h_win + 5ull * j;
+    if (!h_out[j] || ((uintptr_t)h_out[j] & (es - 1))) return NICE_E_ARG;
+    if (h_row_pitch[j] < (uint64_t)out_w * (planar ? 1u : 3u)) return NICE_E_ARG;
+    const TileRange r = nice::window_tiles(tile_w, tile_h, q[1], q[2], q[3], q[4]);
+    const uint64_t pp = planar ? h_plane_pitch[j] : 0;
+    tab[j] = SetResizeWindow{h_out[j], h_row_pitch[j], pp, q[1], q[2], q[3], q[4], r.tx0, r.ty0, r.tx1 - r.tx0,
+                             slot_first[j], nice::set_resize_window_mode(h_out[j], h_row_pitch[j], pp, dtype, layout),
+                             (h_flip && h_flip[j]) ? 1u : 0u};
+  }
+  return NICE_OK;
+}
+}  // namespace
+
+int nice_set_resize_tensor_dev(nice_ctx* ctx, void* stream, const uint8_t* d_tiles, uint64_t tile_stride,
+                               const uint8_t* d_packed, const uint64_t* d_src, const int32_t* d_slot_status,
+                               const uint32_t* h_w, const uint32_t* h_h, uint32_t K, uint32_t tile_w, uint32_t tile_h,
+                               const uint32_t* h_win, const uint8_t* h_flip, uint32_t out_w, uint32_t out_h,
+                               void* const* h_out, const uint64_t* h_row_pitch, const uint64_t* h_plane_pitch,
+                               uint32_t M, uint32_t dtype, uint32_t layout, const float* scale, const float* bias) {
+  if (!ctx || !d_src) return NICE_E_ARG;
+  int rc = set_tensor_check(dtype, layout, scale, bias);
+  if (rc) return rc;
+  std::vector<uint32_t> slot_first((size_t)M + 1);
+  if ((rc = nice_set_select(h_w, h_h, K, tile_w, tile_h, h_win, M, slot_first.data()))) return rc;
+  std::vector<SetResizeWindow> tab;
+  if ((rc = set_resize_window_table(h_w, h_h, tile_w, tile_h, h_win, h_flip, slot_first.data(), out_w, out_h, h_out,
+                                    h_row_pitch, h_plane_pitch, M, dtype, layout, tab)))
+    return rc;
+  // dense slots are read as dwords
+  if (d_tiles && (!nice::tl_aligned(d_tiles, tile_stride, 4) || tile_stride < (uint64_t)tile_w * tile_h * 4))
+    return NICE_E_ARG;
+  NICE_HIP(hipSetDevice(ctx->device));
+  if ((rc = ctx->tile_tab.grow(M * sizeof(SetResizeWindow)))) return rc;
+  NICE_HIP(hipMemcpyAsync(ctx->tile_tab.ptr, tab.data(), M * sizeof(SetResizeWindow), hipMemcpyHostToDevice,
+                          (hipStream_t)stream));
+  return nice::set_resize_tensor_launch(stream, d_tiles, tile_stride, d_packed, d_src, d_slot_status,
+                                        (const SetResizeWindow*)ctx->tile_tab.ptr, M, tile_w, tile_h, out_w, out_h,
+                                        dtype, layout, scale, bias);
+}
+
+int nice_decode_set_resized_dev(nice_ctx* ctx, void* stream, const uint8_t* d_packed, uint64_t packed_bytes,
+                                const uint64_t* h_off, const uint64_t* h_len, const uint8_t* h_kind,
+                                const uint32_t* h_w, const uint32_t* h_h, uint32_t K, uint32_t tile_w, uint32_t tile_h,
+                                const uint32_t* h_win, const uint8_t* h_flip, uint32_t out_w, uint32_t out_h,
+                                void* const* h_out, const uint64_t* h_row_pitch, const uint64_t* h_plane_pitch,
+                                uint32_t M, uint32_t dtype, uint32_t layout, const float* scale, const float* bias,
+                                uint32_t flags, int32_t* d_status) {
+  if (!ctx || !d_packed || !h_off || !h_len || !h_kind || !d_status) return NICE_E_ARG;
+  if ((flags & NICE_DEC_STRICT_REFERENCE) || ((uintptr_t)d_packed & 15)) return NICE_E_ARG;
+  int rc = set_tensor_check(dtype, layout, scale, bias);
+  if (rc) return rc;
+  std::vector<uint32_t> first, nx, slot_first((size_t)M + 1);
+  if ((rc = nice::set_select(h_w, h_h, K, tile_w, tile_h, h_win, M, first, nx, slot_first.data()))) return rc;
+  std::vector<SetResizeWindow> wins;
+  if ((rc = set_resize_window_table(h_w, h_h, tile_w, tile_h, h_win, h_flip, slot_first.data(), out_w, out_h, h_out,
+                                    h_row_pitch, h_plane_pitch, M, dtype, layout, wins)))
+    return rc;
+  NICE_HIP(hipSetDevice(ctx->device));
+  // the plan first: its position column travels in the head, behind the window descriptors
+  DevSlots d;
+  plan_colour_slots(SlotTables{h_off, h_len, h_kind, nullptr, packed_bytes},
+                    SlotWindows{tile_w, tile_h, first.data(), nx.data(), h_win, M, true}, d.plan);
+  ctx->last_set_coded = d.plan.by_kind[0];
+  ctx->last_set_raw = d.plan.by_kind[1];
+  std::vector<uint64_t> src;
+  nice::slot_position_sources(d.plan, src);
+  const size_t wins_bytes = M * sizeof(SetResizeWindow);
+  std::vector<uint8_t> head(wins_bytes + 8 * src.size());
+  memcpy(head.data(), wins.data(), wins_bytes);
+  if (!src.empty()) memcpy(head.data() + wins_bytes, src.data(), 8 * src.size());
+  // the coded slots at 4 bytes per pixel, whatever the set's channels: a tap is one dword
+  if ((rc = decode_planned_slots(ctx, stream, d_packed, packed_bytes, head.data(), head.size(), tile_w, tile_h, 4,
+                                 (flags & NICE_DEC_ALPHA_FILL_FF) | NICE_DEC_TOLERANT_HEADER, d_status, d)))
+    return rc;
+  ctx->last_set_merges = 1;
+  return nice::set_resize_tensor_launch(stream, d.dec, d.stride, d_packed, (const uint64_t*)(d.head + wins_bytes),
+                                        d_status, (const SetResizeWindow*)d.head, M, tile_w, tile_h, out_w, out_h,
+                                        dtype, layout, scale, bias);
 }
 
 // ---- image sets: the alpha batch ---------------------------------------------
@@ -2047,6 +2147,12 @@ int nice_test_last_set(nice_ctx* ctx, uint32_t* coded, uint32_t* raw) {
   if (!ctx || !coded || !raw) return NICE_E_ARG;
   *coded = ctx->last_set_coded;
   *raw = ctx->last_set_raw;
+  return NICE_OK;
+}
+
+int nice_test_last_set_merges(nice_ctx* ctx, uint32_t* launches) {
+  if (!ctx || !launches) return NICE_E_ARG;
+  *launches = ctx->last_set_merges;
   return NICE_OK;
 }
 

@@ -140,6 +140,32 @@ int set_merge_tensor_launch(void* stream, const uint8_t* d_tiles, uint64_t tile_
                             uint32_t tile_h, uint32_t tile_channels, uint32_t dtype, uint32_t layout, const float* scale,
                             const float* bias);
 
+// ---- image sets: resized tensor output (nice_sets_resize.hip) -------------------
+// A window of the resize merge: its out_h x out_w elements per channel laid out
+// as SetTensorWindow's; its slots are slot_first + (ty - ty0) * ntx + (tx - tx0)
+// for the tiles tx0 <= tx < tx0 + ntx, ty0 <= ty of its image.  mode: log2 of
+// the consecutive output columns a lane stores as one vector per plane, the
+// best the base, the pitches and the element size allow.
+struct SetResizeWindow {
+  void* out;
+  uint64_t row_pitch, plane_pitch;
+  uint32_t x0, y0, rw, rh;      // the rectangle, inside its image
+  uint32_t tx0, ty0, ntx;       // its tiles
+  uint32_t slot_first;
+  uint32_t mode, flip;
+};
+uint32_t set_resize_window_mode(const void* d_out, uint64_t row_pitch, uint64_t plane_pitch, uint32_t dtype,
+                                uint32_t layout);
+// Every element of the n_wins windows from the slots its taps fall in (d_src[p]
+// as slot_position_sources gives it: dense slots at d_tiles + value *
+// tile_stride, dwords; raw slots at d_packed + value).  An element with a tap
+// in a slot whose d_slot_status[p] != 0 (may be null) or whose source is
+// neither dense nor raw is not written.  One launch.
+int set_resize_tensor_launch(void* stream, const uint8_t* d_tiles, uint64_t tile_stride, const uint8_t* d_packed,
+                             const uint64_t* d_src, const int32_t* d_slot_status, const SetResizeWindow* d_wins,
+                             uint32_t n_wins, uint32_t tile_w, uint32_t tile_h, uint32_t out_w, uint32_t out_h,
+                             uint32_t dtype, uint32_t layout, const float* scale, const float* bias);
+
 // ---- the alpha batch of an image set (nice_sets.hip) --------------------------
 // The set forms of alpha_range_launch, alpha_gather_launch and alpha_merge_launch
 // above: tiles are global tile indices, their images (RGBA) come from d_imgs.

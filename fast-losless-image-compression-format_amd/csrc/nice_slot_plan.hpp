@@ -207,6 +207,21 @@ inline void plan_alpha_slots(const SlotTables& t, const SlotWindows& g, SlotPlan
   });
 }
 
+// ---- where every position's pixels are (the resize merge, nice_sets_resize.hip) ----
+// src[p] of a colour plan, for every slot position p: bits 62-63 the kind, bits
+// 0-61 the value.  Dense: 4 bytes per pixel, the value-th coded slot of the
+// batch decode (in c_pos order); raw: 3 bytes per pixel at that byte offset of
+// the packed batch (s_src, in order); none: refused by the plan, nothing to read.
+constexpr uint64_t SLOT_SRC_DENSE = 0ull << 62, SLOT_SRC_RAW = 1ull << 62, SLOT_SRC_NONE = 3ull << 62;
+constexpr uint64_t SLOT_SRC_VALUE = (1ull << 62) - 1;
+inline void slot_position_sources(const SlotPlan& s, std::vector<uint64_t>& src) {
+  src.assign(s.init.size(), SLOT_SRC_NONE);
+  for (size_t k = 0; k < s.c_pos.size(); ++k) src[s.c_pos[k]] = SLOT_SRC_DENSE | (uint64_t)k;
+  size_t r = 0;
+  for (size_t p = 0; p < src.size(); ++p)
+    if (src[p] == SLOT_SRC_NONE && s.init[p] == NICE_OK) src[p] = SLOT_SRC_RAW | (s.s_src[r++] & SLOT_SRC_VALUE);
+}
+
 // ---- one host buffer for the upload -------------------------------------------
 // `head` (the callers' window descriptors; head_bytes a multiple of 8), then
 // the plan's u64 columns, its u32 columns, its u8 column; host.size() == c_st,

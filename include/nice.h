@@ -566,6 +566,85 @@ int nice_decode_set_tensor_dev(nice_ctx* ctx, void* stream, const uint8_t* d_pac
                                uint32_t dtype, uint32_t layout, const float* scale, const float* bias,
                                uint32_t flags, int32_t* d_status /* slot_first[M] */);
 
+/* ---- image sets: resized tensor output ----
+ * "image sets: tensor output" with every window resampled to one size,
+ * out_h x out_w, whatever its own: the random resized crop of a training
+ * loader, from the packed set to [M, 3, out_h, out_w] in one call.  Dtypes,
+ * layouts, pitches, h_flip, scale and bias are the tensor output's; window j
+ * is out_w x out_h elements per channel at h_out[j] (h_row_pitch[j] >= out_w,
+ * interleaved >= 3 * out_w).
+ *
+ * The value is defined exactly, so results compare bit for bit: fixed-point
+ * bilinear sampling with 8 fractional bits of position and no antialiasing (a
+ * strong reduction aliases, as torch's antialias=False does).  For an output
+ * axis of n_out elements over a window axis of n_in pixels the position of
+ * output index x is the integer q, in 1/256 of a pixel (64-bit unsigned
+ * arithmetic, floor division; the subtraction stops at 0):
+ *   t  = ((2x + 1) * n_in * 256 + n_out) / (2 * n_out)   nearest 1/256 to (x + 1/2) * n_in / n_out, halves up
+ *   q  = clamp(t - 128, 0, (n_in - 1) * 256)             minus the half pixel
+ *   i0 = q >> 8,  f = q & 255,  i1 = min(i0 + (f != 0), n_in - 1)
+ * Indices are relative to the window and the clamp is to the window, not the
+ * image: a resized window reads no pixel outside itself and touches exactly
+ * the tiles nice_set_select reports for it.  A mirrored window computes the
+ * column position from out_w - 1 - x.  With (i0, i1, fx) for the column,
+ * (j0, j1, fy) for the row and b the byte of channel c,
+ *   acc = (256 - fy) * ((256 - fx) * b[j0][i0] + fx * b[j0][i1])
+ *       +        fy  * ((256 - fx) * b[j1][i0] + fx * b[j1][i1])
+ *   v   = fmaf((float)acc * 0x1p-16f, scale[c], bias[c])
+ * acc <= 255 * 65536 < 2^24, so the conversion and the scaling by 2^-16 are
+ * exact and the fmaf is the one rounding.  NICE_TENSOR_F32 stores v, the
+ * 16-bit types v rounded to nearest even.  Where out_w == rw and out_h == rh,
+ * f is 0 everywhere, acc = b << 16, and the result is the tensor output's bit
+ * for bit; an exact halving of both axes gives the mean of each 2 x 2 block.
+ *
+ * An element is written iff every slot one of its taps falls in has status
+ * NICE_OK and a readable source (a tap of weight 0 coincides with its
+ * neighbour, so an element of an unresized window depends on one slot); else
+ * it is left untouched.  Nothing outside a window's 3 * out_h * out_w elements
+ * is written.  NICE_E_ARG besides the errors of the tensor calls: out_w or
+ * out_h 0 or above NICE_RESIZE_MAX. */
+#define NICE_RESIZE_MAX 8192u
+/* the kinds of d_src, its bits 62-63 */
+#define NICE_SRC_DENSE 0u
+#define NICE_SRC_RAW   1u
+#define NICE_SRC_NONE  3u
+/* The kernel alone.  d_src: slot_first[M] u64 in device memory, one per slot
+ * in nice_set_select's order, saying where the slot's pixels are:
+ *   bits 62-63  0 dense, 4 bytes per pixel (byte +3 ignored) at d_tiles + value * tile_stride
+ *                 (d_tiles and tile_stride multiples of 4: a tap is one dword load)
+ *               1 raw, 3 bytes per pixel at d_packed + value
+ *               3 nothing to read (2 is read as 3)
+ *   bits 0-61   value
+ * d_slot_status: slot_first[M] codes, or null (all NICE_OK).  Dense or raw is
+ * decided per tap by d_src, so there is one launch whatever M is and whatever
+ * the slots are.  A lane owns 1, 2 or 4 consecutive output columns, whose
+ * positions it computes once per block, and stores them per plane as one store
+ * of 4, 8 or 16 bytes as far as the window's base and pitches allow; every
+ * other window goes element by element, in the same launch.  Asynchronous after the
+ * upload of the M window descriptors. */
+int nice_set_resize_tensor_dev(nice_ctx* ctx, void* stream, const uint8_t* d_tiles, uint64_t tile_stride,
+                               const uint8_t* d_packed, const uint64_t* d_src /* slot_first[M] */,
+                               const int32_t* d_slot_status /* slot_first[M], or null */, const uint32_t* h_w,
+                               const uint32_t* h_h, uint32_t K, uint32_t tile_w, uint32_t tile_h,
+                               const uint32_t* h_win, const uint8_t* h_flip /* M, or null */, uint32_t out_w,
+                               uint32_t out_h, void* const* h_out, const uint64_t* h_row_pitch,
+                               const uint64_t* h_plane_pitch /* planar only */, uint32_t M, uint32_t dtype,
+                               uint32_t layout, const float* scale /* 3 */, const float* bias /* 3 */);
+/* nice_decode_set_tensor_dev with out_w, out_h and the one resize launch in
+ * place of the two tensor merges: the same host tables, slots, per-slot
+ * statuses and their order, host-side refusals and flags; coded slots decoded
+ * at 4 bytes per pixel, raw slots read in place.  One upload (the position
+ * column d_src travels behind the window descriptors), one batch decode over
+ * the coded slots, one status scatter, one resize launch: the number of
+ * launches depends on neither K nor M. */
+int nice_decode_set_resized_dev(nice_ctx* ctx, void* stream, const uint8_t* d_packed, uint64_t packed_bytes,
+                                const uint64_t* h_off, const uint64_t* h_len, const uint8_t* h_kind,
+                                const uint32_t* h_w, const uint32_t* h_h, uint32_t K, uint32_t tile_w, uint32_t tile_h,
+                                const uint32_t* h_win, const uint8_t* h_flip, uint32_t out_w, uint32_t out_h,
+                                void* const* h_out, const uint64_t* h_row_pitch, const uint64_t* h_plane_pitch,
+                                uint32_t M, uint32_t dtype, uint32_t layout, const float* scale, const float* bias,
+                                uint32_t flags, int32_t* d_status /* slot_first[M] */);
+
 /* ---- one image sharded over ranks (config 4) ----
  * The image's raster is cut into bands of whole encoder tiles (1024 pixels in
  * raster order); rank r encodes tiles [tile_lo, tile_hi).  The caller runs the

@@ -55,6 +55,10 @@ int nice_test_last_tiled(struct nice_ctx* ctx, uint32_t* coded, uint32_t* raw);
  * window and tile the window touches) decoded as streams and expanded from raw
  * pixels, minus those refused on the host */
 int nice_test_last_set(struct nice_ctx* ctx, uint32_t* coded, uint32_t* raw);
+/* the merge launches of the context's last nice_decode_set_tensor_dev (one
+ * for its coded slots, one for its raw slots, each only if there are any) or
+ * nice_decode_set_resized_dev (one) */
+int nice_test_last_set_merges(struct nice_ctx* ctx, uint32_t* launches);
 /* the slots of the context's last nice_decode_set_alpha_dev by kind: decoded as
  * streams, read from raw planes, constant; minus those refused on the host */
 int nice_test_last_set_alpha(struct nice_ctx* ctx, uint32_t* coded, uint32_t* raw, uint32_t* constant);
