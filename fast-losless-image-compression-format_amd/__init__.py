@@ -66,10 +66,12 @@ EXPORTS = [
     "nice_set_alpha_bound", "nice_set_alpha_range_dev", "nice_encode_set_alpha_dev", "nice_decode_set_alpha_dev",
     "nice_set_merge_tensor_dev", "nice_decode_set_tensor_dev",
     "nice_set_resize_tensor_dev", "nice_decode_set_resized_dev",
+    "nice_set_resize_aa_tensor_dev", "nice_decode_set_resized_aa_dev",
 ]
 TENSOR_F32, TENSOR_F16, TENSOR_BF16 = 0, 1, 2
 TENSOR_PLANAR, TENSOR_INTERLEAVED = 0, 1
 RESIZE_MAX = 8192
+RESIZE_AA_MAX_IN = 65536
 
 
 class NiceError(RuntimeError):
@@ -159,6 +161,10 @@ def _signatures():
                                            u32, p, p]),
         "nice_decode_set_resized_dev": (i, [p, p, p, u64, p, p, p, p, p, u32, u32, u32, p, p, u32, u32, p, p, p, u32, u32,
                                             u32, p, p, u32, p]),
+        "nice_set_resize_aa_tensor_dev": (i, [p, p, p, u64, p, p, p, p, p, u32, u32, u32, p, p, u32, u32, p, p, p, u32,
+                                              u32, u32, p, p]),
+        "nice_decode_set_resized_aa_dev": (i, [p, p, p, u64, p, p, p, p, p, u32, u32, u32, p, p, u32, u32, p, p, p, u32,
+                                               u32, u32, p, p, u32, p]),
         "nice_pipe_create": (i, [i, u32, u32, u8, u32, u32, pp]),
         "nice_pipe_destroy": (None, [p]),
         "nice_pipe_stream_stride": (u64, [p]),
@@ -1276,7 +1282,8 @@ def decode_set_tensor(iset: ImageSet, images=None, windows=None, out=None, dtype
 
 def decode_set_resized(iset: ImageSet, windows=None, images=None, size=None, out=None, dtype=None,
                        scale=(1 / 255,) * 3, bias=(0.,) * 3, flip=None, channels_last: bool = False,
-                       flags: int = DEC_ALPHA_FILL_FF, stream=None, ctx: "_Ctx | None" = None):
+                       flags: int = DEC_ALPHA_FILL_FF, stream=None, ctx: "_Ctx | None" = None,
+                       antialias: bool = False):
     """``decode_set_tensor`` with every window resampled to one ``size`` =
     (oh, ow), whatever its own size: a random resized crop per window, from the
     packed set to one cuda tensor [M, 3, oh, ow] of ``dtype`` (float16 by
@@ -1312,7 +1319,36 @@ def decode_set_resized(iset: ImageSet, windows=None, images=None, size=None, out
     and no float32 temporary exist, and the number of launches does not depend
     on M.  An element is written iff every tile one of its taps falls in
     decoded; errors, ``.statuses``, ``.out`` and the wait are
-    ``decode_set_tensor``'s."""
+    ``decode_set_tensor``'s.
+
+    ``antialias=True`` filters a reducing axis instead of sampling it: the
+    triangle filter of support ``n_in / n_out`` that
+    ``interpolate(bilinear, antialias=True)`` and PIL's resize apply, in
+    integers and as exactly defined.  Each axis is treated separately.  An
+    axis with ``n_out >= n_in`` keeps the taps above with the weights
+    ``16 * (256 - f)`` on ``i0`` and ``16 * f`` on ``i1`` (in 1/4096; one tap
+    where ``f == 0``).  An axis with ``n_out < n_in`` must have
+    ``n_in <= 65536`` (``RESIZE_AA_MAX_IN``; else NiceError(E_ARG)); for
+    output index ``x`` (mirrored: ``ow - 1 - x``)::
+
+        C = (2x + 1) * n_in;  P_i = (2i + 1) * n_out;  S = 2 * n_in
+        r_i = S - |P_i - C|                     the taps: the i with r_i > 0, one run lo..hi inside the window
+        W_i = (cum * 8192 + R) // (2 * R)       cum = r_lo + ... + r_i, R = the sum over the run   [(cum * 8192 + R) / (2 * R), floor]
+        w_i = W_i - W_(i-1),  W_(lo-1) = 0      sums to 4096 exactly, none negative
+
+    and with column taps (i, w_i), row taps (j, v_j)::
+
+        h[j]  = sum_i w_i * b[j][i]
+        acc32 = sum_j v_j * h[j]
+        acc   = (acc32 + 128) >> 8
+        v     = fmaf(float32(acc) * 2**-16, scale[c], bias[c])
+
+    A window that reduces on neither axis gives the bits of
+    ``antialias=False``; an exact halving has the interior weights 512, 1536,
+    1536, 512 (the support-2 triangle, not the block mean).  An element is
+    written iff every tile its tap rectangle (columns lo..hi by rows lo..hi)
+    meets decoded.  The resampling takes two launches whatever M is: the
+    weights, computed on the device, and the separable filter."""
     import torch
     who = "decode_set_resized"
     dtype = torch.float16 if dtype is None else dtype
@@ -1354,14 +1390,15 @@ def decode_set_resized(iset: ImageSet, windows=None, images=None, size=None, out
         raise NiceError(E_ARG, f"{who}: the outputs' strides must all be planar (innermost 1) or all interleaved "
                                "(channel stride 1, innermost 3)")
     status = torch.full((slot_first[m],), 99, dtype=torch.int32, device=dev)
-    rc = lib().nice_decode_set_resized_dev(
+    name = "nice_decode_set_resized_aa_dev" if antialias else "nice_decode_set_resized_dev"
+    rc = getattr(lib(), name)(
         *_launch(torch, dev, stream, ctx), _p(packed), int(tables[0][n]), *map(_p, tables),
         *_set_geom(iset.widths, iset.heights, iset.tile_w, iset.tile_h), _win_array(windows),
         (ctypes.c_uint8 * m)(*flips), ow, oh, *_images(outs, [v[0] for v in pitches]),
         (ctypes.c_uint64 * m)(*[v[1] for v in pitches]), m, dt, layout, (ctypes.c_float * 3)(*scale),
         (ctypes.c_float * 3)(*bias), flags, _p(status))
-    _check(rc, "nice_decode_set_resized_dev")
-    return _decode_tail(stream, [("nice_decode_set_resized_dev", status)], result, alpha_field=False)
+    _check(rc, name)
+    return _decode_tail(stream, [(name, status)], result, alpha_field=False)
 
 
 # Host-side container of an image set: one file, little-endian throughout

@@ -173,6 +173,7 @@ struct nice_ctx {
   // tiled images: the split tiles, the decoded tiles, and the small tables
   // (gathered offsets, tile indices, statuses) of one call
   Arena tiles, tile_dec, tile_tab;
+  Arena aa_weights;                                     // the weight tables of the antialiased resize
   uint32_t last_tiled_coded = 0, last_tiled_raw = 0;   // test hook nice_test_last_tiled
   uint32_t last_set_coded = 0, last_set_raw = 0;       // test hook nice_test_last_set
   uint32_t last_set_merges = 0;                         // test hook nice_test_last_set_merges
@@ -248,6 +249,7 @@ void nice_ctx_destroy(nice_ctx* ctx) {
   ctx->tiles.release();
   ctx->tile_dec.release();
   ctx->tile_tab.release();
+  ctx->aa_weights.release();
   ctx->timer.release();
   (void)hipSetDevice(prev);
   delete ctx;
@@ -1621,50 +1623,50 @@ int set_resize_window_table(const uint32_t* h_w, const uint32_t* h_h, uint32_t t
 }
 }  // namespace
 
-int nice_set_resize_tensor_dev(nice_ctx* ctx, void* stream, const uint8_t* d_tiles, uint64_t tile_stride,
-                               const uint8_t* d_packed, const uint64_t* d_src, const int32_t* d_slot_status,
-                               const uint32_t* h_w, const uint32_t* h_h, uint32_t K, uint32_t tile_w, uint32_t tile_h,
-                               const uint32_t* h_win, const uint8_t* h_flip, uint32_t out_w, uint32_t out_h,
-                               void* const* h_out, const uint64_t* h_row_pitch, const uint64_t* h_plane_pitch,
-                               uint32_t M, uint32_t dtype, uint32_t layout, const float* scale, const float* bias) {
+extern "C++" {
+namespace {
+// What the resize entry points share; Win is the window descriptor of the kernel.
+// The kernel alone: the checks, the windows (table(slot_first, tab)), their
+// upload, then launch(d_wins).
+template <class Win, class Table, class Launch>
+int set_resize_alone(nice_ctx* ctx, void* stream, const uint8_t* d_tiles, uint64_t tile_stride, const uint64_t* d_src,
+                     const uint32_t* h_w, const uint32_t* h_h, uint32_t K, uint32_t tile_w, uint32_t tile_h,
+                     const uint32_t* h_win, uint32_t M, uint32_t dtype, uint32_t layout, const float* scale,
+                     const float* bias, Table table, Launch launch) {
   if (!ctx || !d_src) return NICE_E_ARG;
   int rc = set_tensor_check(dtype, layout, scale, bias);
   if (rc) return rc;
   std::vector<uint32_t> slot_first((size_t)M + 1);
   if ((rc = nice_set_select(h_w, h_h, K, tile_w, tile_h, h_win, M, slot_first.data()))) return rc;
-  std::vector<SetResizeWindow> tab;
-  if ((rc = set_resize_window_table(h_w, h_h, tile_w, tile_h, h_win, h_flip, slot_first.data(), out_w, out_h, h_out,
-                                    h_row_pitch, h_plane_pitch, M, dtype, layout, tab)))
-    return rc;
+  std::vector<Win> tab;
+  if ((rc = table(slot_first.data(), tab))) return rc;
   // dense slots are read as dwords
   if (d_tiles && (!nice::tl_aligned(d_tiles, tile_stride, 4) || tile_stride < (uint64_t)tile_w * tile_h * 4))
     return NICE_E_ARG;
   NICE_HIP(hipSetDevice(ctx->device));
-  if ((rc = ctx->tile_tab.grow(M * sizeof(SetResizeWindow)))) return rc;
-  NICE_HIP(hipMemcpyAsync(ctx->tile_tab.ptr, tab.data(), M * sizeof(SetResizeWindow), hipMemcpyHostToDevice,
-                          (hipStream_t)stream));
-  return nice::set_resize_tensor_launch(stream, d_tiles, tile_stride, d_packed, d_src, d_slot_status,
-                                        (const SetResizeWindow*)ctx->tile_tab.ptr, M, tile_w, tile_h, out_w, out_h,
-                                        dtype, layout, scale, bias);
+  if ((rc = ctx->tile_tab.grow(M * sizeof(Win)))) return rc;
+  NICE_HIP(hipMemcpyAsync(ctx->tile_tab.ptr, tab.data(), M * sizeof(Win), hipMemcpyHostToDevice, (hipStream_t)stream));
+  return launch((const Win*)ctx->tile_tab.ptr);
 }
 
-int nice_decode_set_resized_dev(nice_ctx* ctx, void* stream, const uint8_t* d_packed, uint64_t packed_bytes,
-                                const uint64_t* h_off, const uint64_t* h_len, const uint8_t* h_kind,
-                                const uint32_t* h_w, const uint32_t* h_h, uint32_t K, uint32_t tile_w, uint32_t tile_h,
-                                const uint32_t* h_win, const uint8_t* h_flip, uint32_t out_w, uint32_t out_h,
-                                void* const* h_out, const uint64_t* h_row_pitch, const uint64_t* h_plane_pitch,
-                                uint32_t M, uint32_t dtype, uint32_t layout, const float* scale, const float* bias,
-                                uint32_t flags, int32_t* d_status) {
+// The whole call: the checks, the windows, the plan with its position column
+// behind the window descriptors in the head, one upload, one batch decode of
+// the coded slots at 4 bytes per pixel (a tap or a staged pixel is one dword),
+// one status scatter, then launch(d, d_wins, d_src), which makes `launches` launches.
+template <class Win, class Table, class Launch>
+int set_decode_resized(nice_ctx* ctx, void* stream, const uint8_t* d_packed, uint64_t packed_bytes, const uint64_t* h_off,
+                       const uint64_t* h_len, const uint8_t* h_kind, const uint32_t* h_w, const uint32_t* h_h, uint32_t K,
+                       uint32_t tile_w, uint32_t tile_h, const uint32_t* h_win, uint32_t M, uint32_t dtype,
+                       uint32_t layout, const float* scale, const float* bias, uint32_t flags, int32_t* d_status,
+                       uint32_t launches, Table table, Launch launch) {
   if (!ctx || !d_packed || !h_off || !h_len || !h_kind || !d_status) return NICE_E_ARG;
   if ((flags & NICE_DEC_STRICT_REFERENCE) || ((uintptr_t)d_packed & 15)) return NICE_E_ARG;
   int rc = set_tensor_check(dtype, layout, scale, bias);
   if (rc) return rc;
   std::vector<uint32_t> first, nx, slot_first((size_t)M + 1);
   if ((rc = nice::set_select(h_w, h_h, K, tile_w, tile_h, h_win, M, first, nx, slot_first.data()))) return rc;
-  std::vector<SetResizeWindow> wins;
-  if ((rc = set_resize_window_table(h_w, h_h, tile_w, tile_h, h_win, h_flip, slot_first.data(), out_w, out_h, h_out,
-                                    h_row_pitch, h_plane_pitch, M, dtype, layout, wins)))
-    return rc;
+  std::vector<Win> wins;
+  if ((rc = table(slot_first.data(), wins))) return rc;
   NICE_HIP(hipSetDevice(ctx->device));
   // the plan first: its position column travels in the head, behind the window descriptors
   DevSlots d;
@@ -1674,18 +1676,135 @@ int nice_decode_set_resized_dev(nice_ctx* ctx, void* stream, const uint8_t* d_pa
   ctx->last_set_raw = d.plan.by_kind[1];
   std::vector<uint64_t> src;
   nice::slot_position_sources(d.plan, src);
-  const size_t wins_bytes = M * sizeof(SetResizeWindow);
+  const size_t wins_bytes = M * sizeof(Win);
   std::vector<uint8_t> head(wins_bytes + 8 * src.size());
   memcpy(head.data(), wins.data(), wins_bytes);
   if (!src.empty()) memcpy(head.data() + wins_bytes, src.data(), 8 * src.size());
-  // the coded slots at 4 bytes per pixel, whatever the set's channels: a tap is one dword
   if ((rc = decode_planned_slots(ctx, stream, d_packed, packed_bytes, head.data(), head.size(), tile_w, tile_h, 4,
                                  (flags & NICE_DEC_ALPHA_FILL_FF) | NICE_DEC_TOLERANT_HEADER, d_status, d)))
     return rc;
-  ctx->last_set_merges = 1;
-  return nice::set_resize_tensor_launch(stream, d.dec, d.stride, d_packed, (const uint64_t*)(d.head + wins_bytes),
-                                        d_status, (const SetResizeWindow*)d.head, M, tile_w, tile_h, out_w, out_h,
-                                        dtype, layout, scale, bias);
+  ctx->last_set_merges = launches;
+  return launch(d, (const Win*)d.head, (const uint64_t*)(d.head + wins_bytes));
+}
+}  // namespace
+}  // extern "C++"
+
+int nice_set_resize_tensor_dev(nice_ctx* ctx, void* stream, const uint8_t* d_tiles, uint64_t tile_stride,
+                               const uint8_t* d_packed, const uint64_t* d_src, const int32_t* d_slot_status,
+                               const uint32_t* h_w, const uint32_t* h_h, uint32_t K, uint32_t tile_w, uint32_t tile_h,
+                               const uint32_t* h_win, const uint8_t* h_flip, uint32_t out_w, uint32_t out_h,
+                               void* const* h_out, const uint64_t* h_row_pitch, const uint64_t* h_plane_pitch,
+                               uint32_t M, uint32_t dtype, uint32_t layout, const float* scale, const float* bias) {
+  return set_resize_alone<SetResizeWindow>(
+      ctx, stream, d_tiles, tile_stride, d_src, h_w, h_h, K, tile_w, tile_h, h_win, M, dtype, layout, scale, bias,
+      [&](const uint32_t* slot_first, std::vector<SetResizeWindow>& tab) {
+        return set_resize_window_table(h_w, h_h, tile_w, tile_h, h_win, h_flip, slot_first, out_w, out_h, h_out,
+                                       h_row_pitch, h_plane_pitch, M, dtype, layout, tab);
+      },
+      [&](const SetResizeWindow* d_wins) {
+        return nice::set_resize_tensor_launch(stream, d_tiles, tile_stride, d_packed, d_src, d_slot_status, d_wins, M,
+                                              tile_w, tile_h, out_w, out_h, dtype, layout, scale, bias);
+      });
+}
+
+int nice_decode_set_resized_dev(nice_ctx* ctx, void* stream, const uint8_t* d_packed, uint64_t packed_bytes,
+                                const uint64_t* h_off, const uint64_t* h_len, const uint8_t* h_kind,
+                                const uint32_t* h_w, const uint32_t* h_h, uint32_t K, uint32_t tile_w, uint32_t tile_h,
+                                const uint32_t* h_win, const uint8_t* h_flip, uint32_t out_w, uint32_t out_h,
+                                void* const* h_out, const uint64_t* h_row_pitch, const uint64_t* h_plane_pitch,
+                                uint32_t M, uint32_t dtype, uint32_t layout, const float* scale, const float* bias,
+                                uint32_t flags, int32_t* d_status) {
+  return set_decode_resized<SetResizeWindow>(
+      ctx, stream, d_packed, packed_bytes, h_off, h_len, h_kind, h_w, h_h, K, tile_w, tile_h, h_win, M, dtype, layout,
+      scale, bias, flags, d_status, 1,
+      [&](const uint32_t* slot_first, std::vector<SetResizeWindow>& tab) {
+        return set_resize_window_table(h_w, h_h, tile_w, tile_h, h_win, h_flip, slot_first, out_w, out_h, h_out,
+                                       h_row_pitch, h_plane_pitch, M, dtype, layout, tab);
+      },
+      [&](const DevSlots& d, const SetResizeWindow* d_wins, const uint64_t* d_src) {
+        return nice::set_resize_tensor_launch(stream, d.dec, d.stride, d_packed, d_src, d_status, d_wins, M, tile_w,
+                                              tile_h, out_w, out_h, dtype, layout, scale, bias);
+      });
+}
+
+// ---- image sets: antialiased resized tensor output -------------------------------
+namespace {
+// The windows of the antialiased resize (checked as set_resize_window_table
+// checks its own; NICE_E_ARG also for a reducing axis above
+// NICE_RESIZE_AA_MAX_IN), the entries of their weight tables and the longest
+// reducing axis.
+int set_resize_aa_window_table(const uint32_t* h_w, const uint32_t* h_h, uint32_t tile_w, uint32_t tile_h,
+                               const uint32_t* h_win, const uint8_t* h_flip, const uint32_t* slot_first,
+                               uint32_t out_w, uint32_t out_h, void* const* h_out, const uint64_t* h_row_pitch,
+                               const uint64_t* h_plane_pitch, uint32_t M, uint32_t dtype, uint32_t layout,
+                               std::vector<SetResizeAaWindow>& tab, uint64_t& entries, uint32_t& max_reducing) {
+  std::vector<SetResizeWindow> plain;
+  int rc = set_resize_window_table(h_w, h_h, tile_w, tile_h, h_win, h_flip, slot_first, out_w, out_h, h_out, h_row_pitch,
+                                   h_plane_pitch, M, dtype, layout, plain);
+  if (rc) return rc;
+  tab.resize(M);
+  entries = 0;
+  max_reducing = 0;
+  for (uint32_t j = 0; j < M; ++j) {
+    const SetResizeWindow& p = plain[j];
+    if (!nice::resize_aa_axis_ok(p.rw, out_w) || !nice::resize_aa_axis_ok(p.rh, out_h)) return NICE_E_ARG;
+    const uint64_t nc = nice::set_resize_aa_table_entries(p.rw, out_w), nr = nice::set_resize_aa_table_entries(p.rh, out_h);
+    if (entries + nc + nr > 0xFFFFFFFFull) return NICE_E_ARG;
+    tab[j] = SetResizeAaWindow{p.out, p.row_pitch, p.plane_pitch, p.x0, p.y0, p.rw, p.rh, p.tx0, p.ty0, p.ntx,
+                               p.slot_first, (uint32_t)entries, (uint32_t)(entries + nc), p.flip, 0u};
+    entries += nc + nr;
+    if (nc) max_reducing = std::max(max_reducing, p.rw);
+    if (nr) max_reducing = std::max(max_reducing, p.rh);
+  }
+  return NICE_OK;
+}
+}  // namespace
+
+int nice_set_resize_aa_tensor_dev(nice_ctx* ctx, void* stream, const uint8_t* d_tiles, uint64_t tile_stride,
+                                  const uint8_t* d_packed, const uint64_t* d_src, const int32_t* d_slot_status,
+                                  const uint32_t* h_w, const uint32_t* h_h, uint32_t K, uint32_t tile_w,
+                                  uint32_t tile_h, const uint32_t* h_win, const uint8_t* h_flip, uint32_t out_w,
+                                  uint32_t out_h, void* const* h_out, const uint64_t* h_row_pitch,
+                                  const uint64_t* h_plane_pitch, uint32_t M, uint32_t dtype, uint32_t layout,
+                                  const float* scale, const float* bias) {
+  uint64_t entries = 0;
+  uint32_t max_reducing = 0;
+  return set_resize_alone<SetResizeAaWindow>(
+      ctx, stream, d_tiles, tile_stride, d_src, h_w, h_h, K, tile_w, tile_h, h_win, M, dtype, layout, scale, bias,
+      [&](const uint32_t* slot_first, std::vector<SetResizeAaWindow>& tab) {
+        return set_resize_aa_window_table(h_w, h_h, tile_w, tile_h, h_win, h_flip, slot_first, out_w, out_h, h_out,
+                                          h_row_pitch, h_plane_pitch, M, dtype, layout, tab, entries, max_reducing);
+      },
+      [&](const SetResizeAaWindow* d_wins) {
+        if (int rc = ctx->aa_weights.grow(std::max<size_t>(2 * entries, 16))) return rc;
+        return nice::set_resize_aa_tensor_launch(stream, d_tiles, tile_stride, d_packed, d_src, d_slot_status, d_wins, M,
+                                                 (uint16_t*)ctx->aa_weights.ptr, max_reducing, tile_w, tile_h, out_w,
+                                                 out_h, dtype, layout, scale, bias);
+      });
+}
+
+int nice_decode_set_resized_aa_dev(nice_ctx* ctx, void* stream, const uint8_t* d_packed, uint64_t packed_bytes,
+                                   const uint64_t* h_off, const uint64_t* h_len, const uint8_t* h_kind,
+                                   const uint32_t* h_w, const uint32_t* h_h, uint32_t K, uint32_t tile_w,
+                                   uint32_t tile_h, const uint32_t* h_win, const uint8_t* h_flip, uint32_t out_w,
+                                   uint32_t out_h, void* const* h_out, const uint64_t* h_row_pitch,
+                                   const uint64_t* h_plane_pitch, uint32_t M, uint32_t dtype, uint32_t layout,
+                                   const float* scale, const float* bias, uint32_t flags, int32_t* d_status) {
+  uint64_t entries = 0;
+  uint32_t max_reducing = 0;
+  return set_decode_resized<SetResizeAaWindow>(
+      ctx, stream, d_packed, packed_bytes, h_off, h_len, h_kind, h_w, h_h, K, tile_w, tile_h, h_win, M, dtype, layout,
+      scale, bias, flags, d_status, 2,   // the weight tables, the filter
+      [&](const uint32_t* slot_first, std::vector<SetResizeAaWindow>& tab) {
+        return set_resize_aa_window_table(h_w, h_h, tile_w, tile_h, h_win, h_flip, slot_first, out_w, out_h, h_out,
+                                          h_row_pitch, h_plane_pitch, M, dtype, layout, tab, entries, max_reducing);
+      },
+      [&](const DevSlots& d, const SetResizeAaWindow* d_wins, const uint64_t* d_src) {
+        if (int rc = ctx->aa_weights.grow(std::max<size_t>(2 * entries, 16))) return rc;
+        return nice::set_resize_aa_tensor_launch(stream, d.dec, d.stride, d_packed, d_src, d_status, d_wins, M,
+                                                 (uint16_t*)ctx->aa_weights.ptr, max_reducing, tile_w, tile_h, out_w,
+                                                 out_h, dtype, layout, scale, bias);
+      });
 }
 
 // ---- image sets: the alpha batch ---------------------------------------------

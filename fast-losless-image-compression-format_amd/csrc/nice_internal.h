@@ -166,6 +166,30 @@ int set_resize_tensor_launch(void* stream, const uint8_t* d_tiles, uint64_t tile
                              uint32_t n_wins, uint32_t tile_w, uint32_t tile_h, uint32_t out_w, uint32_t out_h,
                              uint32_t dtype, uint32_t layout, const float* scale, const float* bias);
 
+// ---- image sets: antialiased resized tensor output (nice_sets_resize_aa.hip) ----
+// A window of the antialiased resize: SetResizeWindow's output and slots, and
+// where the weight tables of its axes begin, in entries of 16 bits (a reducing
+// axis of n_in pixels has 2 n_in entries, any other none).
+struct SetResizeAaWindow {
+  void* out;
+  uint64_t row_pitch, plane_pitch;
+  uint32_t x0, y0, rw, rh;      // the rectangle, inside its image
+  uint32_t tx0, ty0, ntx;       // its tiles
+  uint32_t slot_first;
+  uint32_t wcol, wrow;          // the tables of its columns and of its rows
+  uint32_t flip, pad;
+};
+uint64_t set_resize_aa_table_entries(uint32_t n_in, uint32_t n_out);
+// set_resize_tensor_launch's slots and skips, by the triangle filter of
+// nice_resize.hpp.  d_weights: room for the tables of all windows;
+// max_reducing: the longest reducing axis among them (0: none reduces).  Two
+// launches: the weight tables, then the filter.
+int set_resize_aa_tensor_launch(void* stream, const uint8_t* d_tiles, uint64_t tile_stride, const uint8_t* d_packed,
+                                const uint64_t* d_src, const int32_t* d_slot_status, const SetResizeAaWindow* d_wins,
+                                uint32_t n_wins, uint16_t* d_weights, uint32_t max_reducing, uint32_t tile_w,
+                                uint32_t tile_h, uint32_t out_w, uint32_t out_h, uint32_t dtype, uint32_t layout,
+                                const float* scale, const float* bias);
+
 // ---- the alpha batch of an image set (nice_sets.hip) --------------------------
 // The set forms of alpha_range_launch, alpha_gather_launch and alpha_merge_launch
 // above: tiles are global tile indices, their images (RGBA) come from d_imgs.

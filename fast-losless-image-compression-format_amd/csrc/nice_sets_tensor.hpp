@@ -1,5 +1,5 @@
 // nice_sets_tensor.hpp -- what the tensor merges share (nice_sets_tensor.hip,
-// nice_sets_resize.hip): the stored form of an element and the combined store
+// nice_sets_resize.hip, nice_sets_resize_aa.hip): the stored form of an element and the combined store
 // of a lane's consecutive elements.
 #pragma once
 #include <hip/hip_runtime.h>

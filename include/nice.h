@@ -645,6 +645,83 @@ int nice_decode_set_resized_dev(nice_ctx* ctx, void* stream, const uint8_t* d_pa
                                 uint32_t M, uint32_t dtype, uint32_t layout, const float* scale, const float* bias,
                                 uint32_t flags, int32_t* d_status /* slot_first[M] */);
 
+/* ---- image sets: antialiased resized tensor output ----
+ * The resized tensor output above with a reducing axis filtered, not sampled:
+ * the triangle filter of support n_in / n_out that torch's
+ * interpolate(bilinear, antialias=True) and PIL's resize apply, in integers, so
+ * results compare bit for bit.  Windows, slots, d_src, dtypes, layouts,
+ * pitches, h_flip, scale, bias, statuses, refusals and flags are the resized
+ * tensor output's; only the value differs.  Each axis is treated separately.
+ *
+ * A non-reducing axis (n_out >= n_in): the taps (i0, i1, f) of the position
+ * above, with the weights 16 * (256 - f) on i0 and 16 * f on i1, in 1/4096
+ * (one tap where f == 0).
+ *
+ * A reducing axis (n_out < n_in; n_in <= NICE_RESIZE_AA_MAX_IN, else
+ * NICE_E_ARG): for output index x (a mirrored window takes out_w - 1 - x on
+ * the column axis) let
+ *   C = (2x + 1) * n_in,  P_i = (2i + 1) * n_out,  S = 2 * n_in     (below 2^30)
+ *   r_i = S - |P_i - C|   for 0 <= i < n_in      the raw weight of pixel i
+ * The taps are the i with r_i > 0: one contiguous run lo..hi, relative to the
+ * window and inside it (the window is never left).  With R the sum of all r_i
+ * of the run and cum_i = r_lo + ... + r_i (64-bit, floor division),
+ *   W_i = (cum * 8192 + R) / (2 * R)      with cum = cum_i;  W_(lo-1) = 0
+ *   w_i = W_i - W_(i-1)
+ * The w_i are not negative, sum to 4096 exactly, and each is within 1/4096 of
+ * r_i / R; renormalising at a window edge is the same rule.  There is no limit
+ * on the reduction ratio.
+ *
+ * The element: with column taps (i, w_i), row taps (j, v_j) and b the byte of
+ * channel c,
+ *   h[j]  = sum over i of w_i * b[j][i]             at most 255 * 2^12
+ *   acc32 = sum over j of v_j * h[j]                at most 255 * 2^24
+ *   acc   = (acc32 + 128) >> 8                      at most 255 * 65536
+ *   v     = fmaf((float)acc * 0x1p-16f, scale[c], bias[c])
+ * stored as the other tensor outputs store v.  A window that reduces on
+ * neither axis has acc32 = 256 * (the acc above) and gives the resized tensor
+ * output's bits; a window of the output's size gives the tensor output's; an
+ * exact halving has the interior weights 512, 1536, 1536, 512 (the triangle of
+ * support 2, not the 2 x 2 block mean).
+ *
+ * An element is written iff every slot its tap rectangle meets (columns
+ * lo..hi by rows lo..hi; i0..i1 on a non-reducing axis) has status NICE_OK and
+ * a readable source; else it is left untouched.  Nothing outside a window's
+ * 3 * out_h * out_w elements is written. */
+#define NICE_RESIZE_AA_MAX_IN 65536u
+/* The kernels alone: nice_set_resize_tensor_dev's parameters.  Two launches
+ * whatever M is and whatever the slots are: the weights of every reducing axis
+ * into a table in the context's scratch (computed on the device, one thread
+ * per source pixel), then the filter.  The filter is separable: a block walks
+ * the source rows of a band of output rows once, stages each row's span in LDS
+ * (the slot of a pixel is looked up once, not once per tap), sums the column
+ * taps per lane and adds the row sums into the band's accumulators; the work
+ * per window is proportional to its pixels, and no tap count is bounded.
+ * A lane owns one output column: planar elements go one per plane and lane
+ * (consecutive lanes, consecutive elements), an interleaved float32 pixel as
+ * one 12-byte store, an interleaved 16-bit pixel as three stores.
+ * Asynchronous after the upload of the M window descriptors. */
+int nice_set_resize_aa_tensor_dev(nice_ctx* ctx, void* stream, const uint8_t* d_tiles, uint64_t tile_stride,
+                                  const uint8_t* d_packed, const uint64_t* d_src /* slot_first[M] */,
+                                  const int32_t* d_slot_status /* slot_first[M], or null */, const uint32_t* h_w,
+                                  const uint32_t* h_h, uint32_t K, uint32_t tile_w, uint32_t tile_h,
+                                  const uint32_t* h_win, const uint8_t* h_flip /* M, or null */, uint32_t out_w,
+                                  uint32_t out_h, void* const* h_out, const uint64_t* h_row_pitch,
+                                  const uint64_t* h_plane_pitch /* planar only */, uint32_t M, uint32_t dtype,
+                                  uint32_t layout, const float* scale /* 3 */, const float* bias /* 3 */);
+/* nice_decode_set_resized_dev with the antialiased value: the same host
+ * tables, slots, per-slot statuses and their order, host-side refusals and
+ * flags.  One upload, one batch decode over the coded slots, one status
+ * scatter, then the two resample launches: the number of launches depends on
+ * neither K nor M. */
+int nice_decode_set_resized_aa_dev(nice_ctx* ctx, void* stream, const uint8_t* d_packed, uint64_t packed_bytes,
+                                   const uint64_t* h_off, const uint64_t* h_len, const uint8_t* h_kind,
+                                   const uint32_t* h_w, const uint32_t* h_h, uint32_t K, uint32_t tile_w,
+                                   uint32_t tile_h, const uint32_t* h_win, const uint8_t* h_flip, uint32_t out_w,
+                                   uint32_t out_h, void* const* h_out, const uint64_t* h_row_pitch,
+                                   const uint64_t* h_plane_pitch, uint32_t M, uint32_t dtype, uint32_t layout,
+                                   const float* scale, const float* bias, uint32_t flags,
+                                   int32_t* d_status /* slot_first[M] */);
+
 /* ---- one image sharded over ranks (config 4) ----
  * The image's raster is cut into bands of whole encoder tiles (1024 pixels in
  * raster order); rank r encodes tiles [tile_lo, tile_hi).  The caller runs the

@@ -170,9 +170,20 @@ inline void decode_set_tensor(const Context& ctx, void* stream, const SetTables&
 // ---- image sets: resized tensor output (nice.h, "image sets: resized tensor output") ----
 // decode_set_tensor with every window resampled to out_h x out_w (fixed-point
 // bilinear, no antialiasing): t.out[j] holds out_h x out_w elements per channel.
+// antialias: a reducing axis takes the integer triangle filter of nice.h,
+// "image sets: antialiased resized tensor output" (nice_decode_set_resized_aa_dev).
 inline void decode_set_resized(const Context& ctx, void* stream, const SetTables& s, const TensorWindows& t,
                                uint32_t out_w, uint32_t out_h, TensorType type, TensorLayout layout,
-                               const TensorAffine& a, int32_t* d_status, uint32_t flags = NICE_DEC_ALPHA_FILL_FF) {
+                               const TensorAffine& a, int32_t* d_status, uint32_t flags = NICE_DEC_ALPHA_FILL_FF,
+                               bool antialias = false) {
+  if (antialias) {
+    check(nice_decode_set_resized_aa_dev(ctx.get(), stream, s.d_packed, s.packed_bytes, s.off, s.len, s.kind, s.w, s.h,
+                                         s.K, s.tile_w, s.tile_h, t.win, t.flip, out_w, out_h, t.out, t.row_pitch,
+                                         t.plane_pitch, t.M, (uint32_t)type, (uint32_t)layout, a.scale, a.bias, flags,
+                                         d_status),
+          "nice_decode_set_resized_aa_dev");
+    return;
+  }
   check(nice_decode_set_resized_dev(ctx.get(), stream, s.d_packed, s.packed_bytes, s.off, s.len, s.kind, s.w, s.h, s.K,
                                     s.tile_w, s.tile_h, t.win, t.flip, out_w, out_h, t.out, t.row_pitch,
                                     t.plane_pitch, t.M, (uint32_t)type, (uint32_t)layout, a.scale, a.bias, flags,

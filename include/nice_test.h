@@ -57,7 +57,8 @@ int nice_test_last_tiled(struct nice_ctx* ctx, uint32_t* coded, uint32_t* raw);
 int nice_test_last_set(struct nice_ctx* ctx, uint32_t* coded, uint32_t* raw);
 /* the merge launches of the context's last nice_decode_set_tensor_dev (one
  * for its coded slots, one for its raw slots, each only if there are any) or
- * nice_decode_set_resized_dev (one) */
+ * nice_decode_set_resized_dev (one), or the resample launches of its last
+ * nice_decode_set_resized_aa_dev (two: the weight tables, the filter) */
 int nice_test_last_set_merges(struct nice_ctx* ctx, uint32_t* launches);
 /* the slots of the context's last nice_decode_set_alpha_dev by kind: decoded as
  * streams, read from raw planes, constant; minus those refused on the host */

@@ -25,6 +25,17 @@ float16, planar and channels_last, with the two bars.  Every figure is a median
 of --runs with min, max and spread (max - min).
 
     python tools/bench_sets_resize.py [--images 256] [--runs 7] [--log profiles/sets_resize_bench.json]
+
+--antialias adds the antialiased leg ("image sets: antialiased resized tensor
+output") to the same run, sides alternated as above: decode_set_resized(
+antialias=True) and nice_set_resize_aa_tensor_dev against the same chain with
+interpolate(antialias=True), whose largest difference from the kernel is
+checked per window against the bound derived from the definition; and, with no
+bar, against the sampled call and kernel, beside the device copy, with the
+peak allocations.  The bar: the antialiased call is faster than its chain end
+to end by more than the sum of the two spreads.
+
+    python tools/bench_sets_resize.py --antialias --log profiles/sets_resize_aa_bench.json
 """
 from __future__ import annotations
 
@@ -62,6 +73,7 @@ def main():
     ap.add_argument("--images", type=int, default=256)
     ap.add_argument("--runs", type=int, default=7)
     ap.add_argument("--log", default=None, help="also write the report to this file")
+    ap.add_argument("--antialias", action="store_true", help="add the antialiased leg")
     args = ap.parse_args()
     import torch
     import torch.nn.functional as F
@@ -91,10 +103,10 @@ def main():
     b_t = torch.tensor(bias, dtype=torch.float32, device=dev)
 
     # ---- the torch chain behind M uint8 windows [rh, rw, 3], into out [M, 3, CW, CW]
-    def chain(u8s, out):
+    def chain(u8s, out, antialias=False):
         for j, u8 in enumerate(u8s):
             x = u8.permute(2, 0, 1)[None].float()
-            x = F.interpolate(x, size=(CW, CW), mode="bilinear", align_corners=False, antialias=False)
+            x = F.interpolate(x, size=(CW, CW), mode="bilinear", align_corners=False, antialias=antialias)
             x = x.mul(s_t[None, :, None, None]).add(b_t[None, :, None, None])
             if flips[j]:
                 x = x.flip(-1)
@@ -129,7 +141,7 @@ def main():
     def st():
         return p(torch.cuda.current_stream().cuda_stream)
 
-    def resize_fn(out, channels_last):
+    def resize_fn(out, channels_last, entry="nice_set_resize_tensor_dev"):
         """out [M, 3, CW, CW], planar or a channels_last view"""
         es = out.element_size()
         base, step = out.data_ptr(), out.stride(0) * es
@@ -138,7 +150,7 @@ def main():
         layout = nice.TENSOR_INTERLEAVED if channels_last else nice.TENSOR_PLANAR
 
         def call():
-            rc = L.nice_set_resize_tensor_dev(
+            rc = getattr(L, entry)(
                 ctx.ptr, st(), p(slots.data_ptr()), stride, None, p(d_src.data_ptr()), None, h_w, h_h, K, tw, th, h_win,
                 h_flip, CW, CW, h_out, h_rp, h_pp, M, nice.TENSOR_F16, layout, c_scale, c_bias)
             assert rc == 0, rc
@@ -176,6 +188,56 @@ def main():
 
     def same_bits(a, b):
         return bool(torch.equal(a.contiguous().view(torch.int16), b.contiguous().view(torch.int16)))
+
+    def axis_bound(n_in):
+        """grey levels one axis adds against the exact filter (tests/test_sets_resize_aa_cpu.py): a reducing
+        axis of at most T taps 255 (T - 1) / 8192, T <= 2 ceil(n_in / CW) (the pixel centres inside an open interval 2 n_in / CW long); any other 255 / 512"""
+        return 255 / 512 if CW >= n_in else 255 * (2 * -(-n_in // CW) - 1) / 8192
+
+    def aa_leg(out, other, cl, resize, ca, cb, moved):
+        kw = dict(windows=crops, size=(CW, CW), scale=scale, bias=bias, flip=flips, ctx=ctx)
+        resize_aa = resize_fn(out, cl, "nice_set_resize_aa_tensor_dev")
+        out.zero_()
+        resize_aa()
+        alone = out.clone()
+        out.zero_()
+        nice.decode_set_resized(iset, out=out, antialias=True, **kw)
+        e2e_ok = same_bits(out, alone)
+        merge_u8()
+        chain(u8s, other, True)
+        diff = (out.float() - other.float()).abs().amax(dim=(2, 3)).cpu().numpy()            # [M, 3]
+        smax = np.abs(np.array(scale))
+        bound = np.array([[(axis_bound(rw) + axis_bound(rh) + 2.0 ** -16) * s + 2 * 2.0 ** -11 * 3.0 for s in smax]
+                          for _, _, _, rw, rh in crops])                                       # |v| < 3 with these constants
+        chain_ok = bool((diff < bound).all())
+        t = {k: [] for k in ("merge_aa", "merge_sampled", "merge_aa_chain", "copy", "e2e_aa", "e2e_sampled",
+                             "e2e_aa_chain")}
+        for _ in range(runs):
+            t["merge_aa"].append(event_ms(torch, resize_aa))
+            t["merge_sampled"].append(event_ms(torch, resize))
+            t["merge_aa_chain"].append(event_ms(torch, lambda: (merge_u8(), chain(u8s, other, True))))
+            t["copy"].append(event_ms(torch, lambda: cb.copy_(ca)))
+            t["e2e_aa"].append(wall_ms(torch, lambda: nice.decode_set_resized(iset, out=out, antialias=True, **kw)))
+            t["e2e_sampled"].append(wall_ms(torch, lambda: nice.decode_set_resized(iset, out=out, **kw)))
+            t["e2e_aa_chain"].append(wall_ms(torch, lambda: chain(nice.decode_set(iset, windows=crops, out=u8s, ctx=ctx),
+                                                                  other, True)))
+        s = {k: summary(v) for k, v in t.items()}
+        bar = (s["e2e_aa_chain"]["median_ms"] - s["e2e_aa"]["median_ms"]
+               > s["e2e_aa_chain"]["spread_ms"] + s["e2e_aa"]["spread_ms"])
+        return dict(
+            s, windows_reducing_on_an_axis=sum(1 for c in crops if c[3] > CW or c[4] > CW),
+            merge_aa_gb_s=round(moved / s["merge_aa"]["median_ms"] / 1e6, 1),
+            copy_gb_s=round(moved / s["copy"]["median_ms"] / 1e6, 1),
+            merge_aa_over_sampled=round(s["merge_aa"]["median_ms"] / s["merge_sampled"]["median_ms"], 2),
+            e2e_aa_over_sampled=round(s["e2e_aa"]["median_ms"] / s["e2e_sampled"]["median_ms"], 3),
+            e2e_ratio=round(s["e2e_aa_chain"]["median_ms"] / s["e2e_aa"]["median_ms"], 3),
+            peak_bytes_aa=peak(lambda: nice.decode_set_resized(iset, channels_last=cl, antialias=True, **kw)),
+            peak_bytes_chain=peak(lambda: chain(nice.decode_set(iset, windows=crops, out_channels=3, ctx=ctx), alloc(cl),
+                                                True)),
+            decode_bits_equal_kernels_alone=e2e_ok, chain_within_bound=chain_ok,
+            largest_difference_to_chain=diff.max(axis=0).tolist(), largest_bound=bound.max(axis=0).tolist(),
+            bar_e2e_aa_faster_than_chain_by_more_than_both_spreads=bool(bar),
+            checks_passed=e2e_ok and chain_ok and bool(bar))               # the bar decides the exit status too
 
     REPS = 20
     for name, cl in (("float16", False), ("float16_channels_last", True)):
@@ -229,6 +291,9 @@ def main():
             # not slower means median <= the other's median + its spread
             bar_merge_resize_wins=wins(s["merge_resize"], s["merge_chain"]),
             bar_e2e_not_slower=s["e2e_resized"]["median_ms"] <= s["e2e_chain"]["median_ms"] + s["e2e_chain"]["spread_ms"])
+        if args.antialias:
+            report[name]["antialias"] = aa_leg(out, other, cl, resize, ca, cb, moved)
+            ok = ok and report[name]["antialias"]["checks_passed"]
         del out, other, alone, ca, cb
 
     report["all_checks_passed"] = ok

@@ -6,6 +6,13 @@
 //   sweep N                            the same for every n_in, n_out in 1 .. N
 //   acc B00 B01 B10 B11 FX FY [...]    a line per six numbers: the accumulator
 //   unit ACC [...]                     a line per number: the bits of acc / 65536 in binary32, hex
+//   aa N_IN N_OUT [N_IN N_OUT ...]   antialiased weights, a line per output index: "n_in n_out x lo: w ..."
+//                                      (the taps lo, lo + 1, ...; the two taps of resize_pos where n_out >= n_in)
+//   aasweep N                          the same for every n_in, n_out in 1 .. N
+//   aax N_IN N_OUT X [X ...]           a line per index: "x lo hi R sum min w_lo w_mid w_hi" (mid = (lo + hi) / 2;
+//                                      sum and min over all the taps' weights)
+//   aaok N_IN N_OUT [...]              a line per pair: 1 where the antialiased entry points take the axis
+//   aaround ACC32 [...]                a line per number: the accumulator in 1/65536
 //   src TW TH BYTES K (W H)*K M (I X Y W H)*M (KIND OFF LEN)*n
 //                                      a line per slot position: "p kind value init"
 #include <stdio.h>
@@ -24,6 +31,22 @@ static void print_pos(uint32_t n_in, uint32_t n_out) {
     printf(" %u,%u,%u", p.i0, p.i1, p.f);
   }
   printf("\n");
+}
+
+static void print_aa(uint32_t n_in, uint32_t n_out) {
+  for (uint32_t x = 0; x < n_out; ++x) {
+    if (n_out >= n_in) {
+      const nice::ResizePos p = nice::resize_pos(x, n_in, n_out);
+      printf("%u %u %u %u: %u", n_in, n_out, x, p.i0, nice::resize_aa_w0(p.f));
+      if (p.i1 != p.i0) printf(" %u", nice::resize_aa_w1(p.f));
+    } else {
+      const nice::ResizeAaRange r = nice::resize_aa_range(x, n_in, n_out);
+      const uint64_t R = nice::resize_aa_cum(r.hi, r.lo, x, n_in, n_out);
+      printf("%u %u %u %u:", n_in, n_out, x, r.lo);
+      for (uint32_t i = r.lo; i <= r.hi; ++i) printf(" %u", nice::resize_aa_weight(i, r.lo, R, x, n_in, n_out));
+    }
+    printf("\n");
+  }
 }
 
 int main(int argc, char** argv) {
@@ -47,6 +70,33 @@ int main(int argc, char** argv) {
       memcpy(&bits, &f, 4);
       printf("%08x\n", bits);
     }
+  } else if (!strcmp(mode, "aa") && v.size() % 2 == 0) {
+    for (size_t i = 0; i < v.size(); i += 2) print_aa((uint32_t)v[i], (uint32_t)v[i + 1]);
+  } else if (!strcmp(mode, "aasweep") && v.size() == 1) {
+    for (uint32_t n_in = 1; n_in <= v[0]; ++n_in)
+      for (uint32_t n_out = 1; n_out <= v[0]; ++n_out) print_aa(n_in, n_out);
+  } else if (!strcmp(mode, "aax") && v.size() >= 2 && v[1] < v[0]) {
+    const uint32_t n_in = (uint32_t)v[0], n_out = (uint32_t)v[1];
+    for (size_t k = 2; k < v.size(); ++k) {
+      const uint32_t x = (uint32_t)v[k];
+      const nice::ResizeAaRange r = nice::resize_aa_range(x, n_in, n_out);
+      const uint64_t R = nice::resize_aa_cum(r.hi, r.lo, x, n_in, n_out);
+      uint64_t sum = 0;
+      uint32_t mn = ~0u;
+      for (uint32_t i = r.lo; i <= r.hi; ++i) {
+        const uint32_t w = nice::resize_aa_weight(i, r.lo, R, x, n_in, n_out);
+        sum += w;
+        mn = w < mn ? w : mn;
+      }
+      printf("%u %u %u %llu %llu %u %u %u %u\n", x, r.lo, r.hi, (unsigned long long)R, (unsigned long long)sum, mn,
+             nice::resize_aa_weight(r.lo, r.lo, R, x, n_in, n_out),
+             nice::resize_aa_weight((r.lo + r.hi) / 2, r.lo, R, x, n_in, n_out),
+             nice::resize_aa_weight(r.hi, r.lo, R, x, n_in, n_out));
+    }
+  } else if (!strcmp(mode, "aaok") && v.size() % 2 == 0) {
+    for (size_t i = 0; i < v.size(); i += 2) printf("%d\n", nice::resize_aa_axis_ok((uint32_t)v[i], (uint32_t)v[i + 1]) ? 1 : 0);
+  } else if (!strcmp(mode, "aaround")) {
+    for (uint64_t a : v) printf("%u\n", nice::resize_aa_round((uint32_t)a));
   } else if (!strcmp(mode, "src") && v.size() >= 5) {
     size_t at = 0;
     const uint32_t tw = (uint32_t)v[at++], th = (uint32_t)v[at++];
