@@ -480,6 +480,7 @@ struct DecLayout {
   size_t total;
   size_t o_tables, o_dstart, o_entry, o_last, o_ck, o_cpx, o_cstart, o_recs, o_changed, o_fchanged, o_rowbuf;
   size_t o_ev, o_evck, o_evn, o_agree, o_items, o_icount;
+  size_t o_hev, o_hevn, o_hevag;
   size_t o_hand, o_abort;
 };
 // Jacobi iterations queued (one change flag each; each returns at once when the
@@ -521,6 +522,11 @@ DecLayout dec_layout(uint32_t n_frames, uint64_t npx, const DecPlan& p) {
   L.o_agree = take(ev_cap ? (size_t)n_frames * max_chunks * 4 : 0);
   L.o_items = take(ev_cap ? (size_t)n_frames * max_chunks * subs * 4 : 0);
   L.o_icount = take(ev_cap ? (size_t)n_frames * 4 : 0);
+  // the re-parses' head events (hev_cap per slice, 0: not kept), laid out as the first pass's
+  const uint32_t hev_cap = ev_cap ? p.hev_cap : 0u;
+  L.o_hev = take((size_t)n_frames * ((max_chunks + 63) & ~63u) * hev_cap * 4);
+  L.o_hevn = take(hev_cap ? (size_t)n_frames * max_chunks * 4 : 0);
+  L.o_hevag = take(hev_cap ? (size_t)n_frames * max_chunks * 4 : 0);
   L.o_hand = take(p.hand);
   L.o_abort = take(p.abort_flags ? (size_t)n_frames * 4 : 0);
   L.total = o;
@@ -558,6 +564,12 @@ void dec_args_scratch(DecArgs& a, const DecLayout& L, uint8_t* base, const DecPl
     a.agree = (uint32_t*)(base + L.o_agree);
     a.head_items = (uint32_t*)(base + L.o_items);
     a.head_count = (uint32_t*)(base + L.o_icount);
+    if (P.hev_cap) {
+      a.hev = (uint32_t*)(base + L.o_hev);
+      a.hev_cap = P.hev_cap;
+      a.hev_n = (uint32_t*)(base + L.o_hevn);
+      a.hev_ag = (uint32_t*)(base + L.o_hevag);
+    }
   }
 }
 
@@ -622,6 +634,8 @@ void dec_print_stats(hipStream_t st, const unsigned long long* dstats, const uin
   fprintf(stderr, "[nice dec stats] slices by first-pass meeting checkpoint: 0:%llu 1:%llu 2-4:%llu 5-16:%llu "
           "17-64:%llu 65+:%llu none:%llu overflow:%llu (ev_cap %u)\n",
           h[50], h[51], h[52], h[53], h[54], h[55], h[56], h[57], a.ev_cap);
+  fprintf(stderr, "[nice dec stats] slice heads: none=%llu placed=%llu emitted=%llu whole_slice_emitted=%llu "
+          "invariant_violations=%llu (hev_cap %u)\n", h[26], h[27], h[28], h[29], h[30], a.hev_cap);
   fprintf(stderr, "[nice dec stats] fix-up rounds per row: 0:%llu 1:%llu 2:%llu 3:%llu 4:%llu 5:%llu 6+:%llu\n",
           h[9], h[10], h[11], h[12], h[13], h[14], h[15]);
   if (h[61]) fprintf(stderr, "[nice dec stats] sync first pass: waves=%llu cycles/wave=%.0f refill cycles/wave=%.0f "
@@ -791,13 +805,19 @@ int nice::decode_batch_impl(nice_ctx* ctx, void* stream, const uint8_t* d_stream
   auto opt = [](int id) { return DecOpt{opt_set(id), opt_val(id)}; };
   const DecOpts opts{opt(NICE_OPT_DEC_SLICE_BITS), opt(NICE_OPT_DEC_SINGLE_WAVE), opt(NICE_OPT_DEC_SEG),
                      opt(NICE_OPT_DEC_SPLIT),      opt(NICE_OPT_DEC_FLOW),        opt(NICE_OPT_DEC_NO_EVENTS),
-                     opt(NICE_OPT_DEC_EV_CAP)};
+                     opt(NICE_OPT_DEC_EV_CAP),     opt(NICE_OPT_DEC_HEV_CAP)};
   DecPlan P = plan_decode(DecShape{n_frames, w, h, ctx->cus, max_len, total_bits}, opts);
   ctx->last_dec_route = P.rows.route;
   ctx->last_dec_fallback = P.fallback.route;
   if (N > 0 && P.rows.route == DEC_R_NONE) return NICE_E_ARG;   // rows too wide for any row kernel
   DecLayout L = dec_layout(n_frames, N, P);
   int rc = ctx->dec.grow(L.total);
+  if (rc && P.hev_cap) {   // the scratch does not fit: without the re-parses' head events
+    (void)hipGetLastError();   // the failed allocation
+    P.hev_cap = 0;
+    L = dec_layout(n_frames, N, P);
+    rc = ctx->dec.grow(L.total);
+  }
   if (rc && P.ev_cap) {   // the scratch does not fit: without the first pass's events
     (void)hipGetLastError();   // the failed allocation
     P.ev_cap = 0;

@@ -23,7 +23,7 @@ struct DecOpt {
   int64_t val;
   bool on() const { return set && val != 0; }
 };
-struct DecOpts { DecOpt slice_bits, single_wave, seg, split, flow, no_events, ev_cap; };
+struct DecOpts { DecOpt slice_bits, single_wave, seg, split, flow, no_events, ev_cap, hev_cap; };
 
 // the row kernels (nice_test_last_dec_route reports these values)
 enum DecRoute : uint32_t { DEC_R_NONE, DEC_R_RECONSTRUCT, DEC_R_ROWS, DEC_R_ROWS8, DEC_R_ROWS_WIDE, DEC_R_FLOW, DEC_R_SPLIT };
@@ -44,6 +44,7 @@ struct RecGeom {
 };
 struct DecPlan {
   uint32_t slice_bits, max_chunks, ck_bits, n_ck, ev_cap, subs;
+  uint32_t hev_cap;     // head events kept per slice by the re-parses (0: none)
   DecLaunch rows;       // the row kernel of every frame; DEC_R_NONE: rows too wide to decode
   DecLaunch fallback;   // DEC_R_NONE, or the redo launch for frames the flow / split kernel gave up on
   uint32_t strips, split_frames;   // split: strips per frame, frames per launch
@@ -108,6 +109,18 @@ inline DecPlan plan_decode(const DecShape& s, const DecOpts& o) {
   if (o.ev_cap.set) {   // tests: force event overflow
     const uint32_t v = (uint32_t)o.ev_cap.val;
     if (p.ev_cap && v >= 4 && v % 4 == 0 && v < p.ev_cap) p.ev_cap = v;
+  }
+  // keep each re-parse's events as well, up to the second checkpoint (where
+  // nearly every re-parse has met the previous parse; a head with more events
+  // is parsed again in dec_emit); only with the first pass's events, and the
+  // caller clears hev_cap first when the scratch does not fit
+  {
+    const uint32_t head_bits = 2 * p.ck_bits < cb ? 2 * p.ck_bits : cb;
+    p.hev_cap = p.ev_cap ? (head_bits / 4 + 3u) & ~3u : 0u;
+  }
+  if (o.hev_cap.set) {   // tests: force head overflow
+    const uint32_t v = (uint32_t)o.hev_cap.val;
+    if (p.hev_cap && v >= 4 && v % 4 == 0 && v < p.hev_cap) p.hev_cap = v;
   }
   const RecGeom g = p.g = rec_geom(w);
   const uint32_t cus = (uint32_t)(s.cus > 1 ? s.cus : 1);

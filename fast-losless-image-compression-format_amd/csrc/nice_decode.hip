@@ -667,6 +667,47 @@ __device__ __forceinline__ uint64_t ev_group(const DecArgs& a, uint32_t f, uint3
   return ((uint64_t)f * ((a.max_chunks + 63u) & ~63u) + (j & ~63u)) * a.ev_cap + (j & 63u) * 4u;
 }
 __device__ __forceinline__ uint32_t ev_word(uint32_t y) { return (y >> 2) * 256u + (y & 3u); }
+// the re-parses' head events: the same layout, hev_cap events per slice
+__device__ __forceinline__ uint64_t hev_group(const DecArgs& a, uint32_t f, uint32_t j) {
+  return ((uint64_t)f * ((a.max_chunks + 63u) & ~63u) + (j & ~63u)) * a.hev_cap + (j & 63u) * 4u;
+}
+
+// Who writes a slice's records once the parse is at its fixpoint (dec_heads,
+// dec_emit and dec_place all decide it here):
+//   SLICE_EMIT       dec_emit parses the whole slice: the final parse never met
+//                    the first pass, or the first pass's events overflowed
+//   SLICE_HEAD_EMIT  dec_emit parses the head up to the meeting checkpoint,
+//                    dec_place writes the first pass's events from there
+//   SLICE_PLACE      dec_place writes both: the head from the events the
+//                    latest re-parse kept (none when the first pass itself
+//                    started at the slice's final entry), then the first pass's
+// A kept head stands only for a consistent slice (parsed last from its present
+// entry) whose latest re-parse met the previous parse at `agree`, the latest
+// meeting point of all passes: a re-parse that met earlier has overwritten the
+// events between its meeting point and `agree`.
+constexpr uint32_t SLICE_EMIT = 0, SLICE_HEAD_EMIT = 1, SLICE_PLACE = 2;
+// hn: the head events dec_place walks (SLICE_PLACE), else 0.  (Every load is
+// issued before the first is used: dec_place's short waves wait on them.)
+__device__ __forceinline__ uint32_t slice_route(const DecArgs& a, uint64_t base, uint32_t j, uint32_t& ag,
+                                                uint32_t& nvalid, uint32_t& hn) {
+  const unsigned long long last = a.last[base + j];
+  ag = a.agree[base + j];
+  const uint32_t nev = a.ev_n[base + j];
+  unsigned long long e = 0;
+  uint32_t hev_n = EV_OVERFLOW, hev_ag = AGREE_NONE;
+  if (a.hev) {
+    e = j == 0 ? 0ull : a.entry[base + j];
+    hev_n = a.hev_n[base + j];
+    hev_ag = a.hev_ag[base + j];
+  }
+  nvalid = (uint32_t)(last >> 56);
+  hn = 0;
+  if (ag == AGREE_NONE || nev == EV_OVERFLOW || ag > nvalid) return SLICE_EMIT;
+  if (ag == 0u) return SLICE_PLACE;
+  if ((last & PS_MASK) != e || hev_n == EV_OVERFLOW || hev_ag != ag) return SLICE_HEAD_EMIT;
+  hn = hev_n;
+  return SLICE_PLACE;
+}
 
 // Event word of a coded pixel: its prefix and payload symbols as read
 // (SMALL_DIFF index < 343, bytes < 256; LUMA: reference < 11, so its fourth
@@ -727,8 +768,13 @@ __global__ __launch_bounds__(DEC_PARSE_THREADS) PARSE_ATTR void dec_sync(DecArgs
   unsigned long long* ck = a.ck + (uint64_t)f * a.n_ck * a.max_chunks + j;
   // first pass: keep the pixel events (16-byte stores of 4)
   const bool keep = a.ev != nullptr && !check;
-  uint32_t* evp = a.ev + ev_group(a, f, j);
+  // (one pointer: a lane keeps the first pass's events or a re-parse's head, never both)
+  uint32_t* evp = check ? a.hev + hev_group(a, f, j) : a.ev + ev_group(a, f, j);
   uint32_t* evck = a.ev_ck + (uint64_t)f * a.n_ck * a.max_chunks + j;
+  // re-parses: keep the head's events, from the entry to the checkpoint where
+  // the parse meets the previous one (ne counts them, as the first pass's)
+  const bool hkeep = a.hev != nullptr && check && need;
+  bool hkept = false;   // (wave-uniform) the loop this wave took kept them
   uint32_t ne = 0, ev0 = 0, ev1 = 0, ev2 = 0;
   Lane L;
   L.pos = D + (e & ((1ull << 40) - 1));
@@ -785,10 +831,10 @@ __global__ __launch_bounds__(DEC_PARSE_THREADS) PARSE_ATTR void dec_sync(DecArgs
                                   : pixel_event(L, my, S, SP, s0, s1, s2, s3);
         const uint32_t c = pixel_count(pfx, dk);
         px = sat_add(px, c);
-        if (keep) {
+        if (keep || hkeep) {
           const uint32_t ev = pfx < (uint32_t)P_RUN1 ? ev_pack(pfx, s0, s1, s2, s3) : EV_RUN | min(c, EV_RUN - 1u);
           // the last three events in a shift register (ev2 the newest)
-          if (ne < a.ev_cap && (ne & 3u) == 3u)
+          if (ne < (keep ? a.ev_cap : a.hev_cap) && (ne & 3u) == 3u)
             *reinterpret_cast<uint4*>(evp + ev_word(ne - 3u)) = make_uint4(ev0, ev1, ev2, ev);
           ev0 = ev1;
           ev1 = ev2;
@@ -824,9 +870,12 @@ __global__ __launch_bounds__(DEC_PARSE_THREADS) PARSE_ATTR void dec_sync(DecArgs
     uint32_t rfill = 0;  // refill once r reaches this (ring empty: at once)
     uint32_t nck = b31 + a.ck_bits;   // next checkpoint (relative)
     uint32_t q0 = 0, q1 = 0, q2 = 0, q3 = 0;   // the current quad of kept events
+    // keep_tag: 0 keeps nothing, 1 the first pass (events into ev), 2 a re-parse
+    // (head events into hev)
     auto step = [&](auto slot_tag, auto keep_tag) -> bool {
       constexpr int SLOT = decltype(slot_tag)::value;
-      constexpr bool KEEP = decltype(keep_tag)::value;
+      constexpr bool KEEP = decltype(keep_tag)::value == 1;
+      constexpr bool HEAD = decltype(keep_tag)::value == 2;
       if (active && (r >= rlim || px > N)) active = false;
       if (active && r >= nck) {
         const uint32_t cur = (r - b31) | (dk << 20);
@@ -841,9 +890,9 @@ __global__ __launch_bounds__(DEC_PARSE_THREADS) PARSE_ATTR void dec_sync(DecArgs
           ck_old = (check && k < nvalid_old) ? ck[(uint64_t)k * a.max_chunks] : ~0ull;
         }
       }
-      // (the first pass tests for the wave's end once per quad: a step after
-      // every lane stopped only evaluates masked conditions)
-      if ((!KEEP || SLOT == 0) && !__any(active)) return false;
+      // (the passes that keep events test for the wave's end once per quad: a
+      // step after every lane stopped only evaluates masked conditions)
+      if ((!(KEEP || HEAD) || SLOT == 0) && !__any(active)) return false;
       if (__any(active && r >= rfill)) {   // the next event's 3 words would pass the ring's end
         const uint32_t wsa = (bwl + (r >> 5)) & ~3u;
         ring_fill_ws(wring, p, len, al16, wsa);
@@ -880,18 +929,40 @@ __global__ __launch_bounds__(DEC_PARSE_THREADS) PARSE_ATTR void dec_sync(DecArgs
           }
           ++ne;
         }
+        if (HEAD && hkeep) {   // (every re-parsing lane of the wave starts at event 0 in the same step)
+          const uint32_t ev = pfx < (uint32_t)P_RUN1 ? ev_pack(pfx, s0, s1, s2, s3) : EV_RUN | min(c, EV_RUN - 1u);
+          if constexpr (SLOT == 0) q0 = ev;
+          if constexpr (SLOT == 1) q1 = ev;
+          if constexpr (SLOT == 2) q2 = ev;
+          if constexpr (SLOT == 3) {
+            q3 = ev;
+            if (ne < a.hev_cap) *reinterpret_cast<uint4*>(evp + ev_word(ne - 3u)) = make_uint4(q0, q1, q2, q3);
+          }
+          ++ne;
+        }
       }
       return true;
     };
+    using keep_none = std::integral_constant<int, 0>;
+    using keep_first = std::integral_constant<int, 1>;
+    using keep_head = std::integral_constant<int, 2>;
     if (__any(keep && active)) {   // the first pass: unrolled by the quad
       for (;;) {
-        if (!step(std::integral_constant<int, 0>{}, std::true_type{})) break;
-        if (!step(std::integral_constant<int, 1>{}, std::true_type{})) break;
-        if (!step(std::integral_constant<int, 2>{}, std::true_type{})) break;
-        if (!step(std::integral_constant<int, 3>{}, std::true_type{})) break;
+        if (!step(std::integral_constant<int, 0>{}, keep_first{})) break;
+        if (!step(std::integral_constant<int, 1>{}, keep_first{})) break;
+        if (!step(std::integral_constant<int, 2>{}, keep_first{})) break;
+        if (!step(std::integral_constant<int, 3>{}, keep_first{})) break;
       }
-    } else {   // later passes keep nothing (a smaller loop: these launches are short)
-      while (step(std::integral_constant<int, 0>{}, std::false_type{})) {
+    } else if (__any(hkeep && active)) {   // a re-parse keeping its head: the same way
+      hkept = true;
+      for (;;) {
+        if (!step(std::integral_constant<int, 0>{}, keep_head{})) break;
+        if (!step(std::integral_constant<int, 1>{}, keep_head{})) break;
+        if (!step(std::integral_constant<int, 2>{}, keep_head{})) break;
+        if (!step(std::integral_constant<int, 3>{}, keep_head{})) break;
+      }
+    } else {   // a re-parse that keeps nothing (a smaller loop: these launches are short)
+      while (step(std::integral_constant<int, 0>{}, keep_none{})) {
       }
     }
     L.pos = B + r;
@@ -902,6 +973,7 @@ __global__ __launch_bounds__(DEC_PARSE_THREADS) PARSE_ATTR void dec_sync(DecArgs
     ev2 = sl == 3u ? q2 : sl == 2u ? q1 : q0;
   } else {
     parse(std::false_type{});   // (any tables; the general parse)
+    hkept = true;
   }
   if (tstat) {
     const unsigned long long tw = __builtin_amdgcn_s_memtime() - tw0;
@@ -912,21 +984,29 @@ __global__ __launch_bounds__(DEC_PARSE_THREADS) PARSE_ATTR void dec_sync(DecArgs
     atomicAdd(&a.stats[60], nact);
   }
   if (!need) return;
+  // the last (ne & 3) kept events are the newest of ev0..ev2
+  auto store_tail = [&](uint32_t* t) {
+    const uint32_t slot = ne & 3u;
+    if (slot == 3u) { t[0] = ev0; t[1] = ev1; t[2] = ev2; }
+    if (slot == 2u) { t[0] = ev1; t[1] = ev2; }
+    if (slot == 1u) t[0] = ev2;
+  };
   if (keep) {
-    const uint32_t slot = ne & 3u, q0 = ne & ~3u;
-    if (ne <= a.ev_cap) {
-      uint32_t* t = evp + ev_word(q0);
-      // the last `slot` events are the newest of ev0..ev2
-      if (slot == 3u) { t[0] = ev0; t[1] = ev1; t[2] = ev2; }
-      if (slot == 2u) { t[0] = ev1; t[1] = ev2; }
-      if (slot == 1u) t[0] = ev2;
-    }
+    if (ne <= a.ev_cap) store_tail(evp + ev_word(ne & ~3u));
     a.ev_n[base + j] = ne <= a.ev_cap ? ne : EV_OVERFLOW;
     a.agree[base + j] = 0;
   } else if (a.ev) {
     // the final parse equals the first pass from the latest meeting point on
     const uint32_t ag = synced ? k + 1u : AGREE_NONE;
     a.agree[base + j] = max(a.agree[base + j], ag);
+    if (a.hev) {
+      // the head stands when this parse met the previous one within hev_cap
+      // events; a later re-parse of the slice overwrites it
+      const bool ok = synced && hkept && ne <= a.hev_cap;
+      if (ok) store_tail(evp + ev_word(ne & ~3u));
+      a.hev_n[base + j] = ok ? ne : EV_OVERFLOW;
+      a.hev_ag[base + j] = ag;
+    }
   }
   if (a.stats && check) {   // diagnostics: where re-parses met the previous parse (16: never)
     atomicAdd(&a.stats[32 + (synced ? min(k, 15u) : 16u)], 1ull);
@@ -1396,11 +1476,13 @@ __global__ __launch_bounds__(DEC_PARSE_THREADS) PARSE_ATTR void dec_emit(DecArgs
     if (q64 > N) active = false;      // past the image: tail bytes
     if (a.ev) {
       // dec_place writes the slice from where the final parse meets the first
-      // pass (its events kept): this lane only parses the head before that
-      const uint32_t ag = a.agree[base + j];
-      if (ag != AGREE_NONE && a.ev_n[base + j] != EV_OVERFLOW && ag <= nvalid) {
-        const unsigned long long stop =
-            ag == 0u ? begin : begin + (ck[(uint64_t)(ag - 1u) * a.max_chunks] & 0xFFFFu);
+      // pass (its events kept): this lane only parses the head before that,
+      // and not even the head when the re-parse kept its events
+      uint32_t ag, nv2, hn;
+      const uint32_t route = slice_route(a, base, j, ag, nv2, hn);
+      if (route == SLICE_PLACE) active = false;
+      if (route == SLICE_HEAD_EMIT) {
+        const unsigned long long stop = begin + (ck[(uint64_t)(ag - 1u) * a.max_chunks] & 0xFFFFu);
         if (stop < end) end = stop;
         if (sub * step >= ag) active = false;   // starts at or past the meeting point
       }
@@ -1524,9 +1606,10 @@ __global__ __launch_bounds__(1024) void dec_heads(DecArgs a) {
   const uint32_t per = (nc + 1023) / 1024;
   const uint32_t c0 = min(threadIdx.x * per, nc), c1 = min(c0 + per, nc);
   auto nsub = [&](uint32_t j) -> uint32_t {
-    const uint32_t ag = a.agree[base + j], nvalid = (uint32_t)(a.last[base + j] >> 56);
-    if (ag == AGREE_NONE || a.ev_n[base + j] == EV_OVERFLOW || ag > nvalid)
-      return min(subs, 1u + nvalid / step);   // every sub-slice with a start (s * step - 1 < nvalid)
+    uint32_t ag, nvalid, hn;
+    const uint32_t route = slice_route(a, base, j, ag, nvalid, hn);
+    if (route == SLICE_EMIT) return min(subs, 1u + nvalid / step);   // every sub-slice with a start (s * step - 1 < nvalid)
+    if (route == SLICE_PLACE) return 0u;      // dec_place has the head's events
     return (ag + step - 1) / step;            // sub-slices starting before the meeting point
   };
   uint32_t cnt = 0;
@@ -1549,8 +1632,9 @@ __global__ __launch_bounds__(1024) void dec_heads(DecArgs a) {
 }
 
 // ---------------------------------------------------------------------------
-// D4b: place the first pass's events past each slice's meeting point (one wave
-// per slice): pixel positions by a wave prefix sum of the events' pixel
+// D4b: place each slice's kept events (one wave per slice): the head's, kept
+// by the slice's latest re-parse, from the slice's first pixel, then the first
+// pass's past the meeting point; pixel positions by a wave prefix sum of the events' pixel
 // counts, one coalesced 4-byte record store per coded pixel, runs left to the
 // memset marker.  Same checks as dec_emit: the first event at q == N is the
 // extra prefix the reference reads (strict: a run digit there is an error),
@@ -1632,31 +1716,63 @@ __global__ __launch_bounds__(64 * DEC_PLACE_WAVES) void dec_place(DecArgs a) {
   const uint32_t nbx = gridDim.x, nwg = nbx * gridDim.y, lin = blockIdx.y * nbx + blockIdx.x;
   const uint32_t xq = nwg / 8u, xr = nwg % 8u, xcd = lin % 8u;
   const uint32_t lg = (xcd < xr ? xcd * (xq + 1u) : xr * (xq + 1u) + (xcd - xr) * xq) + lin / 8u;
-  const uint32_t f = lg / nbx, j = (lg % nbx) * DEC_PLACE_WAVES + (threadIdx.x >> 6);
+  // (the wave's slice in a scalar register: its bookkeeping and the event
+  // buffers' bases then take no vector registers)
+  const uint32_t f = lg / nbx, j = (lg % nbx) * DEC_PLACE_WAVES + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   if (a.status[f] != 0) return;
   const uint64_t len = a.stream_len[f];
   const uint64_t D = a.data_start[f];
   if (j >= n_chunks(len, D, a.chunk_bits)) return;
   const uint64_t base = (uint64_t)f * a.max_chunks;
-  const uint32_t ag = a.agree[base + j], nev = a.ev_n[base + j];
-  const uint32_t nvalid = (uint32_t)(a.last[base + j] >> 56);
+  uint32_t ag, nvalid, hn;
+  const uint32_t route = slice_route(a, base, j, ag, nvalid, hn);
+  const uint32_t nev = a.ev_n[base + j];
   if (a.stats && lane == 0) {   // diagnostics: where the final parse met the first pass
     const uint32_t b = nev == EV_OVERFLOW ? 7u : ag == AGREE_NONE ? 6u : ag == 0u ? 0u : ag == 1u ? 1u
                      : ag <= 4u ? 2u : ag <= 16u ? 3u : ag <= 64u ? 4u : 5u;
     atomicAdd(&a.stats[50 + b], 1ull);
+    // the slice's head: none (the first pass started at the final entry),
+    // placed here, parsed by dec_emit, or the whole slice parsed by dec_emit
+    atomicAdd(&a.stats[route == SLICE_EMIT ? 29 : route == SLICE_HEAD_EMIT ? 28 : ag == 0u ? 26 : 27], 1ull);
   }
-  if (ag == AGREE_NONE || nev == EV_OVERFLOW || ag > nvalid) return;   // dec_emit parsed it all
+  if (route == SLICE_EMIT) return;   // dec_emit parsed it all
+  // the head's events kept by the latest re-parse (hn of them), then the first
+  // pass's from the meeting checkpoint.  (One index space over both buffers,
+  // each lane picking buffer and index, cost dec_place 28 % for 10 % more
+  // events: 15 more VGPRs and a 64-bit select per load.  The two are walked
+  // one after the other instead, every step reading one buffer.)
+  const bool head = route == SLICE_PLACE && ag != 0u;
   // (the bookkeeping loads issued together, the first checkpoint taken as
   // the meeting point before `agree` is in: no faster, r06zv_ab_pack_place.log)
   const uint64_t cki = (uint64_t)f * a.n_ck * a.max_chunks + j + (uint64_t)(ag ? ag - 1u : 0u) * a.max_chunks;
-  const uint32_t i_first = ag == 0u ? 0u : a.ev_ck[cki];
-  unsigned long long q = a.chunk_start[base + j] + (ag == 0u ? 0ull : (a.ck[cki] >> 32));
+  // (wave-uniform values the tail needs after the head's loop, kept in scalar registers)
+  auto uni = [](uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); };
+  const uint32_t i_first1 = uni(ag == 0u ? 0u : a.ev_ck[cki]), nev1 = uni(nev);
+  hn = uni(hn);
+  const unsigned long long q_first = a.chunk_start[base + j];
+  // pixels before the meeting point: where the head's events must end
+  const unsigned long long q_meet_v = q_first + (ag == 0u ? 0ull : (a.ck[cki] >> 32));
+  const unsigned long long q_meet = ((unsigned long long)uni((uint32_t)(q_meet_v >> 32)) << 32) | uni((uint32_t)q_meet_v);
+  unsigned long long q = head ? q_first : q_meet;
   const uint64_t N = (uint64_t)a.W * a.H;
   if (q > N) return;                    // tail bytes
-  const uint32_t* evp = a.ev + ev_group(a, f, j);
   uint32_t* rec = a.recs + (uint64_t)f * a.rec_stride;
   const bool strict = (a.flags & NICE_DEC_STRICT_REFERENCE) != 0;
-  bool err = false;
+  bool err = false, stopped = false;
+  for (uint32_t part = head ? 0u : 1u; part < 2u && !stopped; ++part) {
+  // events [i_first, nev) of this part's buffer
+  const uint32_t* evp = part == 0u ? a.hev + hev_group(a, f, j) : a.ev + ev_group(a, f, j);
+  const uint32_t i_first = part == 0u ? 0u : i_first1, nev = part == 0u ? hn : nev1;
+  if (part == 1u && head && q != q_meet) {
+    // the head must end where the first pass's events take over, or the two
+    // parses are not the ones the checkpoints describe: the frame fails
+    // (NICE_E_HIP, as a parse that is not at its fixpoint), never decodes
+    if (lane == 0) {
+      if (a.stats) atomicAdd(&a.stats[30], 1ull);
+      set_status(&a.status[f], NICE_E_HIP);
+    }
+    return;
+  }
   // 256 events per step: 4 rows of 64 consecutive events (coalesced loads and
   // record stores), prefix sums per row plus the rows before
   // the next step's events, loaded one step ahead and unconditionally (lanes
@@ -1664,7 +1780,7 @@ __global__ __launch_bounds__(64 * DEC_PLACE_WAVES) void dec_place(DecArgs a) {
   // used): with every load issued, the compiler's wait at the top of a step
   // leaves the next step's four in flight (a conditional load with a zero
   // fill made it wait for all of them)
-  if (i_first >= nev) return;
+  if (i_first >= nev) continue;
   const uint32_t ev_last = nev - 1u;
   uint32_t nx[4];
 #pragma unroll
@@ -1763,9 +1879,11 @@ __global__ __launch_bounds__(64 * DEC_PLACE_WAVES) void dec_place(DecArgs a) {
     }
     if (stop_k < 4u) {
       if (lane == 0) err = stop_at_n ? (strict && stop_run) : true;
+      stopped = true;
       break;
     }
     q += carry;
+  }
   }
   if (err) set_status(&a.status[f], NICE_E_FORMAT);
 }

@@ -184,6 +184,13 @@ struct DecArgs {
   uint32_t* agree;                    // n_frames * max_chunks: final parse == first pass from checkpoint agree-1 (0: entry)
   uint32_t* head_items;               // n_frames * max_chunks * (chunk_bits / DEC_EMIT_BITS): dec_emit's sub-slices
   uint32_t* head_count;               // n_frames: sub-slices listed
+  // pixel events of each slice's latest re-parse, from its entry to the
+  // checkpoint where it met the previous parse (the slice's head); null: not
+  // kept (dec_emit parses the heads)
+  uint32_t* hev;                      // n_frames * max_chunks * hev_cap events, laid out as ev
+  uint32_t hev_cap;                   // head events per slice (multiple of 4)
+  uint32_t* hev_n;                    // n_frames * max_chunks: head events kept, EV_OVERFLOW
+  uint32_t* hev_ag;                   // n_frames * max_chunks: `agree` of the parse that wrote them
   // dec_rows_split (wide frames, several workgroups per frame): strips per
   // frame, the units' published first / last pixels (n_frames * H * strips *
   // 8 granules, zeroed per call) and a per-frame abort flag

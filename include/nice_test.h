@@ -31,6 +31,7 @@ enum nice_test_opt {
   NICE_OPT_ENC_NO_PAIR = 12,    /* != 0: no two-tile classify iterations */
   NICE_OPT_ENC_NO_SLIDE = 13,   /* != 0: no per-lane sliding-window classify */
   NICE_OPT_TEST_FLOW_ABSENT = 14, /* != 0: dec_rows_flow's last wave never starts (fallback test) */
+  NICE_OPT_DEC_HEV_CAP = 15,    /* head events kept per slice by the re-parses (forces overflow) */
   NICE_OPT_COUNT = 16
 };
 
