@@ -2,8 +2,10 @@
 // per-channel cyclic intervals, the per-pixel word kinds and the one-pixel
 // steps.  No HIP header: a plain C++ compiler reads it too, so the CPU check of
 // this arithmetic (tools/rows_arith_check.cpp, tests/test_rows_arith.py) runs
-// the functions the kernels run.  What needs DPP, v_perm or inline asm
-// (unspread3_perm, the pre-passes) stays in nice_rows.hip.
+// the functions the kernels run.  The barrier kernels' body and its stages
+// (unspread3_perm, the pre-passes) are nice_rows_body.hpp, which a host
+// compiler reads through a shim of the HIP names; what needs DPP or wave votes
+// stays in nice_rows.hip.
 #pragma once
 #include <stdint.h>
 

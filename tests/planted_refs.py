@@ -306,6 +306,8 @@ DEC_SHAPES = {
     (515, 64, 3): wave_edges(515, 8),
     (1026, 64, 3): wave_edges(1026) + strip_edges(1026, 2) + strip_edges(1026, 3),
     (1026, 64, 4): wave_edges(1026) + strip_edges(1026, 2) + strip_edges(1026, 3),
+    # dec_rows_wide and the default three strips of dec_rows_split: nine waves, ten edges
+    (8194, 40, 3): wave_edges(8194) + strip_edges(8194, 3),
 }
 
 
@@ -327,6 +329,7 @@ SEEDS = {
     (10300, 24, 4): (2, 104, 205), (10300, 24, 3): (6, 101, 201),
     (37, 64, 3): (1, 101, 201), (61, 64, 3): (3, 101, 201), (67, 64, 3): (1, 101, 201),
     (515, 64, 3): (1, 101, 201), (1026, 64, 3): (1, 101, 201), (1026, 64, 4): (1, 101, 201),
+    (8194, 40, 3): (2, 103, 201),
 }
 
 

@@ -23,6 +23,10 @@ def test_header_declares_boundary():
 
 def test_library_exports_every_declared_symbol():
     pkg = nice_pkg()
+    # torch first, as lib() does: loaded before it, the library binds to the system's HIP
+    # runtime instead of the one torch brings, and a later GPU test in this process finds
+    # no device (two runtimes in one process)
+    pkg.lib()
     L = ctypes.CDLL(pkg.LIB_PATH)
     for n in _declared():
         assert hasattr(L, n), n

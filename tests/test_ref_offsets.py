@@ -58,6 +58,9 @@ DEC_CASES = {
     "split2-1026": ("dec_rows_split", {"NICE_DEC_SPLIT": 2}, (3, 4), (1026, 64, 3)),
     "split3-1026": ("dec_rows_split", {"NICE_DEC_SPLIT": 3}, (3, 4), (1026, 64, 3)),
     "split2-67": ("dec_rows_split", {"NICE_DEC_SPLIT": 2}, (3,), (67, 64, 3)),   # strips of 3 and 2 segments
+    # the ring in global memory (64-bit addresses), nine waves of which the last holds one segment
+    "wide-8194": ("dec_rows_wide", {"NICE_DEC_SPLIT": 0}, (3,), (8194, 40, 3)),
+    "split-8194": ("dec_rows_split", {}, (3,), (8194, 40, 3)),   # the default: three strips
 }
 
 
@@ -139,6 +142,10 @@ def test_decode_planted(nice, opts, case):
     # the properties the shapes were chosen for
     if W in (67, 1026) and kernel == "dec_rows":
         assert W % 16 == (3 if W == 67 else 2) and want["threads"] == (64 if W == 67 else 128)
+    if case == "wide-8194":
+        assert want["threads"] == 576 and W % 16 == 2
+    if case == "split-8194":
+        assert want["strips"] == 3 and P.strip_edges(W, 3) == [2736, 5472] and want["fallback"] == "dec_rows_wide"
     if case == "split2-67":
         assert (want["strips"], P.strip_edges(W, 2)) == (2, [48]) and (W + 15) // 16 == 5
     ctx = nice.Context(0)

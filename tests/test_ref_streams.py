@@ -33,7 +33,7 @@ from test_ref_offsets import DEC_CASES
 H = 16
 WIDTHS = sorted({shape[0] for _, _, _, shape in DEC_CASES.values()})
 # streams per width (seeds at which the pooled classes below hold every reference)
-SEEDS = {37: (1, 2, 3), 61: (1, 2, 3), 67: (1, 2, 3), 515: (1, 2, 7), 1026: (1, 2, 3)}
+SEEDS = {37: (1, 2, 3), 61: (1, 2, 3), 67: (1, 2, 3), 515: (1, 2, 7), 1026: (1, 2, 3), 8194: (1, 2, 6)}
 KINDS = [(0, 0)] + [(2, k) for k in range(11)]
 
 
@@ -87,6 +87,8 @@ def test_crafted_streams_decode(nice, opts, case):
     cus = torch.cuda.get_device_properties(0).multi_processor_count
     want = plan_driver.plan(W, H, 1, cus, **{k[len("NICE_DEC_"):].lower(): v for k, v in options.items()})
     assert want["route"] == kernel
+    if W == 8194:
+        assert (want["threads"] == 576) if kernel == "dec_rows_wide" else (want["strips"] == 3)
     ctx = nice.Context(0)
     for i, (s, _, ref) in enumerate(_streams(W)):
         sb = torch.zeros((1, (len(s) + 255) // 256 * 256), dtype=torch.uint8)
