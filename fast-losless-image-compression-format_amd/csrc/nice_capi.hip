@@ -608,6 +608,15 @@ void dec_print_stats(hipStream_t st, const unsigned long long* dstats, const uin
   (void)hipMemcpyAsync(h, dstats, 1024, hipMemcpyDeviceToHost, st);
   uint32_t chg[kSyncFlags] = {0};
   (void)hipMemcpyAsync(chg, changed, 4 * kSyncFlags, hipMemcpyDeviceToHost, st);
+  // which parse each frame's tables allow (DecTables::fast, one byte a frame)
+  // and frame 0's table plan: max_aob and lut_bits lie next to each other
+  const uint8_t* tb = (const uint8_t*)a.tables;
+  std::vector<uint8_t> tfast(a.n_frames, 0);
+  uint8_t plan0[2 * N_STREAMS] = {0};
+  static_assert(offsetof(DecTables, lut_bits) == offsetof(DecTables, max_aob) + N_STREAMS, "one copy for both");
+  (void)hipMemcpy2DAsync(tfast.data(), 1, tb + offsetof(DecTables, fast), sizeof(DecTables), 1, a.n_frames,
+                         hipMemcpyDeviceToHost, st);
+  (void)hipMemcpyAsync(plan0, tb + offsetof(DecTables, max_aob), sizeof(plan0), hipMemcpyDeviceToHost, st);
   (void)hipStreamSynchronize(st);
   fprintf(stderr,
           "[nice dec stats] rows=%llu unconverged_segs=%llu tail_unknown_segs=%llu "
@@ -617,6 +626,14 @@ void dec_print_stats(hipStream_t st, const unsigned long long* dstats, const uin
   fprintf(stderr, "[nice dec stats] sync iterations that changed an entry:");
   for (uint32_t i = 0; i < kSyncFlags; ++i) fprintf(stderr, " %u", chg[i]);
   fprintf(stderr, " (queued %u, then settled, final)\n", queued);
+  uint32_t n_fast = 0;
+  for (uint8_t v : tfast) n_fast += v ? 1u : 0u;
+  fprintf(stderr, "[nice dec stats] parse: frames=%u fast=%u slow_parse=%u frame0 max=", a.n_frames, n_fast,
+          a.parse_slow);
+  for (int s = 0; s < N_STREAMS; ++s) fprintf(stderr, "%s%u", s ? "," : "", (unsigned)plan0[s]);
+  fprintf(stderr, " lut_bits=");
+  for (int s = 0; s < N_STREAMS; ++s) fprintf(stderr, "%s%u", s ? "," : "", (unsigned)plan0[N_STREAMS + s]);
+  fprintf(stderr, "\n");
   for (int w = 0; w < 4; ++w) {   // dec_rows_flow (-DNICE_FLOW_STATS builds): cycles per row by phase
     const unsigned long long* q = h + 64 + 8 * w;
     if (q[7])

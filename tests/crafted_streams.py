@@ -13,6 +13,10 @@ so whether the reference decoder finishes depends only on its bit reader:
 `read_24bits_noclear` with a table of 26-31 bits wraps its u8 offset at some
 alignments (bitreader.rs:85-98).  The oracle decides which streams do.
 """
+import functools
+import os
+import re
+
 import numpy as np
 
 # stream sizes (code.rs:91-116) and the payload streams of each prefix
@@ -20,6 +24,54 @@ SIZES = [256, 13, 64, 32, 11, 343, 64, 32, 32, 11]
 BR_OFF = lambda W: [1, W, W - 1, 2, 2 * W]
 LUMA_OFF = lambda W: [1, W, W - 1, W - 3, 3, 3 * W - 1, 3 * W, 3 * W + 1, W + 3, 3 * W + 3, 3 * W - 3]
 DEEP_STREAMS = [0, 2, 3, 5, 6, 7, 8]   # alphabets that can hold a 25-31 bit table
+# payload streams of the coded modes, by prefix id (code.rs:576-644)
+PAY_STREAMS = [[9], [0, 0, 0], [4, 2, 3, 3], [5], [6, 7, 8]]
+DATA_START_BITS = 13 * 8 + 6056   # file header + the ten table headers
+
+
+@functools.lru_cache(maxsize=None)
+def lut_constants():
+    """(DEC_LUT_MAX_BITS, DEC_LUT_BUDGET) as csrc/nice_bits.hpp states them."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    with open(os.path.join(root, "fast-losless-image-compression-format_amd", "csrc", "nice_bits.hpp")) as f:
+        text = f.read()
+    return tuple(int(re.search(r"constexpr\s+int\s+%s\s*=\s*(\d+)\s*;" % name, text).group(1))
+                 for name in ("DEC_LUT_MAX_BITS", "DEC_LUT_BUDGET"))
+
+
+def lut_plan(maxes):
+    """What dec_tables decides from the ten table maxima: (lut_bits,
+    long_streams, longest_event_bits, fast).  First-level widths start at
+    min(max, DEC_LUT_MAX_BITS); while their 2^width sum is over DEC_LUT_BUDGET
+    the widest table (the first of equally wide ones) loses a bit.  A stream
+    whose max is above its width has long codes (the max is attained).  The
+    longest pixel event is the prefix max plus the longest payload sequence;
+    the frame takes the fast parse when no stream has long codes and that
+    event fits 64 bits."""
+    max_bits, budget = lut_constants()
+    maxes = [int(m) for m in maxes]
+    assert len(maxes) == 10
+    lut_bits = [min(m, max_bits) for m in maxes]
+    tot = sum(1 << b for b in lut_bits)
+    while tot > budget:
+        w = lut_bits.index(max(lut_bits))
+        tot -= 1 << (lut_bits[w] - 1)
+        lut_bits[w] -= 1
+    long_streams = [st for st in range(10) if maxes[st] > lut_bits[st]]
+    longest = maxes[1] + max(sum(maxes[st] for st in pay) for pay in PAY_STREAMS)
+    return lut_bits, long_streams, longest, (not long_streams and longest <= 64)
+
+
+def header_lengths(s):
+    """The ten tables of a stream's header: [(max field, lengths array)]."""
+    bits = np.unpackbits(np.frombuffer(s[13:13 + 6056 // 8], np.uint8))
+    out, pos = [], 0
+    for n in SIZES:
+        f = bits[pos:pos + 5 + 7 * n]
+        mx = int(f[:5] @ (1 << np.arange(4, -1, -1)))
+        out.append((mx, (f[5:].reshape(n, 7) @ (1 << np.arange(6, -1, -1))).astype(np.uint8)))
+        pos += 5 + 7 * n
+    return out
 
 
 class _Bits:
@@ -63,8 +115,67 @@ def _lengths(O, rng, n, deep_lo=None, deep_hi=None):
 NO_DEEP = -1   # make_stream(deep=NO_DEEP): every table <= 24 bits
 
 
+def _shaped_lengths(rng, n, mx, pin=()):
+    """Lengths written directly: a complete code (Kraft sum 1) of n symbols
+    whose longest code has exactly mx bits.  A flat code of n - t symbols,
+    then t times one of the longest codes split in two; t is the one at which
+    the maximum comes out as mx.  The symbols in `pin` get the longest codes,
+    in that order; the others are permuted."""
+    for t in range(n - 1):
+        m = n - t
+        k = (m - 1).bit_length()
+        if k + t == mx:
+            break
+    else:
+        raise ValueError((n, mx))
+    ls = [k] * m if m == 1 << k else [k - 1] * ((1 << k) - m) + [k] * (2 * m - (1 << k))
+    for _ in range(t):
+        ls.sort()
+        top = ls.pop()
+        ls += [top + 1, top + 1]
+    ls.sort(reverse=True)
+    assert len(ls) == n and ls[0] == mx and min(ls) >= 1 and sum(1 << (mx - l) for l in ls) == 1 << mx
+    rest = [int(v) for v in rng.permutation(n) if int(v) not in pin]
+    out = np.zeros(n, np.uint8)
+    out[list(pin) + rest] = ls
+    return out
+
+
+def _flat_lengths(O, rng, n):
+    """Near-flat counts (30..60, a narrower range where those give a longer
+    code) whose longest code has ceil(log2 n) bits, the shortest maximum."""
+    for lo in (30, 40, 50, 55, 60):
+        aob = O.code_lengths(rng.integers(lo, 61, n).astype(np.uint64))
+        if int(aob.max()) == (n - 1).bit_length():
+            return aob
+    raise RuntimeError("equal counts gave no flat table")
+
+
+TABLES = ("flat", "long_event", "all12")
+
+
+def _profile_lengths(O, rng, tables):
+    """The ten tables of a profile (make_stream's `tables`)."""
+    if tables == "flat":        # no code over 9 bits: the fast parse, short events
+        shaped = {}
+    elif tables == "long_event":
+        # the largest tables the fast parse takes; a LUMA pixel of the longest
+        # codes is 12 + 10 + 11 + 12 + 12 bits.  Prefix: LUMA 12 bits, the run
+        # digits the next longest, RGB 1 bit
+        shaped = {1: (12, [2, 12, 11, 10, 9, 8, 7, 6, 5, 4, 0, 3, 1]), 2: (11, []), 3: (12, []), 4: (10, [])}
+    elif tables == "all12":
+        # the general parse, long codes in eight streams; the prefix stream's
+        # are LUMA2's (12 bits) and those of the run digits 3 (12) and 6 (11)
+        shaped = {st: (12, [4, 8, 11] if st == 1 else []) for st in (0, 1, 2, 3, 5, 6, 7, 8)}
+        shaped.update({4: (10, []), 9: (10, [])})
+    else:
+        raise ValueError(tables)
+    return [_shaped_lengths(rng, n, *shaped[st]) if st in shaped else _flat_lengths(O, rng, n)
+            for st, n in enumerate(SIZES)]
+
+
 def make_stream(O, seed, W=None, H=None, deep=None, deep_lo=25, deep_hi=31, zero_digits=True, uniform=False,
-                run_p=0.25, run_max=80):
+                run_p=0.25, run_max=80, tables=None, long_p=0.0):
     """One random stream.  Returns (bytes, info dict); info["pixels"] is what
     each pixel was written as: (mode, k) with the prefix ids as modes (0 back
     reference, 1 rgb, 2 luma, 3 small diff, 4 luma2) and k the reference index
@@ -73,15 +184,32 @@ def make_stream(O, seed, W=None, H=None, deep=None, deep_lo=25, deep_hi=31, zero
     every pixel draws its mode uniformly among the valid ones (k is always
     uniform among the valid ones); run_p, run_max: how often a run follows a
     pixel and its longest length.  The defaults draw what they always drew
-    (tests/test_strict_refill.py depends on the streams of its seeds)."""
+    (tests/test_strict_refill.py depends on the streams of its seeds).
+
+    tables: a profile of table shapes instead of tables from random counts
+    (one of TABLES, see _profile_lengths; no deep table then).  long_p: the
+    probability that a pixel is written with the long symbols of its streams
+    (the codes over the first-level width where lut_plan gives the stream
+    such, else its longest codes) and a uniformly drawn mode; with
+    "long_event" such a pixel is the longest valid event, a LUMA pixel of the
+    longest code of each of its streams.
+
+    info["events"] holds, for every prefix read (a coded pixel, every run
+    digit, the extra prefix at the end): (bit position relative to the data
+    start, bit length of the event, [(stream, symbol, code length), ...]);
+    info["lens"] the ten tables."""
     rng = np.random.default_rng(seed)
     W = int(W if W is not None else rng.integers(4, 40))
     H = int(H if H is not None else rng.integers(1, 8))
     N = W * H
-    if deep is None:
-        deep = int(rng.choice(DEEP_STREAMS))
-    lens = [_lengths(O, rng, n, deep_lo, deep_hi) if st == deep else _lengths(O, rng, n)
-            for st, n in enumerate(SIZES)]
+    if tables is not None:
+        deep = NO_DEEP
+        lens = _profile_lengths(O, rng, tables)
+    else:
+        if deep is None:
+            deep = int(rng.choice(DEEP_STREAMS))
+        lens = [_lengths(O, rng, n, deep_lo, deep_hi) if st == deep else _lengths(O, rng, n)
+                for st, n in enumerate(SIZES)]
     codes = [O.canonical(l) for l in lens]
     b = _Bits()
     for st in range(10):
@@ -90,8 +218,24 @@ def make_stream(O, seed, W=None, H=None, deep=None, deep_lo=25, deep_hi=31, zero
             b.put(int(v), 7)
     assert len(b.bits) == 6056
 
+    events = []
+
     def sym(st, v):
-        b.put(int(codes[st][v]), int(lens[st][v]))
+        n = int(lens[st][v])
+        if st == 1:
+            events.append((len(b.bits) - 6056, []))
+        events[-1][1].append((st, int(v), n))
+        b.put(int(codes[st][v]), n)
+
+    long = False   # the pixel being written takes its streams' long symbols
+    if long_p:
+        lut_bits = lut_plan([l.max() for l in lens])[0]
+        longsym = [np.nonzero(l > wd)[0] if (l > wd).any() else np.nonzero(l == l.max())[0]
+                   for l, wd in zip(lens, lut_bits)]
+        k_long = int(longsym[4][0])
+
+    def draw(st):
+        return int(rng.choice(longsym[st])) if long else rng.integers(SIZES[st])
 
     # mode weights: how often the deep stream is read decides how likely a
     # wrapping read is, so both outcomes occur
@@ -100,9 +244,13 @@ def make_stream(O, seed, W=None, H=None, deep=None, deep_lo=25, deep_hi=31, zero
     i = 0
     while i < N:
         k = 0
+        long = bool(long_p) and i > 0 and rng.random() < long_p
+        longest = long and tables == "long_event" and 0 < LUMA_OFF(W)[k_long] <= i
         if i == 0:
             mode = 1   # RGB (predicts from pixel 0 itself, code.rs:640)
-        elif uniform:
+        elif longest:
+            mode = 2
+        elif uniform or long:
             mode = int(rng.integers(5 if i >= W else 4))
         else:
             mode = int(rng.choice(5, p=w / w.sum()))
@@ -112,14 +260,14 @@ def make_stream(O, seed, W=None, H=None, deep=None, deep_lo=25, deep_hi=31, zero
             k = int(rng.choice([k for k, o in enumerate(BR_OFF(W)) if 0 < o <= i]))
             sym(1, 0); sym(9, k)
         elif mode == 1:
-            sym(1, 1); sym(0, rng.integers(256)); sym(0, rng.integers(256)); sym(0, rng.integers(256))
+            sym(1, 1); sym(0, draw(0)); sym(0, draw(0)); sym(0, draw(0))
         elif mode == 2:
-            k = int(rng.choice([k for k, o in enumerate(LUMA_OFF(W)) if 0 < o <= i]))
-            sym(1, 2); sym(4, k); sym(2, rng.integers(64)); sym(3, rng.integers(32)); sym(3, rng.integers(32))
+            k = k_long if longest else int(rng.choice([k for k, o in enumerate(LUMA_OFF(W)) if 0 < o <= i]))
+            sym(1, 2); sym(4, k); sym(2, draw(2)); sym(3, draw(3)); sym(3, draw(3))
         elif mode == 3:
-            sym(1, 3); sym(5, rng.integers(343))
+            sym(1, 3); sym(5, draw(5))
         else:
-            sym(1, 4); sym(6, rng.integers(64)); sym(7, rng.integers(32)); sym(8, rng.integers(32))
+            sym(1, 4); sym(6, draw(6)); sym(7, draw(7)); sym(8, draw(8))
         pixels[i] = (mode, k)
         i += 1
         if i < N and rng.random() < run_p:
@@ -138,11 +286,12 @@ def make_stream(O, seed, W=None, H=None, deep=None, deep_lo=25, deep_hi=31, zero
     hdr = b"nice" + W.to_bytes(4, "big") + H.to_bytes(4, "big") + bytes([3])
     tail = bytes(rng.integers(0, 256, int(rng.integers(0, 6)), dtype=np.uint8)) + bytes(5)
     info = {"W": W, "H": H, "deep": deep, "max": int(lens[deep].max() if deep != NO_DEEP else max(l.max() for l in lens)),
-            "pixels": pixels}
+            "pixels": pixels, "lens": lens,
+            "events": [(pos, sum(n for _, _, n in syms), syms) for pos, syms in events]}
     return hdr + b.tobytes() + tail, info
 
 
-def make_slow_sync(O, seed, W, H, every=20):
+def make_slow_sync(O, seed, W, H, every=20, flat_small_diff=False):
     """A stream whose Huffman parse re-synchronises only after thousands of
     bits (the Jacobi fixpoint of the slice-parallel parse then needs tens of
     iterations).  Every pixel is RGB with zero residuals except one pixel in
@@ -151,7 +300,10 @@ def make_slow_sync(O, seed, W, H, every=20):
     zero pixel is 25 zero bits and a parse that starts at the wrong bit keeps
     reading 25-bit zero events at that offset; only the SMALL_DIFF pixels can
     move it, and each lands it on the true boundary with probability about
-    1/25.  Returns the stream (header channels 3)."""
+    1/25.  flat_small_diff: the SMALL_DIFF table from equal counts (codes of 8
+    and 9 bits) instead of random ones (13 bits and long codes): the same kind
+    of stream, breakers included, on tables for which lut_plan says fast.
+    Returns the stream (header channels 3)."""
     rng = np.random.default_rng(seed)
     N = W * H
     lens = []
@@ -163,6 +315,8 @@ def make_slow_sync(O, seed, W, H, every=20):
             counts[1] = 1 << 20                               # RGB prefix: 1 bit
         else:
             counts = rng.integers(1, 60, n).astype(np.uint64)
+            if st == 5 and flat_small_diff:
+                counts[:] = 1000
         lens.append(O.code_lengths(counts))
     codes = [O.canonical(l) for l in lens]
     assert int(lens[1][1]) == 1 and int(codes[1][1]) == 0

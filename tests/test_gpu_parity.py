@@ -100,21 +100,49 @@ def test_decode_matches(nice, O, case):
 
 
 @pytest.mark.parametrize("parse", ["fast", "general"])
-def test_decode_parse_paths(nice, O, parse, opts):
+def test_decode_parse_paths(nice, O, parse, opts, capfd):
     """dec_sync decodes a frame whose codes all fit the first-level tables and
     whose pixel events fit 64 bits from one window per event (DecTables::fast),
     others symbol by symbol with refills and the long-code search; forcing the
-    general path (NICE_DEC_SLOW_PARSE) must give the same pixels."""
+    general path (NICE_DEC_SLOW_PARSE) must give the same pixels.
+
+    Which parse a frame's tables allow is read from the statistics and must be
+    what crafted_streams.lut_plan gives the table maxima worked out from the
+    header's lengths (parse_streams.tolerant_maxes, which the reported maxima
+    must equal).  Only syn512x4 and
+    syn1920x1080x4 are fast; syn256x3, odd37x23x4, noise300x200x3,
+    stripes700x300x3, palette333x90x3 and wide9000x6x3 have tables with codes
+    over their first-level width, so both values of `parse` run them on the
+    general parse (tests/test_parse_paths.py has small streams for the fast
+    one)."""
+    import crafted_streams as C
+    import parse_streams as PS
+    opts.setenv("NICE_DEC_STATS", 1)
     if parse == "general":
         opts.setenv("NICE_DEC_SLOW_PARSE", "1")
+    fast_cases = []
     for name, px, w, h, c in CASES:
         if name not in ("syn512x4", "syn1920x1080x4", "syn256x3", "odd37x23x4", "noise300x200x3",
                         "stripes700x300x3", "palette333x90x3", "wide9000x6x3"):
             continue
         # tolerant header: small frames spill the 5-bit max field (hfe.rs:97-99)
-        got, _ = nice.decode_bytes(O.encode(px, w, h, c), flags=nice.DEC_ALPHA_FILL_FF | nice.DEC_TOLERANT_HEADER)
+        s = O.encode(px, w, h, c)
+        got, _ = nice.decode_bytes(s, flags=nice.DEC_ALPHA_FILL_FF | nice.DEC_TOLERANT_HEADER)
         g = np.frombuffer(got, np.uint8).reshape(-1, c)
         assert np.array_equal(g[:, :3], px.reshape(-1, c)[:, :3]), (name, parse)
+        ps = PS.parse_stats(capfd.readouterr().err)
+        print(name, ps)
+        maxes = PS.tolerant_maxes(s)   # from the header's lengths, spilled max fields repaired
+        hdr = C.header_lengths(s)
+        if all(mx == int(lens.max()) for mx, lens in hdr):   # nothing spilled: the max fields themselves
+            assert maxes == [mx for mx, _ in hdr], name
+        lut_bits, _, _, fast = C.lut_plan(maxes)
+        assert ps["max"] == maxes, (name, ps, maxes)
+        assert (ps["frames"], ps["fast"], ps["lut_bits"]) == (1, int(fast), lut_bits), (name, ps)
+        assert ps["slow_parse"] == int(parse == "general"), (name, ps)
+        if fast:
+            fast_cases.append(name)
+    assert fast_cases == ["syn512x4", "syn1920x1080x4"], fast_cases
 
 
 @pytest.mark.parametrize("case", [c for c in CASES if c[4] == 3], ids=[c[0] for c in CASES if c[4] == 3])

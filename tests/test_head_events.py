@@ -15,8 +15,8 @@ import numpy as np
 import pytest
 
 import crafted_streams as C
-
-OPT_DEC_HEV_CAP = 15          # include/nice_test.h: NICE_OPT_DEC_HEV_CAP
+import parse_streams as PS
+from parse_streams import OPT_DEC_HEV_CAP
 DATA_START_BITS = 13 * 8 + 6056   # file header + the ten table headers
 
 SHAPES = [(256, 256, 4), (256, 256, 3), (257, 130, 4), (257, 130, 3)]
@@ -49,11 +49,7 @@ def _set_hev_cap(opts, v):
     assert opts.L.nice_test_set_option(OPT_DEC_HEV_CAP, v) == 0
 
 
-def _head_stats(err):
-    """The 'slice heads' line of the decoder's statistics as a dict."""
-    line = [l for l in err.splitlines() if "slice heads:" in l][-1]
-    body = line.split("slice heads:")[1].split("(")[0]
-    return {k: int(v) for k, v in (kv.split("=") for kv in body.split())}
+_head_stats = PS.head_stats   # the 'slice heads' line of the decoder's statistics as a dict
 
 
 def test_streams_have_many_slices(O):
@@ -70,11 +66,20 @@ def test_streams_have_many_slices(O):
 @pytest.mark.parametrize("slice_bits", SLICES)
 @pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "%dx%dx%d" % s)
 def test_decode_matches_oracle(nice, O, opts, capfd, shape, slice_bits, mode):
-    """Fast and general parse, with the heads placed (default) and with a head
-    buffer of 4 events, which every head overflows, so dec_emit parses them as
-    before: the same pixels either way."""
+    """With the heads placed (default) and with a head buffer of 4 events,
+    which every head overflows, so dec_emit parses them as before: the same
+    pixels either way.
+
+    All four shapes take the general parse: their SMALL_DIFF table has 17 bits
+    and their LUMA2_BASE table 13, over the 12-bit first level, so
+    DecTables::fast is 0 and "default" runs the code "slow_parse" forces (the
+    statistics' parse line is asserted to say so).  The fast parse at these
+    slice sizes is tests/test_parse_paths.py's, on a 512x512 frame and on
+    hand-built streams."""
     w, h, c = shape
     s, want = _syn(O, w, h, c)
+    lut_bits, long_streams, _, fast = C.lut_plan(PS.maxes(s))
+    assert long_streams == [5, 6] and not fast
     opts.setenv("NICE_DEC_SLICE_BITS", slice_bits)
     opts.setenv("NICE_DEC_STATS", 1)
     if "slow_parse" in mode:
@@ -83,7 +88,11 @@ def test_decode_matches_oracle(nice, O, opts, capfd, shape, slice_bits, mode):
         _set_hev_cap(opts, 4)
     got = _gpu_rgb(nice, s, c)
     assert np.array_equal(got, want)
-    st = _head_stats(capfd.readouterr().err)
+    err = capfd.readouterr().err
+    ps = PS.parse_stats(err)
+    assert (ps["frames"], ps["fast"], ps["max"], ps["lut_bits"]) == (1, 0, PS.maxes(s), lut_bits), ps
+    assert ps["slow_parse"] == int("slow_parse" in mode), ps
+    st = _head_stats(err)
     print(st)
     assert st["invariant_violations"] == 0
     assert sum(st[k] for k in ("none", "placed", "emitted", "whole_slice_emitted")) == _n_slices(s, slice_bits)
