@@ -385,7 +385,8 @@ struct LutLds {
   uint8_t len[N_BINS];
   uint32_t gp[16];    // per stream: lut_off | lut_bits << 16 | max_aob << 24
   uint32_t gs[16];    // per stream: canonical-order base | alphabet size << 16
-  uint4 pp[8];        // fast parse: per prefix 0..4, the fast_param of its payload streams 0..3
+  uint4 pp[8];        // fast parse: per prefix 0..4, the fast_param of its payload streams 0..3,
+                      // and in bits 5..9 (which a lookup ignores) the symbol's place in the event word
 };
 
 __device__ inline void load_lut(LutLds& S, const DecTables* T) {
@@ -408,7 +409,7 @@ __device__ inline void load_lut(LutLds& S, const DecTables* T) {
 #pragma unroll
     for (uint32_t i = 0; i < 4; ++i) {
       const uint32_t st = m < 5u ? pay_stream(m, i) : 0u;
-      w[i] = (32u - T->lut_bits[st]) | ((uint32_t)T->lut_off[st] << 17);
+      w[i] = (32u - T->lut_bits[st]) | (ev_shift(m, i) << 5) | ((uint32_t)T->lut_off[st] << 17);
     }
     S.pp[m] = make_uint4(w[0], w[1], w[2], w[3]);
   }
@@ -499,7 +500,8 @@ __device__ __forceinline__ bool lane_ok_fast(const Lane& L) {
 }
 // Fast-path stream parameter: (32 - table width) | 2 * table offset << 16, so a
 // lookup's byte address is ((v >> shift) << 17 + param) >> 16 (shifts use the
-// low 5 bits of their operand).
+// low 5 bits of their operand; bits 5..15 do not reach the address, and S.pp
+// keeps the symbol's event-word shift in bits 5..9: ev_shift).
 __device__ __forceinline__ uint32_t fast_param(uint32_t gp) {
   return (32u - ((gp >> 16) & 31u)) | ((gp & 0xFFFFu) << 17);
 }
@@ -602,10 +604,14 @@ __device__ __forceinline__ uint32_t pixel_event_fast(Lane& L, const uint32_t* my
 }
 
 // pixel_event_fast at ring word o, bit sh of it (dec_sync's relative-position
-// loop); returns the prefix and the event's bit count in tot.
+// loop); returns the prefix and the event's bit count in tot.  EV: also the
+// coded pixel's event word (ev_pack), each symbol shifted to its place by the
+// shift its parameter word carries -- off the chain of dependent lookups.
+template <bool EV = false>
 __device__ __forceinline__ uint32_t pixel_event_fast_at(const uint32_t* my, const LutLds& S, uint32_t fp_pfx,
                                                         uint32_t o, uint32_t sh, uint32_t& s0, uint32_t& s1,
-                                                        uint32_t& s2, uint32_t& s3, uint32_t& tot) {
+                                                        uint32_t& s2, uint32_t& s3, uint32_t& tot,
+                                                        uint32_t* evw = nullptr) {
   const uint32_t w0 = my[o], w1 = my[o + 1], w2 = my[o + 2];
   unsigned long long win = ((((unsigned long long)w0 << 32) | w1) << sh) | (((unsigned long long)w2 << sh) >> 32);
   tot = 0;
@@ -614,10 +620,15 @@ __device__ __forceinline__ uint32_t pixel_event_fast_at(const uint32_t* my, cons
     const bool rgb = pfx == (uint32_t)P_RGB, lu = pfx == (uint32_t)P_LUMA, l2 = pfx == (uint32_t)P_LUMA2;
     const uint4 pp = S.pp[pfx];
     s0 = fsym(win, tot, S, pp.x);
+    if constexpr (EV) *evw = (pfx << EV_PFX_SHIFT) | (s0 << ((pp.x >> 5) & 31u));
     if (rgb || lu || l2) {
       s1 = fsym(win, tot, S, pp.y);
       s2 = fsym(win, tot, S, pp.z);
-      if (lu) s3 = fsym(win, tot, S, pp.w);
+      if constexpr (EV) *evw |= (s1 << ((pp.y >> 5) & 31u)) | (s2 << ((pp.z >> 5) & 31u));
+      if (lu) {
+        s3 = fsym(win, tot, S, pp.w);
+        if constexpr (EV) *evw |= s3 << ((pp.w >> 5) & 31u);
+      }
     }
   }
   return pfx;
@@ -709,12 +720,7 @@ __device__ __forceinline__ uint32_t slice_route(const DecArgs& a, uint64_t base,
   return SLICE_PLACE;
 }
 
-// Event word of a coded pixel: its prefix and payload symbols as read
-// (SMALL_DIFF index < 343, bytes < 256; LUMA: reference < 11, so its fourth
-// symbol fits bits 7..11); dec_place turns it into a record.
-__device__ __forceinline__ uint32_t ev_pack(uint32_t pfx, uint32_t s0, uint32_t s1, uint32_t s2, uint32_t s3) {
-  return pfx | (s0 << 3) | (s1 << 12) | (s2 << 20) | (pfx == (uint32_t)P_LUMA ? s3 << 7 : 0u);
-}
+// (The event word of a parsed pixel -- ev_pack -- is nice_dec_event.hpp's.)
 
 // ---------------------------------------------------------------------------
 // D1: sync iteration (Jacobi, in place).  Each lane parses its slice from the
@@ -900,8 +906,9 @@ __global__ __launch_bounds__(DEC_PARSE_THREADS) PARSE_ATTR void dec_sync(DecArgs
         rfill = (wsr + RING_W - 2u) << 5;
       }
       if (active) {
-        uint32_t s0 = 0, s1 = 0, s2 = 0, s3 = 0, tot;
-        const uint32_t pfx = pixel_event_fast_at(my, S, fp_pfx, (r >> 5) - wsr, r & 31u, s0, s1, s2, s3, tot);
+        uint32_t s0 = 0, s1 = 0, s2 = 0, s3 = 0, tot, evw = 0;
+        const uint32_t pfx = pixel_event_fast_at<KEEP || HEAD>(my, S, fp_pfx, (r >> 5) - wsr, r & 31u, s0, s1, s2,
+                                                               s3, tot, &evw);
         r += tot;
         uint32_t c;
         if (pfx < (uint32_t)P_RUN1) {
@@ -919,7 +926,7 @@ __global__ __launch_bounds__(DEC_PARSE_THREADS) PARSE_ATTR void dec_sync(DecArgs
         }
         px = sat_add(px, c);
         if (KEEP && keep) {
-          const uint32_t ev = pfx < (uint32_t)P_RUN1 ? ev_pack(pfx, s0, s1, s2, s3) : EV_RUN | min(c, EV_RUN - 1u);
+          const uint32_t ev = pfx < (uint32_t)P_RUN1 ? evw : EV_RUN | min(c, EV_RUN - 1u);
           if constexpr (SLOT == 0) q0 = ev;
           if constexpr (SLOT == 1) q1 = ev;
           if constexpr (SLOT == 2) q2 = ev;
@@ -930,7 +937,7 @@ __global__ __launch_bounds__(DEC_PARSE_THREADS) PARSE_ATTR void dec_sync(DecArgs
           ++ne;
         }
         if (HEAD && hkeep) {   // (every re-parsing lane of the wave starts at event 0 in the same step)
-          const uint32_t ev = pfx < (uint32_t)P_RUN1 ? ev_pack(pfx, s0, s1, s2, s3) : EV_RUN | min(c, EV_RUN - 1u);
+          const uint32_t ev = pfx < (uint32_t)P_RUN1 ? evw : EV_RUN | min(c, EV_RUN - 1u);
           if constexpr (SLOT == 0) q0 = ev;
           if constexpr (SLOT == 1) q1 = ev;
           if constexpr (SLOT == 2) q2 = ev;
@@ -1341,46 +1348,8 @@ __global__ __launch_bounds__(DEC_PARSE_THREADS) void dec_strict_refill(DecArgs a
 // one 16-byte store when the group lies inside the lane's pixel range.
 // ---------------------------------------------------------------------------
 
-// Record of a completed coded pixel (branch-free), as an event word: the
-// record in its spread layout (REC_K: the constant in bits 0-7, 10-17 and
-// 20-27; the class in bits 28-31) with, in two of the gap bits that later
-// take the call's tag (REC_TAG_MASK: bits 8-9 and 18-19), EV_L2 (bit 8, LUMA2:
-// needs the row above) and EV_BAD (bit 9: an index the reference rejects
-// wherever the pixel is, or an offset that wraps for W < 3).  The
-// position-dependent checks are rec_bad_at's.
-__device__ __forceinline__ uint32_t make_event_rec(uint64_t W, uint32_t mode, uint32_t s0, uint32_t s1,
-                                                   uint32_t s2, uint32_t s3) {
-  const bool isbr = mode == P_BACK_REF, islu = mode == P_LUMA;
-  const bool issd = mode == P_SMALL_DIFF, isl2 = mode == P_LUMA2;
-  const uint32_t id = min(isbr ? s0 : 5u + s0, 15u);
-  const uint32_t cls = (uint32_t)(ID_CLS_PACK >> (4 * id)) & 15u;
-  const uint64_t rows = (CLS_ROWS_PACK >> (2 * cls)) & 3u;
-  const int64_t off = (int64_t)(rows * W) + (int64_t)((CLS_PX_PACK >> (3 * cls)) & 7u) - 3;
-  const bool bad0 = (isbr && s0 >= 5u) || (islu && s0 >= 11u) || off < 0;
-  const uint32_t gl = (s1 - 32u) & 255u;
-  const uint32_t c_lu = ((s2 - 16u + gl) & 255u) | (gl << 10) | (((s3 - 16u + gl) & 255u) << 20);
-  const uint32_t rd = s0 % 7u, t1 = s0 / 7u;
-  const uint32_t c_sd = ((rd - 3u) & 255u) | ((((t1 % 7u) - 3u) & 255u) << 10) | ((((t1 / 7u) - 3u) & 255u) << 20);
-  const uint32_t g2 = (s0 - 32u) & 255u;
-  const uint32_t c_l2 = ((s1 - 16u + g2) & 255u) | (g2 << 10) | (((s2 - 16u + g2) & 255u) << 20);
-  const uint32_t c_rgb = (s0 & 255u) | ((s1 & 255u) << 10) | ((s2 & 255u) << 20);
-  const uint32_t r = (isbr || islu) ? ((cls << 28) | (islu ? c_lu : 0u)) : issd ? c_sd : isl2 ? c_l2 : c_rgb;
-  return r | (isl2 ? EV_L2 : 0u) | ((isbr || islu) && bad0 ? EV_BAD : 0u);
-}
-// The reference panics on this pixel at position q: a reference before the
-// image start (code.rs:141-145 offsets) or LUMA2 on the first row (code.rs:583).
-__device__ __forceinline__ bool rec_bad_at(uint32_t ev, uint64_t q, uint64_t W) {
-  const uint32_t cls = rec_cls(ev);
-  const uint64_t rows = (CLS_ROWS_PACK >> (2 * cls)) & 3u;
-  const uint64_t off = rows * W + ((CLS_PX_PACK >> (3 * cls)) & 7u) - 3u;   // >= 0 unless EV_BAD
-  return (ev & EV_BAD) || ((ev & EV_L2) ? q < W : (cls != 0u && q < off));
-}
-__device__ __forceinline__ uint32_t make_record(uint64_t W, uint64_t q, uint32_t mode, uint32_t s0,
-                                                uint32_t s1, uint32_t s2, uint32_t s3, bool& bad) {
-  const uint32_t ev = make_event_rec(W, mode, s0, s1, s2, s3);
-  bad = rec_bad_at(ev, q, W);
-  return ev & ~(EV_L2 | EV_BAD);
-}
+// (make_record and its two halves, make_event_rec and rec_bad_at, are
+// nice_dec_event.hpp's: dec_emit's record from a pixel's symbols.)
 
 struct RecGroup {
   unsigned long long grp;   // first pixel of the aligned group, ~0: empty (u64: no collision with pixels)
@@ -1640,73 +1609,31 @@ __global__ __launch_bounds__(1024) void dec_heads(DecArgs a) {
 // extra prefix the reference reads (strict: a run digit there is an error),
 // a run past N or a reference the reference rejects sets NICE_E_FORMAT.
 // ---------------------------------------------------------------------------
-// make_record for dec_place: 32-bit arithmetic (q <= N <= 2^30, 3W < 2^32),
-// the SMALL_DIFF constant from a table (sdl: 343 packed constants in LDS), the
-// reference's class and offset from another (idt: 16 entries per block).
-__device__ __forceinline__ uint32_t place_record(uint32_t ev, uint32_t q, uint32_t W, const uint32_t* sdl,
-                                                 const uint2* idt, bool& bad) {
-  const uint32_t pfx = ev & 7u;
-  // prefix tests as bits of one mask: as == compares of one value, the
-  // compiler turned the selects below into a switch of exec-masked branches
-  const uint32_t pm = 1u << pfx;
-  const bool isbr = (pm & (1u << P_BACK_REF)) != 0u, islu = (pm & (1u << P_LUMA)) != 0u;
-  const bool issd = (pm & (1u << P_SMALL_DIFF)) != 0u, isl2 = (pm & (1u << P_LUMA2)) != 0u;
-  const uint32_t s0 = (ev >> 3) & 511u, s1 = (ev >> 12) & 255u, s2 = (ev >> 20) & 255u, s3 = (ev >> 7) & 31u;
-  const uint32_t s0l = s0 & 15u;   // LUMA: the reference (bits 3..6)
-  const uint32_t id = min(isbr ? s0 : 5u + s0l, 15u);
-  // class and offset + 3 of the reference from the block's 16-entry table
-  // (one 8-byte LDS read instead of two packed-constant extractions, one of
-  // them across a word boundary, which compiled to a branch)
-  const uint2 ct = idt[id];
-  const uint32_t cls = ct.x, off3 = ct.y;
-  const bool bad_ref = (isbr && s0 >= 5u) || (islu && s0l >= 11u) || off3 < 3u || q + 3u < off3;
-  const uint32_t gl = (s1 - 32u) & 255u;
-  const uint32_t c_lu = ((s2 - 16u + gl) & 255u) | (gl << 10) | (((s3 - 16u + gl) & 255u) << 20);
-  // (a conflict-free form by two reciprocal multiplies instead of this
-  // gather measured the same: r06zr_ab_place_sdl_arith.log)
-  const uint32_t c_sd = sdl[min(s0, 342u)];
-  const uint32_t g2 = (s0 - 32u) & 255u;
-  const uint32_t c_l2 = ((s1 - 16u + g2) & 255u) | (g2 << 10) | (((s2 - 16u + g2) & 255u) << 20);
-  uint32_t c_rgb = (s0 & 255u) | (s1 << 10) | (s2 << 20);
-  bad = (isbr || islu) ? bad_ref : (isl2 && q < W);
-  // the candidates opaque: otherwise the select chain compiles to a switch of
-  // exec-masked branches on the prefix (about 35 scalar instructions and 8
-  // branches per event, every prefix present in most waves)
-  uint32_t c_br = (cls << 28) | (islu ? c_lu : 0u);
-  uint32_t c_sd2 = c_sd, c_l22 = c_l2;
-  asm volatile("" : "+v"(c_br), "+v"(c_sd2), "+v"(c_l22), "+v"(c_rgb));
-  return (isbr || islu) ? c_br : issd ? c_sd2 : isl2 ? c_l22 : c_rgb;
-}
-
-// SMALL_DIFF index -> record constant (code.rs:230-247): index = rd + 7 gd + 49 bd
-// (each difference + 3), constant = the three differences in spread form
-struct alignas(16) SdlTable {
-  uint32_t v[344];
-};
-constexpr SdlTable make_sdl_table() {
-  SdlTable t{};
-  for (uint32_t i = 0; i < 343u; ++i) {
-    const uint32_t rd = i % 7u, t1 = i / 7u;
-    t.v[i] = ((rd - 3u) & 255u) | ((((t1 % 7u) - 3u) & 255u) << 10) | ((((t1 / 7u) - 3u) & 255u) << 20);
-  }
-  return t;
-}
+// The record comes from the event word by place_record (nice_dec_event.hpp):
+// masks from a table entry per (reference id, prefix) instead of compares and
+// selects on the prefix, the SMALL_DIFF constant from a table (kSdl in LDS).
 __device__ __constant__ SdlTable kSdl = make_sdl_table();
 
 __global__ __launch_bounds__(64 * DEC_PLACE_WAVES) void dec_place(DecArgs a) {
-  __shared__ __attribute__((aligned(16))) uint32_t sdl[344];   // kSdl (code.rs:230-247)
-  __shared__ uint2 idt[16];       // reference id -> {class, rows * W + px + 3}
-  if (threadIdx.x < 16u) {
-    const uint32_t id = threadIdx.x;
-    const uint32_t cls = (uint32_t)(ID_CLS_PACK >> (4u * id)) & 15u;
-    idt[id] = make_uint2(cls, (uint32_t)((CLS_ROWS_PACK >> (2u * cls)) & 3u) * a.W +
-                                  (uint32_t)((CLS_PX_PACK >> (3u * cls)) & 7u));
+  // kSdl (code.rs:230-247), zero up to the 512 words a 9-bit index reaches (a
+  // run event's count bits, read as a SMALL_DIFF index, stay inside)
+  __shared__ __attribute__((aligned(16))) uint32_t sdl[512];
+  __shared__ PlaceEnt idt[PLACE_ENTRIES];   // (reference id, prefix) -> class and masks (place_entry)
+  __shared__ uint32_t off3[PLACE_ENTRIES];  // ... -> pixels needed before the event + 3 (the checked steps)
+  static_assert(64 * DEC_PLACE_WAVES >= PLACE_ENTRIES + 128, "one thread per table entry");
+  if (threadIdx.x >= 64u * DEC_PLACE_WAVES - PLACE_ENTRIES) {   // (the threads that do not fill sdl)
+    const uint32_t entry = threadIdx.x - (64u * DEC_PLACE_WAVES - PLACE_ENTRIES);
+    uint32_t o3;
+    idt[entry] = place_entry(entry, a.W, o3);
+    off3[entry] = o3;
   }
   // copied from a compile-time table: computing the 343 constants in every
   // block (divisions by 7 and 49) cost ~120 VALU per wave, and dec_place runs
   // one short-lived block per four slices
   if (threadIdx.x < 86u)
     reinterpret_cast<uint4*>(sdl)[threadIdx.x] = reinterpret_cast<const uint4*>(kSdl.v)[threadIdx.x];
+  else if (threadIdx.x < 128u)
+    reinterpret_cast<uint4*>(sdl)[threadIdx.x] = make_uint4(0u, 0u, 0u, 0u);
   __syncthreads();
   const uint32_t lane = threadIdx.x & 63u;
   // grid (slices / waves, frames), XCD-aware: consecutive logical blocks are
@@ -1756,6 +1683,8 @@ __global__ __launch_bounds__(64 * DEC_PLACE_WAVES) void dec_place(DecArgs a) {
   unsigned long long q = head ? q_first : q_meet;
   const uint64_t N = (uint64_t)a.W * a.H;
   if (q > N) return;                    // tail bytes
+  // place_deep in 32 bits (q <= N <= 2^30): never, for a row that wide
+  const uint32_t deep32 = 3ull * a.W + 3u > 0xFFFFFFFFull ? 0xFFFFFFFFu : 3u * a.W + 3u;
   uint32_t* rec = a.recs + (uint64_t)f * a.rec_stride;
   const bool strict = (a.flags & NICE_DEC_STRICT_REFERENCE) != 0;
   bool err = false, stopped = false;
@@ -1797,6 +1726,9 @@ __global__ __launch_bounds__(64 * DEC_PLACE_WAVES) void dec_place(DecArgs a) {
     // carries a bad reference -- one uniform check, then plain stores
     {
       const uint32_t N32 = (uint32_t)N;
+      // (wave-uniform) past every reference's reach and the first row: the
+      // step's records take no position check
+      const bool deep = uni((uint32_t)q) >= deep32;
       uint32_t c32[4];
       bool big = false;
 #pragma unroll
@@ -1809,20 +1741,25 @@ __global__ __launch_bounds__(64 * DEC_PLACE_WAVES) void dec_place(DecArgs a) {
         uint32_t qb[4];
         uint32_t base = (uint32_t)q;
         bool stop = false;
+        auto rows = [&](auto check_tag) {
+          constexpr bool CHECK = decltype(check_tag)::value;
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          // rows past the slice's last event (a slice's last step is mostly
-          // empty): skipped by a uniform branch, not computed under a mask
-          if (i + 64u * k >= nev) break;
-          const bool valid = i + 64u * k + lane < nev;
-          const bool run = (ev[k] & EV_RUN) != 0u;
-          const uint32_t incl = wave_incl_scan(c32[k]);
-          qb[k] = base + incl - c32[k];
-          base += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-          bool rbad = false;
-          r[k] = place_record(ev[k], min(qb[k], N32), a.W, sdl, idt, rbad);
-          stop = stop || (valid && (qb[k] >= N32 || (run ? qb[k] + c32[k] > N32 : rbad)));
-        }
+          for (int k = 0; k < 4; ++k) {
+            // rows past the slice's last event (a slice's last step is mostly
+            // empty): skipped by a uniform branch, not computed under a mask
+            if (i + 64u * k >= nev) break;
+            const bool valid = i + 64u * k + lane < nev;
+            const bool run = (ev[k] & EV_RUN) != 0u;
+            const uint32_t incl = wave_incl_scan(c32[k]);
+            qb[k] = base + incl - c32[k];
+            base += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+            bool rbad = false;
+            r[k] = place_record<CHECK>(ev[k], min(qb[k], N32), sdl, idt, off3, rbad);
+            stop = stop || (valid && (qb[k] >= N32 || (run ? qb[k] + c32[k] > N32 : rbad)));
+          }
+        };
+        if (deep) rows(std::false_type{});
+        else rows(std::true_type{});
         if (!__any(stop)) {
 #pragma unroll
           for (int k = 0; k < 4; ++k) {
@@ -1859,7 +1796,7 @@ __global__ __launch_bounds__(64 * DEC_PLACE_WAVES) void dec_place(DecArgs a) {
       carry += __shfl(incl, 63);
       qk[k] = qb;
       bool rbad = false;
-      r[k] = place_record(ev[k], (uint32_t)min(qb, N), a.W, sdl, idt, rbad);
+      r[k] = place_record<true>(ev[k], (uint32_t)min(qb, N), sdl, idt, off3, rbad);
       // a zero-count run event is a zero digit continuing a run (the first
       // digit counts >= 1): at N the reference's run loop reads it and goes on
       const bool at_n = valid && qb == N && !(run && c[k] == 0);

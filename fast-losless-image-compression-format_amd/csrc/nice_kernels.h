@@ -221,10 +221,10 @@ __device__ __forceinline__ const uint8_t* dec_stream_ptr(const DecArgs& a, uint3
   return a.streams + (a.stream_off ? (uint64_t)a.stream_off[f] : (uint64_t)f * a.stream_stride);
 }
 constexpr uint32_t SPLIT_ABORT_ERR = 1u, SPLIT_REDO = 2u;
-// first-pass event of a run digit: EV_RUN | pixels (saturated); a coded
-// pixel's record before its tag: EV_L2 (LUMA2: needs the row above) and EV_BAD
-// in the record's tag bits (make_event_rec, rec_bad_at)
-constexpr uint32_t EV_RUN = 1u << 31, EV_BAD = 1u << 9, EV_L2 = 1u << 8;
+// The event words in ev / hev (nice_dec_event.hpp): a run digit's is EV_RUN |
+// pixels (saturated); a coded pixel's has its prefix in bits 28-30 and its
+// payload symbols in the record's own fields (ev_pack), which place_record
+// turns into the record.  EV_RUN, and dec_emit's EV_L2 / EV_BAD, live there.
 constexpr uint32_t EV_OVERFLOW = 0xFFFFFFFFu, AGREE_NONE = 0xFFFFu;
 
 __global__ void dec_tables(DecArgs a);
