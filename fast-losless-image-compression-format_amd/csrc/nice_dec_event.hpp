@@ -11,15 +11,6 @@
 
 #include "nice_format.h"
 
-// host and device under hipcc (always inlined in a kernel), plain inline elsewhere
-#ifndef NICE_HDI
-#if defined(__HIPCC__) || defined(__CUDACC__)
-#define NICE_HDI __host__ __device__ __forceinline__
-#else
-#define NICE_HDI inline
-#endif
-#endif
-
 namespace nice {
 
 // Record (round 6): the additive constant c in the row kernels' spread form

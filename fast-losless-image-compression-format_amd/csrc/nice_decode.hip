@@ -18,6 +18,10 @@
 //   dec_emit         one 32-bit record per coded pixel (mode + constants).
 // The records go to the row kernels (nice_rows.hip: dec_reconstruct, dec_rows*),
 // which rebuild the pixels row by row.
+// This file keeps the kernels.  The parse machinery and the stages the four
+// parse kernels share are nice_parse.hpp's; the packed words they exchange
+// (slice entry, `last`, checkpoint) and the pixel arithmetic, nice_dec_state.hpp's;
+// the event word and the records, nice_dec_event.hpp's.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -28,14 +32,9 @@
 #include "nice_dec_rec.hpp"
 #include "nice_format.h"
 #include "nice_kernels.h"
+#include "nice_parse.hpp"
 
 namespace nice {
-
-// chunk geometry: chunk j of frame f covers bits [D + j*CB, D + (j+1)*CB)
-__device__ __forceinline__ uint32_t n_chunks(uint64_t len, uint64_t D, uint32_t cb) {
-  const uint64_t bits = len * 8;
-  return bits > D ? (uint32_t)((bits - D + cb - 1) / cb) : 0u;
-}
 
 // ---------------------------------------------------------------------------
 // D0: tables. One block of 256 threads per frame.
@@ -334,393 +333,16 @@ __global__ __launch_bounds__(256) void dec_tables(DecArgs a) {
 #endif
 }
 
-// ---------------------------------------------------------------------------
-// Parse machinery shared by dec_sync and dec_emit.
-//
-// A lane parses one slice of the data bits.  It reads them from a private ring
-// of RING_W big-endian words in LDS, refilled for the whole wave at once with
-// 16-byte loads (consecutive lanes load consecutive 16 bytes of one ring), so
-// the stream is read from HBM in whole lines.  The first-level LUTs and the
-// canonical order for long codes live in LDS.
-//
-// The parse advances one pixel event per step: a prefix symbol, then -- for a
-// coded pixel -- the mode's fixed payload sequence (code.rs:576-644): BACK_REF
-// k; RGB r g b; LUMA ref, g, r, b; SMALL_DIFF index; LUMA2 g r b.  Slices
-// therefore begin and end at prefix positions: a slice's parse stops at the
-// first prefix at or after its end bit, which is where the next slice starts.
-// ---------------------------------------------------------------------------
-#ifndef NICE_RING_W
-#define NICE_RING_W 20
-#endif
-constexpr uint32_t RING_W = NICE_RING_W;   // words per lane ring (a multiple of 4, >= 12)
-constexpr uint32_t RING_STRIDE = RING_W;   // 16-byte aligned rings
-static_assert(RING_W % 4 == 0 && RING_W >= 12, "ring size");
-#ifdef NICE_PARSE_WPE
-#define PARSE_ATTR __attribute__((amdgpu_waves_per_eu(NICE_PARSE_WPE)))
-#else
-#define PARSE_ATTR
-#endif
-constexpr uint32_t RING_QUADS = RING_W / 4;
-constexpr uint32_t PIXEL_WORDS = 5;    // one pixel event: <= 5 symbols of <= 31 bits
-
-constexpr uint32_t PFX_STREAM = S_PREFIX;
-// payload stream i of mode m (code.rs:576-644), 4 bits each at 4 * (4m + i)
-constexpr unsigned long long PAY_STREAMS =
-    ((unsigned long long)S_BACK_REF << 0) |
-    ((unsigned long long)S_RGB << 16) | ((unsigned long long)S_RGB << 20) | ((unsigned long long)S_RGB << 24) |
-    ((unsigned long long)S_LUMA_REF << 32) | ((unsigned long long)S_LUMA_BASE << 36) |
-    ((unsigned long long)S_LUMA_OTHER << 40) | ((unsigned long long)S_LUMA_OTHER << 44) |
-    ((unsigned long long)S_SMALL_DIFF << 48);   // mode 4 (LUMA2): pay_stream
-static_assert(P_BACK_REF == 0 && P_RGB == 1 && P_LUMA == 2 && P_SMALL_DIFF == 3 && P_LUMA2 == 4 &&
-                  P_RUN1 == 5, "prefix numbering");
-__device__ __forceinline__ uint32_t pay_stream(uint32_t m, uint32_t i) {
-  // mode 4 (LUMA2) does not fit the 64-bit table: handled here
-  return m == (uint32_t)P_LUMA2 ? (uint32_t)S_LUMA2_BASE + i : (uint32_t)(PAY_STREAMS >> (4u * (4u * m + i))) & 15u;
-}
-
-struct LutLds {
-  uint16_t lut[DEC_LUT_BUDGET];
-  uint32_t lo[N_BINS];   // canonical order (long codes): aligned lower bounds,
-  uint16_t sym[N_BINS];  // symbols and lengths
-  uint8_t len[N_BINS];
-  uint32_t gp[16];    // per stream: lut_off | lut_bits << 16 | max_aob << 24
-  uint32_t gs[16];    // per stream: canonical-order base | alphabet size << 16
-  uint4 pp[8];        // fast parse: per prefix 0..4, the fast_param of its payload streams 0..3,
-                      // and in bits 5..9 (which a lookup ignores) the symbol's place in the event word
-};
-
-__device__ inline void load_lut(LutLds& S, const DecTables* T) {
-  const uint4* s = reinterpret_cast<const uint4*>(T->lut);
-  uint4* d = reinterpret_cast<uint4*>(S.lut);
-  for (uint32_t i = threadIdx.x; i < sizeof(S.lut) / 16; i += blockDim.x) d[i] = s[i];
-  for (uint32_t i = threadIdx.x; i < N_BINS; i += blockDim.x) {
-    S.lo[i] = T->lo[i];
-    S.sym[i] = T->sym[i];
-    S.len[i] = T->len[i];
-  }
-  if (threadIdx.x < N_STREAMS) {
-    const int st = (int)threadIdx.x;
-    S.gp[st] = (uint32_t)T->lut_off[st] | ((uint32_t)T->lut_bits[st] << 16) | ((uint32_t)T->max_aob[st] << 24);
-    S.gs[st] = (uint32_t)stream_base(st) | ((uint32_t)stream_size(st) << 16);
-  }
-  if (threadIdx.x < 8u) {   // payload streams of each mode (code.rs:576-644), as fast parameters
-    const uint32_t m = threadIdx.x;
-    uint32_t w[4];
-#pragma unroll
-    for (uint32_t i = 0; i < 4; ++i) {
-      const uint32_t st = m < 5u ? pay_stream(m, i) : 0u;
-      w[i] = (32u - T->lut_bits[st]) | (ev_shift(m, i) << 5) | ((uint32_t)T->lut_off[st] << 17);
-    }
-    S.pp[m] = make_uint4(w[0], w[1], w[2], w[3]);
-  }
-}
-
-__device__ __forceinline__ uint32_t stream_word(const uint8_t* p, uint64_t len, uint32_t w) {
-  uint32_t v = 0;
-  for (int k = 0; k < 4; ++k) {
-    const uint64_t i = (uint64_t)w * 4 + k;
-    v = (v << 8) | (i < len ? p[i] : (len ? p[len - 1] : 0u));   // stale last byte past the end
-  }
-  return v;
-}
-
-// Lane bit reader over its LDS ring: a left-aligned 64-bit window (next bit at
-// bit 63) holding `avail` >= 32 valid bits between symbols.
-struct Lane {
-  unsigned long long pos;   // absolute bit position in the frame's stream
-  unsigned long long win;
-  uint32_t avail;
-  uint32_t rp;              // next ring word to shift in
-  uint32_t ws;              // fast parse: stream word held in ring word 0
-};
-// one more pixel event fits in the ring
-__device__ __forceinline__ bool lane_ok(const Lane& L) { return L.rp + PIXEL_WORDS <= RING_W; }
-
-__device__ __noinline__ void ring_fill_slow(uint32_t* dst, const uint8_t* p, uint64_t len, uint32_t w) {
-  dst[0] = stream_word(p, len, w);
-  dst[1] = stream_word(p, len, w + 1);
-  dst[2] = stream_word(p, len, w + 2);
-  dst[3] = stream_word(p, len, w + 3);
-}
-// Wave-cooperative refill: every lane's ring restarts at the word holding its
-// position (rounded down to 16 bytes).  Must be reached by all 64 lanes.
-// ws: the (16-byte aligned) stream word each lane's ring restarts at.
-__device__ __forceinline__ void ring_fill_ws(uint32_t* wring, const uint8_t* p, uint64_t len, bool al16,
-                                             uint32_t ws) {
-  const uint32_t lane = threadIdx.x & 63u;
-  const uint64_t full_words = al16 ? (len >> 2) : 0;   // words fully inside the stream
-  uint4 v[RING_QUADS];
-  uint32_t wq[RING_QUADS];
-#pragma unroll
-  for (uint32_t r = 0; r < RING_QUADS; ++r) {   // issue every load before waiting on any
-    const uint32_t i = lane + 64u * r;
-    const uint32_t owner = i / RING_QUADS, q = i - owner * RING_QUADS;
-    wq[r] = (uint32_t)__shfl((int)ws, (int)owner) + 4u * q;   // all lanes: before any branch
-    const uint64_t wl = (uint64_t)wq[r] + 4 <= full_words ? wq[r] : 0u;
-    v[r] = *reinterpret_cast<const uint4*>(p + wl * 4);
-  }
-#pragma unroll
-  for (uint32_t r = 0; r < RING_QUADS; ++r) {
-    const uint32_t i = lane + 64u * r;
-    const uint32_t owner = i / RING_QUADS, q = i - owner * RING_QUADS;
-    uint32_t* dst = wring + owner * RING_STRIDE + 4u * q;
-    if ((uint64_t)wq[r] + 4 <= full_words) {
-      *reinterpret_cast<uint4*>(dst) = make_uint4(__builtin_bswap32(v[r].x), __builtin_bswap32(v[r].y),
-                                                  __builtin_bswap32(v[r].z), __builtin_bswap32(v[r].w));
-    } else {
-      ring_fill_slow(dst, p, len, wq[r]);
-    }
-  }
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
-}
-template <bool FAST = false>
-__device__ __forceinline__ void ring_fill(uint32_t* wring, const uint8_t* p, uint64_t len, bool al16,
-                                          Lane& L) {
-  const uint32_t lane = threadIdx.x & 63u;
-  const uint32_t ws = (uint32_t)(L.pos >> 5) & ~3u;
-  ring_fill_ws(wring, p, len, al16, ws);
-  if constexpr (FAST) {
-    L.ws = ws;
-  } else {
-    const uint32_t* my = wring + lane * RING_STRIDE;
-    const uint32_t o = (uint32_t)(L.pos >> 5) - ws;
-    const uint32_t sh = (uint32_t)(L.pos & 31u);
-    L.win = (((unsigned long long)my[o] << 32) | my[o + 1]) << sh;
-    L.avail = 64u - sh;
-    L.rp = o + 2u;
-  }
-}
-
-// Fast parse (DecTables::fast): the event's 64 bits are taken from the ring at
-// its start and every symbol is one table lookup -- no long codes, no top-up.
-__device__ __forceinline__ bool lane_ok_fast(const Lane& L) {
-  return ((uint32_t)(L.pos >> 5) - L.ws) + 3u <= RING_W;
-}
-// Fast-path stream parameter: (32 - table width) | 2 * table offset << 16, so a
-// lookup's byte address is ((v >> shift) << 17 + param) >> 16 (shifts use the
-// low 5 bits of their operand; bits 5..15 do not reach the address, and S.pp
-// keeps the symbol's event-word shift in bits 5..9: ev_shift).
-__device__ __forceinline__ uint32_t fast_param(uint32_t gp) {
-  return (32u - ((gp >> 16) & 31u)) | ((gp & 0xFFFFu) << 17);
-}
-__device__ __forceinline__ uint32_t fsym(unsigned long long& win, uint32_t& tot, const LutLds& S, uint32_t fp) {
-  const uint32_t v = (uint32_t)(win >> 32);
-  const uint32_t byte = (((v >> (fp & 31u)) << 17) + fp) >> 16;
-  const uint32_t e = *reinterpret_cast<const uint16_t*>(reinterpret_cast<const uint8_t*>(S.lut) + byte);
-  const uint32_t n = e & 31u;
-  win <<= n;
-  tot += n;
-  return e >> 5;
-}
-
-// Long code (longer than the LUT width): search of the canonical order.
-__device__ __forceinline__ uint32_t long_code(const LutLds& S, uint32_t v, uint32_t gp, uint32_t gsz) {
-  const uint32_t x = v >> (32u - (gp >> 24));
-  int lo = (int)(gsz & 0xFFFFu), hi = lo + (int)(gsz >> 16) - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (S.lo[mid] <= x) hi = mid;
-    else lo = mid + 1;
-  }
-  return ((uint32_t)S.sym[lo] << 5) | (uint32_t)S.len[lo];
-}
-
-// One symbol of stream st (gp: S.gp[st], passed in for the prefix stream,
-// which a lane reads at every event).
-__device__ __forceinline__ uint32_t dsym_gp(Lane& L, const uint32_t* my, const LutLds& S, uint32_t st,
-                                            uint32_t gp) {
-  const uint32_t v = (uint32_t)(L.win >> 32);
-  uint32_t e = S.lut[(gp & 0xFFFFu) + (v >> (32u - ((gp >> 16) & 31u)))];
-  if ((e & 31u) == 0) e = long_code(S, v, gp, S.gs[st]);
-  const uint32_t n = e & 31u;
-  L.pos += n;
-  L.win <<= n;
-  L.avail -= n;
-  // top up to >= 32 bits (branch-free; lane_ok() guarantees the word exists)
-  const uint32_t w = my[min(L.rp, RING_W - 1u)];
-  const bool need = L.avail < 32u;
-  L.win |= need ? ((unsigned long long)w << (32u - L.avail)) : 0ull;
-  L.rp += need ? 1u : 0u;
-  L.avail += need ? 32u : 0u;
-  return e >> 5;
-}
-// One pixel event at a prefix position: the prefix and, for a coded pixel, its
-// payload symbols.  Returns the prefix; s0..s3 receive the payload.
-// The frame's stream parameters (S.gp) held in scalar registers: a payload
-// symbol's parameters are selected by the prefix instead of read from LDS, so
-// its LUT lookup does not wait on a dependent LDS read.
-struct StreamParams {
-  uint32_t g[N_STREAMS];
-  __device__ __forceinline__ void load(const LutLds& S) {
-#pragma unroll
-    for (int i = 0; i < N_STREAMS; ++i) g[i] = __builtin_amdgcn_readfirstlane(S.gp[i]);
-  }
-};
-__device__ __forceinline__ uint32_t pixel_event(Lane& L, const uint32_t* my, const LutLds& S,
-                                                const StreamParams& G, uint32_t& s0, uint32_t& s1, uint32_t& s2,
-                                                uint32_t& s3) {
-  const uint32_t pfx = dsym_gp(L, my, S, PFX_STREAM, G.g[PFX_STREAM]);
-  if (pfx < (uint32_t)P_RUN1) {
-    const bool rgb = pfx == (uint32_t)P_RGB, lu = pfx == (uint32_t)P_LUMA, l2 = pfx == (uint32_t)P_LUMA2;
-    const uint32_t gp0 = pfx == (uint32_t)P_BACK_REF ? G.g[S_BACK_REF] : rgb ? G.g[S_RGB] : lu ? G.g[S_LUMA_REF]
-                       : l2 ? G.g[S_LUMA2_BASE] : G.g[S_SMALL_DIFF];
-    s0 = dsym_gp(L, my, S, pay_stream(pfx, 0), gp0);
-    if (rgb || lu || l2) {
-      s1 = dsym_gp(L, my, S, pay_stream(pfx, 1), rgb ? G.g[S_RGB] : lu ? G.g[S_LUMA_BASE] : G.g[S_LUMA2_R]);
-      s2 = dsym_gp(L, my, S, pay_stream(pfx, 2), rgb ? G.g[S_RGB] : lu ? G.g[S_LUMA_OTHER] : G.g[S_LUMA2_B]);
-      if (lu) s3 = dsym_gp(L, my, S, S_LUMA_OTHER, G.g[S_LUMA_OTHER]);
-    }
-  }
-  return pfx;
-}
-
-// pixel_event on the fast path: one 64-bit window per event (DecTables::fast
-// bounds every event by 64 bits), no per-symbol refill.
-__device__ __forceinline__ uint32_t pixel_event_fast(Lane& L, const uint32_t* my, const LutLds& S,
-                                                     const StreamParams& G, uint32_t& s0, uint32_t& s1,
-                                                     uint32_t& s2, uint32_t& s3) {
-  const uint32_t o = (uint32_t)(L.pos >> 5) - L.ws;
-  const uint32_t sh = (uint32_t)L.pos & 31u;
-  const uint32_t w0 = my[o], w1 = my[o + 1], w2 = my[o + 2];
-  unsigned long long win = ((((unsigned long long)w0 << 32) | w1) << sh) | (((unsigned long long)w2 << sh) >> 32);
-  uint32_t tot = 0;
-  const uint32_t pfx = fsym(win, tot, S, G.g[PFX_STREAM]);
-  if (pfx < (uint32_t)P_RUN1) {
-    const bool rgb = pfx == (uint32_t)P_RGB, lu = pfx == (uint32_t)P_LUMA, l2 = pfx == (uint32_t)P_LUMA2;
-    // the mode's payload parameters in one LDS read (selecting them from
-    // scalar registers by prefix took a move and a select per candidate)
-    const uint4 pp = S.pp[pfx];
-    s0 = fsym(win, tot, S, pp.x);
-    if (rgb || lu || l2) {
-      s1 = fsym(win, tot, S, pp.y);
-      s2 = fsym(win, tot, S, pp.z);
-      if (lu) s3 = fsym(win, tot, S, pp.w);
-    }
-  }
-  L.pos += tot;
-  return pfx;
-}
-
-// pixel_event_fast at ring word o, bit sh of it (dec_sync's relative-position
-// loop); returns the prefix and the event's bit count in tot.  EV: also the
-// coded pixel's event word (ev_pack), each symbol shifted to its place by the
-// shift its parameter word carries -- off the chain of dependent lookups.
-template <bool EV = false>
-__device__ __forceinline__ uint32_t pixel_event_fast_at(const uint32_t* my, const LutLds& S, uint32_t fp_pfx,
-                                                        uint32_t o, uint32_t sh, uint32_t& s0, uint32_t& s1,
-                                                        uint32_t& s2, uint32_t& s3, uint32_t& tot,
-                                                        uint32_t* evw = nullptr) {
-  const uint32_t w0 = my[o], w1 = my[o + 1], w2 = my[o + 2];
-  unsigned long long win = ((((unsigned long long)w0 << 32) | w1) << sh) | (((unsigned long long)w2 << sh) >> 32);
-  tot = 0;
-  const uint32_t pfx = fsym(win, tot, S, fp_pfx);
-  if (pfx < (uint32_t)P_RUN1) {
-    const bool rgb = pfx == (uint32_t)P_RGB, lu = pfx == (uint32_t)P_LUMA, l2 = pfx == (uint32_t)P_LUMA2;
-    const uint4 pp = S.pp[pfx];
-    s0 = fsym(win, tot, S, pp.x);
-    if constexpr (EV) *evw = (pfx << EV_PFX_SHIFT) | (s0 << ((pp.x >> 5) & 31u));
-    if (rgb || lu || l2) {
-      s1 = fsym(win, tot, S, pp.y);
-      s2 = fsym(win, tot, S, pp.z);
-      if constexpr (EV) *evw |= (s1 << ((pp.y >> 5) & 31u)) | (s2 << ((pp.z >> 5) & 31u));
-      if (lu) {
-        s3 = fsym(win, tot, S, pp.w);
-        if constexpr (EV) *evw |= s3 << ((pp.w >> 5) & 31u);
-      }
-    }
-  }
-  return pfx;
-}
-
-// Pixels a prefix accounts for: 1 for a coded pixel; a run digit d contributes
-// d << 3k (k = digits read before it; the reference's u8 shift counter `+= 3`
-// only matters mod 64) plus the run's first pixel on its first digit
-// (code.rs:660-680).  dk: digits read in the current run, kept in 1..64 once
-// nonzero.  Saturates at 2^32 - 1 (only garbage parses get there).
-__device__ __forceinline__ uint32_t pixel_count(uint32_t pfx, uint32_t& dk) {
-  if (pfx < (uint32_t)P_RUN1) { dk = 0; return 1u; }
-  const uint32_t sh = (3u * dk) & 63u;
-  const uint64_t c = ((uint64_t)(pfx - P_RUN1) << sh) + (dk == 0 ? 1u : 0u);
-  dk = dk >= 64u ? 1u : dk + 1u;
-  return c > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)c;
-}
-__device__ __forceinline__ uint32_t sat_add(uint32_t a, uint32_t b) { return a + b < a ? 0xFFFFFFFFu : a + b; }
-
-// Packed slice entry: bit position relative to the data start (40 bits), run
-// digits read so far (7).  Bits 56..63 of `last` hold the number of valid
-// checkpoints.  Checkpoint: position in the slice (16), run digits (7) << 20,
-// pixels since the slice entry << 32.
-constexpr unsigned long long PS_MASK = (1ull << 51) - 1ull;
-__device__ __forceinline__ unsigned long long ps_pack(unsigned long long rel, uint32_t dk) {
-  return rel | ((unsigned long long)dk << 44);
-}
-
-
 // Initial entry guesses: every slice starts at its first bit, at a prefix.
 __global__ __launch_bounds__(256) void dec_init_entries(DecArgs a) {
   const uint32_t f = blockIdx.y;
   for (uint32_t j = blockIdx.x * 256 + threadIdx.x; j < a.max_chunks; j += gridDim.x * 256) {
     const uint64_t i = (uint64_t)f * a.max_chunks + j;
     a.entry[i] = ps_pack((unsigned long long)j * a.chunk_bits, 0);
-    a.last[i] = ~0ull;
+    a.last[i] = LAST_NEVER;
   }
 }
 
-// Event layout: the slices of a frame in groups of 64 (one parse wave); a
-// group's events are interleaved in 16-byte quads, quad c of the group's slice
-// l at words (c * 64 + l) * 4.  The first pass keeps every active lane at the
-// same event index, so each of its 16-byte stores is one contiguous 1 KB per
-// wave (a per-slice layout made every store touch 64 lines: +10 % parse time).
-// Frames are padded to a multiple of 64 slices.
-__device__ __forceinline__ uint64_t ev_group(const DecArgs& a, uint32_t f, uint32_t j) {
-  return ((uint64_t)f * ((a.max_chunks + 63u) & ~63u) + (j & ~63u)) * a.ev_cap + (j & 63u) * 4u;
-}
-__device__ __forceinline__ uint32_t ev_word(uint32_t y) { return (y >> 2) * 256u + (y & 3u); }
-// the re-parses' head events: the same layout, hev_cap events per slice
-__device__ __forceinline__ uint64_t hev_group(const DecArgs& a, uint32_t f, uint32_t j) {
-  return ((uint64_t)f * ((a.max_chunks + 63u) & ~63u) + (j & ~63u)) * a.hev_cap + (j & 63u) * 4u;
-}
-
-// Who writes a slice's records once the parse is at its fixpoint (dec_heads,
-// dec_emit and dec_place all decide it here):
-//   SLICE_EMIT       dec_emit parses the whole slice: the final parse never met
-//                    the first pass, or the first pass's events overflowed
-//   SLICE_HEAD_EMIT  dec_emit parses the head up to the meeting checkpoint,
-//                    dec_place writes the first pass's events from there
-//   SLICE_PLACE      dec_place writes both: the head from the events the
-//                    latest re-parse kept (none when the first pass itself
-//                    started at the slice's final entry), then the first pass's
-// A kept head stands only for a consistent slice (parsed last from its present
-// entry) whose latest re-parse met the previous parse at `agree`, the latest
-// meeting point of all passes: a re-parse that met earlier has overwritten the
-// events between its meeting point and `agree`.
-constexpr uint32_t SLICE_EMIT = 0, SLICE_HEAD_EMIT = 1, SLICE_PLACE = 2;
-// hn: the head events dec_place walks (SLICE_PLACE), else 0.  (Every load is
-// issued before the first is used: dec_place's short waves wait on them.)
-__device__ __forceinline__ uint32_t slice_route(const DecArgs& a, uint64_t base, uint32_t j, uint32_t& ag,
-                                                uint32_t& nvalid, uint32_t& hn) {
-  const unsigned long long last = a.last[base + j];
-  ag = a.agree[base + j];
-  const uint32_t nev = a.ev_n[base + j];
-  unsigned long long e = 0;
-  uint32_t hev_n = EV_OVERFLOW, hev_ag = AGREE_NONE;
-  if (a.hev) {
-    e = j == 0 ? 0ull : a.entry[base + j];
-    hev_n = a.hev_n[base + j];
-    hev_ag = a.hev_ag[base + j];
-  }
-  nvalid = (uint32_t)(last >> 56);
-  hn = 0;
-  if (ag == AGREE_NONE || nev == EV_OVERFLOW || ag > nvalid) return SLICE_EMIT;
-  if (ag == 0u) return SLICE_PLACE;
-  if ((last & PS_MASK) != e || hev_n == EV_OVERFLOW || hev_ag != ag) return SLICE_HEAD_EMIT;
-  hn = hev_n;
-  return SLICE_PLACE;
-}
-
-// (The event word of a parsed pixel -- ev_pack -- is nice_dec_event.hpp's.)
 
 // ---------------------------------------------------------------------------
 // D1: sync iteration (Jacobi, in place).  Each lane parses its slice from the
@@ -742,51 +364,40 @@ __global__ __launch_bounds__(DEC_PARSE_THREADS) PARSE_ATTR void dec_sync(DecArgs
   const uint32_t f = blockIdx.x / a.chunk_blocks;
   const uint32_t jb = blockIdx.x % a.chunk_blocks;
   if (a.status[f] != 0) return;
-  const uint64_t len = a.stream_len[f];
-  const uint64_t D = a.data_start[f];
-  const uint32_t nc = n_chunks(len, D, a.chunk_bits);
+  ParseCtx C = parse_frame(a, f);
+  const uint64_t D = C.D, base = C.base;
+  const uint32_t nc = C.nc;
   if (jb * DEC_PARSE_THREADS >= nc) return;
   const uint32_t j = jb * DEC_PARSE_THREADS + threadIdx.x;
-  const uint64_t base = (uint64_t)f * a.max_chunks;
-  unsigned long long e = 0, last = ~0ull;
+  unsigned long long e = 0, last = LAST_NEVER;
   if (j < nc) {
-    e = j == 0 ? 0ull : a.entry[base + j];
+    e = slice_entry(a, base, j);
     last = a.last[base + j];
   }
-  const bool need = j < nc && (last == ~0ull || (last & PS_MASK) != e);
+  const bool need = j < nc && (last_never(last) || !last_from(last, e));
   if (!__syncthreads_or(need)) return;
   load_lut(S, reinterpret_cast<const DecTables*>(a.tables) + f);
   __syncthreads();
-  const uint32_t wave = threadIdx.x >> 6;
-  if (jb * DEC_PARSE_THREADS + wave * 64u >= nc) return;
-  StreamParams SP;
-  SP.load(S);
-  uint32_t* wring = ring + wave * 64u * RING_STRIDE;
-  const uint32_t* my = wring + (threadIdx.x & 63u) * RING_STRIDE;
-  const uint8_t* p = dec_stream_ptr(a, f);
-  const bool al16 = (reinterpret_cast<uintptr_t>(p) & 15u) == 0;
-  const bool check = last != ~0ull;
-  const uint32_t nvalid_old = (uint32_t)(last >> 56);
+  if (wave_idle(jb * DEC_PARSE_THREADS, nc)) return;
+  parse_lane(C, S, ring, a, f);
+  const bool check = !last_never(last);
+  const uint32_t nvalid_old = last_nck(last);
   const unsigned long long begin = D + (unsigned long long)j * a.chunk_bits;
   const unsigned long long end = begin + a.chunk_bits;
-  const unsigned long long hard = len * 8 + 64;
   const uint32_t N = a.W * a.H;
   unsigned long long* ck = a.ck + (uint64_t)f * a.n_ck * a.max_chunks + j;
   // first pass: keep the pixel events (16-byte stores of 4)
   const bool keep = a.ev != nullptr && !check;
   // (one pointer: a lane keeps the first pass's events or a re-parse's head, never both)
-  uint32_t* evp = check ? a.hev + hev_group(a, f, j) : a.ev + ev_group(a, f, j);
+  uint32_t* evp = check ? a.hev + ev_group(a, f, j, a.hev_cap) : a.ev + ev_group(a, f, j, a.ev_cap);
   uint32_t* evck = a.ev_ck + (uint64_t)f * a.n_ck * a.max_chunks + j;
   // re-parses: keep the head's events, from the entry to the checkpoint where
   // the parse meets the previous one (ne counts them, as the first pass's)
   const bool hkeep = a.hev != nullptr && check && need;
   bool hkept = false;   // (wave-uniform) the loop this wave took kept them
   uint32_t ne = 0, ev0 = 0, ev1 = 0, ev2 = 0;
-  Lane L;
-  L.pos = D + (e & ((1ull << 40) - 1));
-  L.rp = RING_W;   // empty: filled on the first step
-  L.ws = (uint32_t)(L.pos >> 5) - RING_W;   // (fast path) empty as well
-  uint32_t dk = (uint32_t)(e >> 44) & 127u;
+  uint32_t dk;
+  Lane L = lane_at(C, e, dk);
   uint32_t px = 0, k = 0;
   unsigned long long next_ck = begin + a.ck_bits;
   unsigned long long ck_old = (check && nvalid_old > 0) ? ck[0] : ~0ull;
@@ -801,40 +412,105 @@ __global__ __launch_bounds__(DEC_PARSE_THREADS) PARSE_ATTR void dec_sync(DecArgs
   constexpr bool tstat = false;
 #endif
   if (tstat) tw0 = __builtin_amdgcn_s_memtime();
-  // the event loop, instantiated for the fast and the general parse
-  auto parse = [&](auto fast_tag) {
-    constexpr bool FAST = decltype(fast_tag)::value;
-    if constexpr (FAST) {
-#pragma unroll
-      for (int i = 0; i < N_STREAMS; ++i) SP.g[i] = fast_param(SP.g[i]);
+  // At the first prefix at or past a checkpoint's bit (pos: bits into the
+  // slice): a re-parse that agrees with the previous parse stops here, else the
+  // checkpoint is written: true, and the caller moves on to the next one.
+  auto checkpoint = [&](uint32_t pos) __attribute__((always_inline)) -> bool {
+    const uint32_t cur = ck_key(pos, dk);
+    if (check && k < nvalid_old && ck_key_of(ck_old) == cur) {
+      synced = true;
+      active = false;
+      return false;
     }
-    for (;;) {
-      // at a prefix position: slice end, checkpoint, or one more pixel event
-      if (active && (L.pos >= end || L.pos >= hard || px > N)) active = false;
-      if (active && L.pos >= next_ck) {
-        const uint32_t cur = (uint32_t)(L.pos - begin) | (dk << 20);
-        if (check && k < nvalid_old && (uint32_t)ck_old == cur) {
-          synced = true;
-          active = false;
-        } else {
-          ck[(uint64_t)k * a.max_chunks] = cur | ((unsigned long long)px << 32);
-          if (keep) evck[(uint64_t)k * a.max_chunks] = ne;
-          ++k;
-          next_ck = k < a.n_ck ? next_ck + a.ck_bits : ~0ull;
-          ck_old = (check && k < nvalid_old) ? ck[(uint64_t)k * a.max_chunks] : ~0ull;
+    ck[(uint64_t)k * a.max_chunks] = ck_pack(cur, px);
+    if (keep) evck[(uint64_t)k * a.max_chunks] = ne;
+    ++k;
+    ck_old = (check && k < nvalid_old) ? ck[(uint64_t)k * a.max_chunks] : ~0ull;
+    return true;
+  };
+  // Fast parse in 32-bit positions (RelCursor; the checkpoints too): the loop
+  // is unrolled four times so a kept event goes straight into its slot of the
+  // 16-byte quad (every active lane of the first pass is at the same event
+  // index) instead of through a shift register.  A wave with a lane more than
+  // 2^30 bits away takes the general symbol-by-symbol parse, which reads any
+  // tables.
+  const bool fast = parse_fast(a, f);
+  const unsigned long long B = rel_base(active, L.pos, begin);
+  if (fast && rel_fits(active, L.pos, B, end)) {
+    RelCursor R;
+    R.init(C, B, L.pos, end, active);
+    const uint32_t b31 = (uint32_t)(begin - B);   // the slice's first bit
+    uint32_t nck = b31 + a.ck_bits;   // next checkpoint (relative)
+    uint32_t q0 = 0, q1 = 0, q2 = 0, q3 = 0;   // the current quad of kept events
+    // keep_tag: 0 keeps nothing, 1 the first pass (events into ev), 2 a re-parse
+    // (head events into hev)
+    auto step = [&](auto slot_tag, auto keep_tag) -> bool {
+      constexpr int SLOT = decltype(slot_tag)::value;
+      constexpr bool KEEP = decltype(keep_tag)::value == 1;
+      constexpr bool KEPT = decltype(keep_tag)::value != 0;
+      if (active && (R.r >= R.rlim || px > N)) active = false;
+      if (active && R.r >= nck && checkpoint(R.r - b31)) nck = k < a.n_ck ? nck + a.ck_bits : 0xFFFFFFFFu;
+      // (the passes that keep events test for the wave's end once per quad: a
+      // step after every lane stopped only evaluates masked conditions)
+      if ((!KEPT || SLOT == 0) && !__any(active)) return false;
+      R.refill(C, active);
+      if (active) {
+        uint32_t s0 = 0, s1 = 0, s2 = 0, s3 = 0, evw = 0;
+        const uint32_t pfx = R.event<KEPT>(C, S, s0, s1, s2, s3, &evw);
+        const uint32_t c = pixel_count(pfx, dk);
+        px = sat_add(px, c);
+        // (every re-parsing lane of the wave starts at event 0 in the same step, as the first pass's)
+        if (KEPT && (KEEP ? keep : hkeep)) {
+          const uint32_t ev = pfx < (uint32_t)P_RUN1 ? evw : EV_RUN | min(c, EV_RUN - 1u);
+          if constexpr (SLOT == 0) q0 = ev;
+          if constexpr (SLOT == 1) q1 = ev;
+          if constexpr (SLOT == 2) q2 = ev;
+          if constexpr (SLOT == 3) {
+            q3 = ev;
+            if (ne < (KEEP ? a.ev_cap : a.hev_cap))
+              *reinterpret_cast<uint4*>(evp + ev_word(ne - 3u)) = make_uint4(q0, q1, q2, q3);
+          }
+          ++ne;
         }
       }
-      if (!__any(active)) break;
-      if (__any(active && !(FAST ? lane_ok_fast(L) : lane_ok(L)))) {
-        const unsigned long long tf = tstat ? __builtin_amdgcn_s_memtime() : 0;
-        ring_fill<FAST>(wring, p, len, al16, L);
-        if (tstat) { tfill += __builtin_amdgcn_s_memtime() - tf; ++nfill; }
+      return true;
+    };
+    auto quads = [&](auto keep_tag) __attribute__((always_inline)) {   // unrolled by the quad
+      for (;;) {
+        if (!step(std::integral_constant<int, 0>{}, keep_tag)) break;
+        if (!step(std::integral_constant<int, 1>{}, keep_tag)) break;
+        if (!step(std::integral_constant<int, 2>{}, keep_tag)) break;
+        if (!step(std::integral_constant<int, 3>{}, keep_tag)) break;
       }
+    };
+    if (__any(keep && active)) {   // the first pass
+      quads(std::integral_constant<int, 1>{});
+    } else if (__any(hkeep && active)) {   // a re-parse keeping its head: the same way
+      hkept = true;
+      quads(std::integral_constant<int, 2>{});
+    } else {   // a re-parse that keeps nothing (a smaller loop: these launches are short)
+      while (step(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{})) {
+      }
+    }
+    L.pos = B + R.r;
+    // the tail below stores the last (ne & 3) events from ev0..ev2 (newest last)
+    const uint32_t sl = ne & 3u;
+    ev0 = q0;
+    ev1 = sl == 3u ? q1 : q0;
+    ev2 = sl == 3u ? q2 : sl == 2u ? q1 : q0;
+  } else {   // (any tables; the general parse)
+    for (;;) {
+      // at a prefix position: slice end, checkpoint, or one more pixel event
+      if (active && (L.pos >= end || L.pos >= C.hard || px > N)) active = false;
+      if (active && L.pos >= next_ck && checkpoint((uint32_t)(L.pos - begin)))
+        next_ck = k < a.n_ck ? next_ck + a.ck_bits : ~0ull;
+      if (!__any(active)) break;
+      const unsigned long long tf = tstat ? __builtin_amdgcn_s_memtime() : 0;
+      if (wave_refill(C, L, active) && tstat) { tfill += __builtin_amdgcn_s_memtime() - tf; ++nfill; }
       if (tstat) { ++nit; nact += active ? 1u : 0u; }
       if (active) {
         uint32_t s0 = 0, s1 = 0, s2 = 0, s3 = 0;
-        const uint32_t pfx = FAST ? pixel_event_fast(L, my, S, SP, s0, s1, s2, s3)
-                                  : pixel_event(L, my, S, SP, s0, s1, s2, s3);
+        const uint32_t pfx = pixel_event(L, C.my, S, C.SP, s0, s1, s2, s3);
         const uint32_t c = pixel_count(pfx, dk);
         px = sat_add(px, c);
         if (keep || hkeep) {
@@ -849,137 +525,6 @@ __global__ __launch_bounds__(DEC_PARSE_THREADS) PARSE_ATTR void dec_sync(DecArgs
         }
       }
     }
-  };
-  const bool fast = !a.parse_slow && reinterpret_cast<const DecTables*>(a.tables)[f].fast;
-  // Fast parse in 32-bit positions (round 6): r = bits past the word holding
-  // the slice's first bit, so the slice end, stream end, checkpoints and ring
-  // offsets are 32-bit compares and adds instead of 64-bit ones; the loop is
-  // unrolled four times so a kept event goes straight into its slot of the
-  // 16-byte quad (every active lane of the first pass is at the same event
-  // index) instead of through a shift register; a run digit's pixel count is a
-  // 32-bit shift below 2^30.  r counts from the word holding the slice's first
-  // bit or, when the entry lies before the slice (the previous slice's parse
-  // stopped at px > N: speculative garbage), from the entry's word; a wave
-  // with a lane more than 2^30 bits away takes the general symbol-by-symbol
-  // parse, which reads any tables.
-  const unsigned long long B = (active && L.pos < begin ? L.pos : begin) & ~31ull;
-  if (fast && __all(!active || (L.pos >= B && begin + a.chunk_bits - B < (1ull << 30)))) {
-    // the prefix stream's fast parameter (the payload streams' come from S.pp;
-    // a converted copy of SP here put SP in scratch for the general loop)
-    const uint32_t fp_pfx = fast_param(SP.g[PFX_STREAM]);
-    const uint32_t bwl = (uint32_t)(B >> 5);
-    const uint32_t b31 = (uint32_t)(begin - B);   // the slice's first bit
-    const uint32_t rhard = hard > B ? (uint32_t)min(hard - B, (unsigned long long)0xFFFFFFFFu) : 0u;
-    const uint32_t rlim = min(b31 + a.chunk_bits, rhard);
-    uint32_t r = active ? (uint32_t)(L.pos - B) : 0u;
-    uint32_t wsr = 0;    // ring start word (relative)
-    uint32_t rfill = 0;  // refill once r reaches this (ring empty: at once)
-    uint32_t nck = b31 + a.ck_bits;   // next checkpoint (relative)
-    uint32_t q0 = 0, q1 = 0, q2 = 0, q3 = 0;   // the current quad of kept events
-    // keep_tag: 0 keeps nothing, 1 the first pass (events into ev), 2 a re-parse
-    // (head events into hev)
-    auto step = [&](auto slot_tag, auto keep_tag) -> bool {
-      constexpr int SLOT = decltype(slot_tag)::value;
-      constexpr bool KEEP = decltype(keep_tag)::value == 1;
-      constexpr bool HEAD = decltype(keep_tag)::value == 2;
-      if (active && (r >= rlim || px > N)) active = false;
-      if (active && r >= nck) {
-        const uint32_t cur = (r - b31) | (dk << 20);
-        if (check && k < nvalid_old && (uint32_t)ck_old == cur) {
-          synced = true;
-          active = false;
-        } else {
-          ck[(uint64_t)k * a.max_chunks] = cur | ((unsigned long long)px << 32);
-          if (keep) evck[(uint64_t)k * a.max_chunks] = ne;
-          ++k;
-          nck = k < a.n_ck ? nck + a.ck_bits : 0xFFFFFFFFu;
-          ck_old = (check && k < nvalid_old) ? ck[(uint64_t)k * a.max_chunks] : ~0ull;
-        }
-      }
-      // (the passes that keep events test for the wave's end once per quad: a
-      // step after every lane stopped only evaluates masked conditions)
-      if ((!(KEEP || HEAD) || SLOT == 0) && !__any(active)) return false;
-      if (__any(active && r >= rfill)) {   // the next event's 3 words would pass the ring's end
-        const uint32_t wsa = (bwl + (r >> 5)) & ~3u;
-        ring_fill_ws(wring, p, len, al16, wsa);
-        wsr = wsa - bwl;
-        rfill = (wsr + RING_W - 2u) << 5;
-      }
-      if (active) {
-        uint32_t s0 = 0, s1 = 0, s2 = 0, s3 = 0, tot, evw = 0;
-        const uint32_t pfx = pixel_event_fast_at<KEEP || HEAD>(my, S, fp_pfx, (r >> 5) - wsr, r & 31u, s0, s1, s2,
-                                                               s3, tot, &evw);
-        r += tot;
-        uint32_t c;
-        if (pfx < (uint32_t)P_RUN1) {
-          dk = 0;
-          c = 1u;
-        } else {
-          const uint32_t sh = (3u * dk) & 63u, d = pfx - (uint32_t)P_RUN1;
-          if (sh < 30u) {
-            c = (d << sh) + (dk == 0 ? 1u : 0u);
-          } else {   // (exact, saturating: only a run of >= 2^30 pixels gets here)
-            const uint64_t c64 = (uint64_t)d << sh;
-            c = c64 > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)c64;
-          }
-          dk = dk >= 64u ? 1u : dk + 1u;
-        }
-        px = sat_add(px, c);
-        if (KEEP && keep) {
-          const uint32_t ev = pfx < (uint32_t)P_RUN1 ? evw : EV_RUN | min(c, EV_RUN - 1u);
-          if constexpr (SLOT == 0) q0 = ev;
-          if constexpr (SLOT == 1) q1 = ev;
-          if constexpr (SLOT == 2) q2 = ev;
-          if constexpr (SLOT == 3) {
-            q3 = ev;
-            if (ne < a.ev_cap) *reinterpret_cast<uint4*>(evp + ev_word(ne - 3u)) = make_uint4(q0, q1, q2, q3);
-          }
-          ++ne;
-        }
-        if (HEAD && hkeep) {   // (every re-parsing lane of the wave starts at event 0 in the same step)
-          const uint32_t ev = pfx < (uint32_t)P_RUN1 ? evw : EV_RUN | min(c, EV_RUN - 1u);
-          if constexpr (SLOT == 0) q0 = ev;
-          if constexpr (SLOT == 1) q1 = ev;
-          if constexpr (SLOT == 2) q2 = ev;
-          if constexpr (SLOT == 3) {
-            q3 = ev;
-            if (ne < a.hev_cap) *reinterpret_cast<uint4*>(evp + ev_word(ne - 3u)) = make_uint4(q0, q1, q2, q3);
-          }
-          ++ne;
-        }
-      }
-      return true;
-    };
-    using keep_none = std::integral_constant<int, 0>;
-    using keep_first = std::integral_constant<int, 1>;
-    using keep_head = std::integral_constant<int, 2>;
-    if (__any(keep && active)) {   // the first pass: unrolled by the quad
-      for (;;) {
-        if (!step(std::integral_constant<int, 0>{}, keep_first{})) break;
-        if (!step(std::integral_constant<int, 1>{}, keep_first{})) break;
-        if (!step(std::integral_constant<int, 2>{}, keep_first{})) break;
-        if (!step(std::integral_constant<int, 3>{}, keep_first{})) break;
-      }
-    } else if (__any(hkeep && active)) {   // a re-parse keeping its head: the same way
-      hkept = true;
-      for (;;) {
-        if (!step(std::integral_constant<int, 0>{}, keep_head{})) break;
-        if (!step(std::integral_constant<int, 1>{}, keep_head{})) break;
-        if (!step(std::integral_constant<int, 2>{}, keep_head{})) break;
-        if (!step(std::integral_constant<int, 3>{}, keep_head{})) break;
-      }
-    } else {   // a re-parse that keeps nothing (a smaller loop: these launches are short)
-      while (step(std::integral_constant<int, 0>{}, keep_none{})) {
-      }
-    }
-    L.pos = B + r;
-    // the tail below stores the last (ne & 3) events from ev0..ev2 (newest last)
-    const uint32_t sl = ne & 3u;
-    ev0 = q0;
-    ev1 = sl == 3u ? q1 : q0;
-    ev2 = sl == 3u ? q2 : sl == 2u ? q1 : q0;
-  } else {
-    parse(std::false_type{});   // (any tables; the general parse)
     hkept = true;
   }
   if (tstat) {
@@ -1020,17 +565,17 @@ __global__ __launch_bounds__(DEC_PARSE_THREADS) PARSE_ATTR void dec_sync(DecArgs
   }
   if (synced) {
     // from checkpoint k on this parse equals the previous one, shifted by delta pixels
-    const uint32_t delta = px - (uint32_t)(ck_old >> 32);
+    const uint32_t delta = px - ck_px(ck_old);
     a.chunk_px[base + j] = a.chunk_px[base + j] + (uint64_t)(int64_t)(int32_t)delta;
     for (uint32_t kk = k; kk < nvalid_old; ++kk) {
       unsigned long long& c = ck[(uint64_t)kk * a.max_chunks];
-      c = (c & 0xFFFFFFFFull) | ((unsigned long long)((uint32_t)(c >> 32) + delta) << 32);
+      c = ck_add_px(c, delta);
     }
-    a.last[base + j] = e | ((unsigned long long)nvalid_old << 56);
+    a.last[base + j] = last_pack(e, nvalid_old);
     return;
   }
   a.chunk_px[base + j] = px;
-  a.last[base + j] = e | ((unsigned long long)k << 56);
+  a.last[base + j] = last_pack(e, k);
   if (j + 1 < nc) {
     const unsigned long long x = ps_pack(L.pos - D, dk);
     if (a.entry[base + j + 1] != x) {
@@ -1075,35 +620,26 @@ __global__ __launch_bounds__(SETTLE_THREADS) void dec_sync_settle(DecArgs a, con
   __shared__ unsigned long long xs[SETTLE_THREADS];   // each range's exit in the current round
   const uint32_t f = blockIdx.x;
   if (*last_changed == 0 || fchanged[f] == 0 || a.status[f] != 0) return;   // block-uniform
-  const uint64_t len = a.stream_len[f];
-  const uint64_t D = a.data_start[f];
-  const uint32_t nc = min(n_chunks(len, D, a.chunk_bits), a.max_chunks);
+  ParseCtx C = parse_frame(a, f);
+  const uint64_t D = C.D, base = C.base;
+  const uint32_t nc = min(C.nc, a.max_chunks);
   if (nc < 2) return;
   load_lut(S, reinterpret_cast<const DecTables*>(a.tables) + f);
   __syncthreads();
-  StreamParams SP;
-  SP.load(S);
+  parse_lane(C, S, ring, a, f);   // (every wave stays: the rounds' barriers)
   const uint32_t t = threadIdx.x;
-  uint32_t* wring = ring + (t & ~63u) * RING_STRIDE;
-  const uint32_t* my = ring + t * RING_STRIDE;
-  const uint8_t* p = dec_stream_ptr(a, f);
-  const bool al16 = (reinterpret_cast<uintptr_t>(p) & 15u) == 0;
-  const uint64_t base = (uint64_t)f * a.max_chunks;
   const uint32_t N = a.W * a.H;
-  const unsigned long long hard = len * 8 + 64;
   const uint32_t per = (nc + SETTLE_THREADS - 1) / SETTLE_THREADS;
   const uint32_t lo = min(t * per, nc), hi = min(lo + per, nc);   // nonempty ranges: lanes 0..k, contiguous
-  unsigned long long start = lo == 0 ? 0ull : a.entry[base + lo];
+  unsigned long long start = slice_entry(a, base, lo);
   unsigned long long xprev = 0;   // the lane's exit of the previous round
   bool walk = lo < hi;
-  const bool fast = !a.parse_slow && reinterpret_cast<const DecTables*>(a.tables)[f].fast;
+  const bool fast = parse_fast(a, f);
   for (uint32_t round = 0;; ++round) {
     // ---- one round: the lanes with `walk` parse their range from `start`
-    Lane L;
-    L.pos = D;
-    L.rp = RING_W;
-    L.ws = (uint32_t)(D >> 5) - RING_W;
-    uint32_t j = lo, dk = 0, px = 0;
+    uint32_t dk;
+    Lane L = lane_at(C, 0ull, dk);
+    uint32_t j = lo, px = 0;
     unsigned long long end = 0, xout = xprev;
     bool refill = true;
     // position the lane at slice j with entry x, after the slices it may skip;
@@ -1111,10 +647,10 @@ __global__ __launch_bounds__(SETTLE_THREADS) void dec_sync_settle(DecArgs a, con
     auto advance = [&](unsigned long long x) -> bool {
       for (;;) {
         if (j >= hi) { xout = x; return false; }
-        const unsigned long long cur = j == 0 ? 0ull : a.entry[base + j];
+        const unsigned long long cur = slice_entry(a, base, j);
         if (round == 0) {
           const unsigned long long lj = a.last[base + j];
-          if (x == cur && lj != ~0ull && (lj & PS_MASK) == cur) {   // consistent: its exit is the next entry
+          if (x == cur && !last_never(lj) && last_from(lj, cur)) {   // consistent: its exit is the next entry
             x = j + 1 < nc ? a.entry[base + j + 1] : 0ull;
             ++j;
             continue;
@@ -1124,8 +660,8 @@ __global__ __launch_bounds__(SETTLE_THREADS) void dec_sync_settle(DecArgs a, con
           return false;
         }
         if (j > lo) a.entry[base + j] = x;
-        L.pos = D + (x & ((1ull << 40) - 1));
-        dk = (uint32_t)(x >> 44) & 127u;
+        L.pos = D + ps_pos(x);
+        dk = ps_dk(x);
         px = 0;
         end = D + (unsigned long long)(j + 1) * a.chunk_bits;
         refill = true;
@@ -1135,26 +671,23 @@ __global__ __launch_bounds__(SETTLE_THREADS) void dec_sync_settle(DecArgs a, con
     bool active = walk && advance(start);
     auto parse = [&](auto fast_tag) {
       constexpr bool FAST = decltype(fast_tag)::value;
-      StreamParams G = SP;
+      StreamParams G = C.SP;
       if constexpr (FAST) {
 #pragma unroll
         for (int i = 0; i < N_STREAMS; ++i) G.g[i] = fast_param(G.g[i]);
       }
       for (;;) {
         // at a prefix position: the slice's end (same stop rule as dec_sync), or one more pixel event
-        if (active && (L.pos >= end || L.pos >= hard || px > N)) {
+        if (active && (L.pos >= end || L.pos >= C.hard || px > N)) {
           ++j;
           active = advance(ps_pack(L.pos - D, dk));
         }
         if (!__any(active)) break;
-        if (__any(active && (refill || !(FAST ? lane_ok_fast(L) : lane_ok(L))))) {
-          ring_fill<FAST>(wring, p, len, al16, L);
-          refill = false;
-        }
+        if (wave_refill<FAST>(C, L, active, refill)) refill = false;
         if (active) {
           uint32_t s0 = 0, s1 = 0, s2 = 0, s3 = 0;
-          const uint32_t pfx = FAST ? pixel_event_fast(L, my, S, G, s0, s1, s2, s3)
-                                    : pixel_event(L, my, S, G, s0, s1, s2, s3);
+          const uint32_t pfx = FAST ? pixel_event_fast(L, C.my, S, G, s0, s1, s2, s3)
+                                    : pixel_event(L, C.my, S, G, s0, s1, s2, s3);
           px = sat_add(px, pixel_count(pfx, dk));
         }
       }
@@ -1258,44 +791,35 @@ __global__ __launch_bounds__(DEC_PARSE_THREADS) void dec_strict_refill(DecArgs a
 #pragma unroll
   for (int st = 0; st < N_STREAMS; ++st) mx = max(mx, (uint32_t)T->max_aob[st]);
   if (mx <= 25u) return;   // (P & 7) + M <= 32 for every read
-  const uint64_t len = a.stream_len[f];
-  const uint64_t D = a.data_start[f];
-  const uint32_t nc = n_chunks(len, D, a.chunk_bits);
+  ParseCtx C = parse_frame(a, f);
+  const uint64_t D = C.D, base = C.base;
+  const uint32_t nc = C.nc;
   if (jb * DEC_PARSE_THREADS >= nc) return;
   load_lut(S, T);
   __syncthreads();
-  const uint32_t wave = threadIdx.x >> 6;
-  if (jb * DEC_PARSE_THREADS + wave * 64u >= nc) return;
-  StreamParams SP;
-  SP.load(S);
+  if (wave_idle(jb * DEC_PARSE_THREADS, nc)) return;
+  parse_lane(C, S, ring, a, f);
+  const StreamParams SP = C.SP;  // a copy of its own: rd indexes it dynamically (the kernel's 48 bytes of scratch)
   const uint32_t j = jb * DEC_PARSE_THREADS + threadIdx.x;
   const uint32_t j0 = j > 0 ? j - 1u : 0u;
-  uint32_t* wring = ring + wave * 64u * RING_STRIDE;
-  const uint32_t* my = wring + (threadIdx.x & 63u) * RING_STRIDE;
-  const uint8_t* p = dec_stream_ptr(a, f);
-  const bool al16 = (reinterpret_cast<uintptr_t>(p) & 15u) == 0;
-  const uint64_t base = (uint64_t)f * a.max_chunks;
   const unsigned long long N = (unsigned long long)a.W * a.H;
   const unsigned long long begin = D + (unsigned long long)j * a.chunk_bits;
   const unsigned long long end = begin + a.chunk_bits;
-  const unsigned long long hard = len * 8 + 64;
   bool active = j < nc;
   unsigned long long e = 0, q = 0;
   if (active) {
-    e = j0 == 0 ? 0ull : a.entry[base + j0];
+    e = slice_entry(a, base, j0);
     q = a.chunk_start[base + j0];
   }
-  Lane L;
-  L.pos = D + (e & ((1ull << 40) - 1));
-  L.rp = RING_W;
-  uint32_t dk = (uint32_t)(e >> 44) & 127u;
+  uint32_t dk;
+  Lane L = lane_at(C, e, dk);
   bool closed = q == N;
   unsigned long long nb8 = D;   // 8 x bytes the reference has read (D = 770 bytes)
   bool hang = false;
   for (;;) {
-    if (active && (L.pos >= end || L.pos >= hard || q > N)) active = false;
+    if (active && (L.pos >= end || L.pos >= C.hard || q > N)) active = false;
     if (!__any(active)) break;
-    if (__any(active && !lane_ok(L))) ring_fill<false>(wring, p, len, al16, L);
+    (void)wave_refill(C, L, active);
     if (!active) continue;
     const bool chk = L.pos >= begin;   // an event of slice j (not of slice j - 1)
     // one read of stream st at L.pos, then the symbol
@@ -1305,7 +829,7 @@ __global__ __launch_bounds__(DEC_PARSE_THREADS) void dec_strict_refill(DecArgs a
         hang = hang || (chk && (uint32_t)(L.pos & 7u) + M > 32u);
         nb8 = (L.pos + M + 7u) & ~7ull;
       }
-      return dsym_gp(L, my, S, st, gp);
+      return dsym_gp(L, C.my, S, st, gp);
     };
     const bool at_n = q == N && (dk == 0 || closed);
     const uint32_t pfx = rd(PFX_STREAM);
@@ -1396,28 +920,20 @@ __global__ __launch_bounds__(DEC_PARSE_THREADS) PARSE_ATTR void dec_emit(DecArgs
   const uint32_t f = blockIdx.x / a.emit_blocks;
   const uint32_t vb = blockIdx.x % a.emit_blocks;
   if (a.status[f] != 0) return;
-  const uint64_t len = a.stream_len[f];
-  const uint64_t D = a.data_start[f];
-  const uint32_t nc = n_chunks(len, D, a.chunk_bits);
+  ParseCtx C = parse_frame(a, f);
+  const uint64_t D = C.D, base = C.base;
   const uint32_t subs = a.chunk_bits / DEC_EMIT_BITS;
   // with first-pass events kept, only the listed head sub-slices (dec_heads)
-  const uint32_t nv = a.head_items ? a.head_count[f] : nc * subs;
+  const uint32_t nv = a.head_items ? a.head_count[f] : C.nc * subs;
   if (vb * DEC_PARSE_THREADS >= nv) return;
   load_lut(S, reinterpret_cast<const DecTables*>(a.tables) + f);
   __syncthreads();
-  const uint32_t wave = threadIdx.x >> 6;
-  if (vb * DEC_PARSE_THREADS + wave * 64u >= nv) return;
-  StreamParams SP;
-  SP.load(S);
+  if (wave_idle(vb * DEC_PARSE_THREADS, nv)) return;
+  parse_lane(C, S, ring, a, f);
   const uint32_t v = vb * DEC_PARSE_THREADS + threadIdx.x;
   const uint32_t item = !a.head_items ? v
                       : v < nv ? a.head_items[(uint64_t)f * a.max_chunks * subs + v] : 0u;
   const uint32_t j = item / subs, sub = item - j * subs;
-  uint32_t* wring = ring + wave * 64u * RING_STRIDE;
-  const uint32_t* my = wring + (threadIdx.x & 63u) * RING_STRIDE;
-  const uint8_t* p = dec_stream_ptr(a, f);
-  const bool al16 = (reinterpret_cast<uintptr_t>(p) & 15u) == 0;
-  const uint64_t base = (uint64_t)f * a.max_chunks;
   const uint32_t N = a.W * a.H;
   const unsigned long long begin = D + (unsigned long long)j * a.chunk_bits;
   unsigned long long q64 = 0, e = 0;
@@ -1425,23 +941,23 @@ __global__ __launch_bounds__(DEC_PARSE_THREADS) PARSE_ATTR void dec_emit(DecArgs
   bool active = v < nv;
   if (active) {
     q64 = a.chunk_start[base + j];   // pixels accounted before this slice
-    const uint32_t nvalid = (uint32_t)(a.last[base + j] >> 56);
+    const uint32_t nvalid = last_nck(a.last[base + j]);
     const unsigned long long* ck = a.ck + (uint64_t)f * a.n_ck * a.max_chunks + j;
     const uint32_t step = DEC_EMIT_BITS / a.ck_bits;
     if (sub == 0) {
-      e = j == 0 ? 0ull : a.entry[base + j];
+      e = slice_entry(a, base, j);
     } else {
       const uint32_t c = sub * step - 1;
       if (c < nvalid) {
         const unsigned long long x = ck[(uint64_t)c * a.max_chunks];
-        e = ((begin - D) + (x & 0xFFFFu)) | ((unsigned long long)((x >> 20) & 127u) << 44);
-        q64 += x >> 32;
+        e = ps_pack((begin - D) + ck_pos(x), ck_dk(x));
+        q64 += ck_px(x);
       } else {
         active = false;               // the slice's parse ended before this sub-slice
       }
     }
     const uint32_t c1 = (sub + 1) * step - 1;
-    if (sub + 1 < subs && c1 < nvalid) end = begin + (ck[(uint64_t)c1 * a.max_chunks] & 0xFFFFu);
+    if (sub + 1 < subs && c1 < nvalid) end = begin + ck_pos(ck[(uint64_t)c1 * a.max_chunks]);
     if (q64 > N) active = false;      // past the image: tail bytes
     if (a.ev) {
       // dec_place writes the slice from where the final parse meets the first
@@ -1451,7 +967,7 @@ __global__ __launch_bounds__(DEC_PARSE_THREADS) PARSE_ATTR void dec_emit(DecArgs
       const uint32_t route = slice_route(a, base, j, ag, nv2, hn);
       if (route == SLICE_PLACE) active = false;
       if (route == SLICE_HEAD_EMIT) {
-        const unsigned long long stop = begin + (ck[(uint64_t)(ag - 1u) * a.max_chunks] & 0xFFFFu);
+        const unsigned long long stop = begin + ck_pos(ck[(uint64_t)(ag - 1u) * a.max_chunks]);
         if (stop < end) end = stop;
         if (sub * step >= ag) active = false;   // starts at or past the meeting point
       }
@@ -1459,14 +975,10 @@ __global__ __launch_bounds__(DEC_PARSE_THREADS) PARSE_ATTR void dec_emit(DecArgs
   }
   uint32_t q = (uint32_t)(q64 > N ? N : q64);
   const uint32_t q0 = q;
-  const unsigned long long hard = len * 8 + 64;
   uint32_t* rec = a.recs + (uint64_t)f * a.rec_stride;
   const bool strict = (a.flags & NICE_DEC_STRICT_REFERENCE) != 0;
-  Lane L;
-  L.pos = D + (e & ((1ull << 40) - 1));
-  L.rp = RING_W;
-  L.ws = (uint32_t)(L.pos >> 5) - RING_W;   // (fast parse) empty as well
-  uint32_t dk = (uint32_t)(e >> 44) & 127u;
+  uint32_t dk;
+  Lane L = lane_at(C, e, dk);
   bool closed = (q == N);          // a run completed exactly at N earlier
   bool err = false;
   RecGroup G{~0ull, REC_RUN, REC_RUN, REC_RUN, REC_RUN, 0u};
@@ -1499,37 +1011,16 @@ __global__ __launch_bounds__(DEC_PARSE_THREADS) PARSE_ATTR void dec_emit(DecArgs
       closed = closed || q == N;
     }
   };
-  // the general loop (and, before round 6, the fast one: as dec_sync)
-  auto emit = [&](auto fast_tag) {
-    constexpr bool FAST = decltype(fast_tag)::value;
-    if constexpr (FAST) {
-#pragma unroll
-      for (int k = 0; k < N_STREAMS; ++k) SP.g[k] = fast_param(SP.g[k]);
-    }
-    for (;;) {
-      // at a prefix position
-      const bool at_n = q == N && (dk == 0 || closed);   // every pixel accounted for
-      if (active && (L.pos >= end || L.pos >= hard)) active = false;
-      if (!__any(active)) break;
-      bool ok;
-      if constexpr (FAST) ok = lane_ok_fast(L);
-      else ok = lane_ok(L);
-      if (__any(active && !ok)) ring_fill<FAST>(wring, p, len, al16, L);
-      if (!active) continue;
-      uint32_t s0 = 0, s1 = 0, s2 = 0, s3 = 0;
-      uint32_t pfx;
-      if constexpr (FAST) pfx = pixel_event_fast(L, my, S, SP, s0, s1, s2, s3);
-      else pfx = pixel_event(L, my, S, SP, s0, s1, s2, s3);
-      handle(at_n, pfx, s0, s1, s2, s3);
-    }
-  };
-  const bool fast = !a.parse_slow && reinterpret_cast<const DecTables*>(a.tables)[f].fast;
-  // the fast parse in 32-bit positions relative to B, as dec_sync's (round 6)
-  const unsigned long long B = (active && L.pos < begin ? L.pos : begin) & ~31ull;
-  if (fast && __all(!active || (L.pos >= B && end - B < (1ull << 30)))) {
-    const uint32_t fp_pfx = fast_param(SP.g[PFX_STREAM]);
+  // Two loops, as dec_sync: the fast parse in 32-bit positions relative to B
+  // and the general symbol-by-symbol parse, which reads any tables.  The fast
+  // loop is this kernel's own copy of RelCursor's: through the struct dec_emit
+  // was 2-4 % slower at 64 x 1080p.
+  const bool fast = parse_fast(a, f);
+  const unsigned long long B = rel_base(active, L.pos, begin);
+  if (fast && rel_fits(active, L.pos, B, end)) {
+    const uint32_t fp_pfx = fast_param(C.SP.g[PFX_STREAM]);
     const uint32_t bwl = (uint32_t)(B >> 5);
-    const uint32_t rhard = hard > B ? (uint32_t)min(hard - B, (unsigned long long)0xFFFFFFFFu) : 0u;
+    const uint32_t rhard = C.hard > B ? (uint32_t)min(C.hard - B, (unsigned long long)0xFFFFFFFFu) : 0u;
     const uint32_t rlim = active ? min((uint32_t)(end - B), rhard) : 0u;
     uint32_t r = active ? (uint32_t)(L.pos - B) : 0u;
     uint32_t wsr = 0, rfill = 0;
@@ -1539,18 +1030,28 @@ __global__ __launch_bounds__(DEC_PARSE_THREADS) PARSE_ATTR void dec_emit(DecArgs
       if (!__any(active)) break;
       if (__any(active && r >= rfill)) {
         const uint32_t wsa = (bwl + (r >> 5)) & ~3u;
-        ring_fill_ws(wring, p, len, al16, wsa);
+        ring_fill_ws(C.wring, C.p, C.len, C.al16, wsa);
         wsr = wsa - bwl;
         rfill = (wsr + RING_W - 2u) << 5;
       }
       if (!active) continue;
       uint32_t s0 = 0, s1 = 0, s2 = 0, s3 = 0, tot;
-      const uint32_t pfx = pixel_event_fast_at(my, S, fp_pfx, (r >> 5) - wsr, r & 31u, s0, s1, s2, s3, tot);
+      const uint32_t pfx = pixel_event_fast_at(C.my, S, fp_pfx, (r >> 5) - wsr, r & 31u, s0, s1, s2, s3, tot);
       r += tot;
       handle(at_n, pfx, s0, s1, s2, s3);
     }
   } else {
-    emit(std::false_type{});   // (any tables; the general parse)
+    for (;;) {
+      // at a prefix position
+      const bool at_n = q == N && (dk == 0 || closed);   // every pixel accounted for
+      if (active && (L.pos >= end || L.pos >= C.hard)) active = false;
+      if (!__any(active)) break;
+      (void)wave_refill(C, L, active);
+      if (!active) continue;
+      uint32_t s0 = 0, s1 = 0, s2 = 0, s3 = 0;
+      const uint32_t pfx = pixel_event(L, C.my, S, C.SP, s0, s1, s2, s3);
+      handle(at_n, pfx, s0, s1, s2, s3);
+    }
   }
   G.flush(rec, q0, q0);   // last group: per-record stores (the next lane may own the rest)
   if (err) set_status(&a.status[f], NICE_E_FORMAT);
@@ -1678,7 +1179,7 @@ __global__ __launch_bounds__(64 * DEC_PLACE_WAVES) void dec_place(DecArgs a) {
   hn = uni(hn);
   const unsigned long long q_first = a.chunk_start[base + j];
   // pixels before the meeting point: where the head's events must end
-  const unsigned long long q_meet_v = q_first + (ag == 0u ? 0ull : (a.ck[cki] >> 32));
+  const unsigned long long q_meet_v = q_first + (ag == 0u ? 0ull : ck_px(a.ck[cki]));
   const unsigned long long q_meet = ((unsigned long long)uni((uint32_t)(q_meet_v >> 32)) << 32) | uni((uint32_t)q_meet_v);
   unsigned long long q = head ? q_first : q_meet;
   const uint64_t N = (uint64_t)a.W * a.H;
@@ -1690,7 +1191,7 @@ __global__ __launch_bounds__(64 * DEC_PLACE_WAVES) void dec_place(DecArgs a) {
   bool err = false, stopped = false;
   for (uint32_t part = head ? 0u : 1u; part < 2u && !stopped; ++part) {
   // events [i_first, nev) of this part's buffer
-  const uint32_t* evp = part == 0u ? a.hev + hev_group(a, f, j) : a.ev + ev_group(a, f, j);
+  const uint32_t* evp = part == 0u ? a.hev + ev_group(a, f, j, a.hev_cap) : a.ev + ev_group(a, f, j, a.ev_cap);
   const uint32_t i_first = part == 0u ? 0u : i_first1, nev = part == 0u ? hn : nev1;
   if (part == 1u && head && q != q_meet) {
     // the head must end where the first pass's events take over, or the two

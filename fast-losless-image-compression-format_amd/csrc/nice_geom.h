@@ -7,10 +7,13 @@
 #include <stddef.h>
 #include <stdint.h>
 
+// NICE_HDI: host and device under hipcc (always inlined in a kernel), plain inline elsewhere
 #if defined(__HIPCC__) || defined(__CUDACC__)
 #define NICE_HD __host__ __device__
+#define NICE_HDI __host__ __device__ __forceinline__
 #else
 #define NICE_HD
+#define NICE_HDI inline
 #endif
 
 namespace nice {

@@ -8,14 +8,7 @@
 #pragma once
 #include <stdint.h>
 
-#include "nice_geom.h"
-
-// host and device under hipcc (always inlined in a kernel), plain inline elsewhere
-#if defined(__HIPCC__) || defined(__CUDACC__)
-#define NICE_HDI __host__ __device__ __forceinline__
-#else
-#define NICE_HDI inline
-#endif
+#include "nice_geom.h"   // (NICE_HDI)
 
 namespace nice {
 

@@ -3,18 +3,20 @@
 dec_tables gives a frame the fast parse (DecTables::fast: one 64-bit window
 per pixel event, pixel_event_fast / pixel_event_fast_at, every symbol one
 first-level lookup) or the general parse (dsym_gp: symbol by symbol, ring
-top-up, long-code search); dec_sync, dec_sync_settle and dec_emit have code
-for each.  The hand-built streams of tests/parse_streams.py put what no
-encoder writes on the fast parse ("flat"), its longest events at every bit
-alignment and across slice ends ("long_event"), and long codes into eight
-streams of the general parse, the prefix stream included ("all12");
-tests/test_parse_streams_cpu.py checks that they hold it.
+top-up, long-code search); dec_sync, dec_sync_settle and dec_emit have a loop
+for each (dec_strict_refill: the general one only).  The hand-built streams
+of tests/parse_streams.py put what no encoder writes on the fast parse
+("flat"), its longest events at every bit alignment and across slice ends
+("long_event"), and long codes into eight streams of the general parse, the
+prefix stream included ("all12"); tests/test_parse_streams_cpu.py checks that
+they hold it.
 
-Which fast code a case reaches: dec_sync parses with pixel_event_fast_at in
-its relative-position loop (own refill bound); pixel_event_fast and
-lane_ok_fast run in dec_sync_settle only, which walks slices when the queued
-iterations did not reach the fixpoint -- test_settle_walks_the_fast_parse
-(one queued iteration) and the slow-sync stream.
+Which fast code a case reaches: dec_sync and dec_emit parse with
+pixel_event_fast_at in a relative-position loop each (own refill bound), and
+have no other fast loop; pixel_event_fast and lane_ok_fast run in
+dec_sync_settle only, which walks slices when the queued iterations did not
+reach the fixpoint -- test_settle_walks_the_fast_parse (one queued iteration)
+and the slow-sync stream.
 
 Every case decodes one small stream, compares every byte with the oracle's
 decode in the default mode and with DEC_STRICT_REFERENCE, and asserts from the
