@@ -1208,6 +1208,74 @@ def _tensor_pitches(t, layout):
     return ((s1 if rh > 1 else 3 * rw), 0) if s0 == 1 and (rw == 1 or s2 == 3) else None
 
 
+def _decode_set_tensor(who: str, entry: str, resized: bool, iset: ImageSet, *, images, windows, size, out, dtype,
+                       scale, bias, flip, channels_last: bool, flags: int, stream, ctx):
+    """``decode_set_tensor`` (every output has its window's size) and
+    ``decode_set_resized`` (``resized``: every output is ``size`` = (oh, ow)),
+    whose arguments these are: the checks, each a NiceError(E_ARG) that names
+    ``who``, the outputs and their one layout, then the C entry point ``entry``
+    and ``decode_set``'s tail."""
+    import torch
+    dtype = torch.float16 if dtype is None else dtype
+    dt = {torch.float32: TENSOR_F32, torch.float16: TENSOR_F16, torch.bfloat16: TENSOR_BF16}.get(dtype)
+    if dt is None:
+        raise NiceError(E_ARG, f"{who}: dtype must be torch.float32, torch.float16 or torch.bfloat16")
+    if resized:
+        try:
+            oh, ow = (int(v) for v in size)
+        except (TypeError, ValueError):
+            raise NiceError(E_ARG, f"{who}: size must be (oh, ow)") from None
+        if not (1 <= oh <= RESIZE_MAX and 1 <= ow <= RESIZE_MAX):
+            raise NiceError(E_ARG, f"{who}: size must be within 1..{RESIZE_MAX} on both axes")
+    windows, m, slot_first, n = _set_windows(who, iset, images, windows)
+    packed = iset.packed
+    tables = _host_tables(torch, who, iset, n)
+    scale, bias = [_f32(v) for v in scale], [_f32(v) for v in bias]
+    if len(scale) != 3 or len(bias) != 3:
+        raise NiceError(E_ARG, f"{who}: scale and bias have three entries each")
+    flips = [0] * m if flip is None else [1 if f else 0 for f in flip]
+    if len(flips) != m:
+        raise NiceError(E_ARG, f"{who}: flip must have one entry per window")
+    dev = packed.device
+
+    def new(*shape):   # [..., 3, h, w] in the memory format asked for
+        if channels_last:
+            return torch.empty(shape[:-3] + shape[-2:] + (3,), dtype=dtype, device=dev).movedim(-1, -3)
+        return torch.empty(shape, dtype=dtype, device=dev)
+
+    if not resized:
+        shapes = [(3, wdw[4], wdw[3]) for wdw in windows]
+        shape_msg = f"{who}: out must be [M, 3, rh, rw] or a list of M tensors [3, rh, rw] of their windows"
+    else:
+        shapes = [(3, oh, ow)] * m
+        shape_msg = f"{who}: out must be [M, 3, oh, ow] or a list of M tensors [3, oh, ow]"
+        if out is None:   # one batch tensor
+            out = new(m, 3, oh, ow)
+    outs, result = _set_outputs(out, windows, lambda wdw: new(3, wdw[4], wdw[3]), shape_msg)
+    for shape, o in zip(shapes, outs):
+        if not hasattr(o, "dim") or o.dim() != 3 or tuple(o.shape) != shape:
+            raise NiceError(E_ARG, shape_msg)
+        if o.dtype != dtype or not o.is_cuda or o.device != dev:
+            raise NiceError(E_ARG, f"{who}: out must have the dtype asked for, on the set's device")
+    # one layout per call: the first that every output's strides fit
+    for layout in (TENSOR_PLANAR, TENSOR_INTERLEAVED):
+        pitches = [_tensor_pitches(o, layout) for o in outs]
+        if all(v is not None for v in pitches):
+            break
+    else:
+        raise NiceError(E_ARG, f"{who}: the outputs' strides must all be planar (innermost 1) or all interleaved "
+                               "(channel stride 1, innermost 3)")
+    status = torch.full((slot_first[m],), 99, dtype=torch.int32, device=dev)
+    rc = getattr(lib(), entry)(
+        *_launch(torch, dev, stream, ctx), _p(packed), int(tables[0][n]), *map(_p, tables),
+        *_set_geom(iset.widths, iset.heights, iset.tile_w, iset.tile_h), _win_array(windows),
+        (ctypes.c_uint8 * m)(*flips), *((ow, oh) if resized else ()), *_images(outs, [v[0] for v in pitches]),
+        (ctypes.c_uint64 * m)(*[v[1] for v in pitches]), m, dt, layout, (ctypes.c_float * 3)(*scale),
+        (ctypes.c_float * 3)(*bias), flags, _p(status))
+    _check(rc, entry)
+    return _decode_tail(stream, [(entry, status)], result, alpha_field=False)
+
+
 def decode_set_tensor(iset: ImageSet, images=None, windows=None, out=None, dtype=None,
                       scale=(1 / 255,) * 3, bias=(0.,) * 3, flip=None, channels_last: bool = False,
                       flags: int = DEC_ALPHA_FILL_FF, stream=None, ctx: "_Ctx | None" = None):
@@ -1233,51 +1301,9 @@ def decode_set_tensor(iset: ImageSet, images=None, windows=None, out=None, dtype
     kernel: no uint8 image and no float32 temporary exist.  Errors, the
     untouched elements of a failed tile, ``.statuses`` and ``.out`` and the wait
     are ``decode_set``'s."""
-    import torch
-    dtype = torch.float16 if dtype is None else dtype
-    dt = {torch.float32: TENSOR_F32, torch.float16: TENSOR_F16, torch.bfloat16: TENSOR_BF16}.get(dtype)
-    if dt is None:
-        raise NiceError(E_ARG, "decode_set_tensor: dtype must be torch.float32, torch.float16 or torch.bfloat16")
-    windows, m, slot_first, n = _set_windows("decode_set_tensor", iset, images, windows)
-    packed = iset.packed
-    tables = _host_tables(torch, "decode_set_tensor", iset, n)
-    scale, bias = [_f32(v) for v in scale], [_f32(v) for v in bias]
-    if len(scale) != 3 or len(bias) != 3:
-        raise NiceError(E_ARG, "decode_set_tensor: scale and bias have three entries each")
-    flips = [0] * m if flip is None else [1 if f else 0 for f in flip]
-    if len(flips) != m:
-        raise NiceError(E_ARG, "decode_set_tensor: flip must have one entry per window")
-    dev = packed.device
-    shape_msg = "decode_set_tensor: out must be [M, 3, rh, rw] or a list of M tensors [3, rh, rw] of their windows"
-
-    def new(wdw):
-        if channels_last:
-            return torch.empty((wdw[4], wdw[3], 3), dtype=dtype, device=dev).permute(2, 0, 1)
-        return torch.empty((3, wdw[4], wdw[3]), dtype=dtype, device=dev)
-
-    outs, result = _set_outputs(out, windows, new, shape_msg)
-    for wdw, o in zip(windows, outs):
-        if not hasattr(o, "dim") or o.dim() != 3 or tuple(o.shape) != (3, wdw[4], wdw[3]):
-            raise NiceError(E_ARG, shape_msg)
-        if o.dtype != dtype or not o.is_cuda or o.device != dev:
-            raise NiceError(E_ARG, "decode_set_tensor: out must have the dtype asked for, on the set's device")
-    # one layout per call: the first that every output's strides fit
-    for layout in (TENSOR_PLANAR, TENSOR_INTERLEAVED):
-        pitches = [_tensor_pitches(o, layout) for o in outs]
-        if all(v is not None for v in pitches):
-            break
-    else:
-        raise NiceError(E_ARG, "decode_set_tensor: the outputs' strides must all be planar (innermost 1) or all "
-                               "interleaved (channel stride 1, innermost 3)")
-    status = torch.full((slot_first[m],), 99, dtype=torch.int32, device=dev)
-    rc = lib().nice_decode_set_tensor_dev(
-        *_launch(torch, dev, stream, ctx), _p(packed), int(tables[0][n]), *map(_p, tables),
-        *_set_geom(iset.widths, iset.heights, iset.tile_w, iset.tile_h), _win_array(windows),
-        (ctypes.c_uint8 * m)(*flips), *_images(outs, [v[0] for v in pitches]),
-        (ctypes.c_uint64 * m)(*[v[1] for v in pitches]), m, dt, layout, (ctypes.c_float * 3)(*scale),
-        (ctypes.c_float * 3)(*bias), flags, _p(status))
-    _check(rc, "nice_decode_set_tensor_dev")
-    return _decode_tail(stream, [("nice_decode_set_tensor_dev", status)], result, alpha_field=False)
+    return _decode_set_tensor("decode_set_tensor", "nice_decode_set_tensor_dev", False, iset, images=images,
+                              windows=windows, size=None, out=out, dtype=dtype, scale=scale, bias=bias, flip=flip,
+                              channels_last=channels_last, flags=flags, stream=stream, ctx=ctx)
 
 
 def decode_set_resized(iset: ImageSet, windows=None, images=None, size=None, out=None, dtype=None,
@@ -1349,56 +1375,10 @@ def decode_set_resized(iset: ImageSet, windows=None, images=None, size=None, out
     written iff every tile its tap rectangle (columns lo..hi by rows lo..hi)
     meets decoded.  The resampling takes two launches whatever M is: the
     weights, computed on the device, and the separable filter."""
-    import torch
-    who = "decode_set_resized"
-    dtype = torch.float16 if dtype is None else dtype
-    dt = {torch.float32: TENSOR_F32, torch.float16: TENSOR_F16, torch.bfloat16: TENSOR_BF16}.get(dtype)
-    if dt is None:
-        raise NiceError(E_ARG, f"{who}: dtype must be torch.float32, torch.float16 or torch.bfloat16")
-    try:
-        oh, ow = (int(v) for v in size)
-    except (TypeError, ValueError):
-        raise NiceError(E_ARG, f"{who}: size must be (oh, ow)") from None
-    if not (1 <= oh <= RESIZE_MAX and 1 <= ow <= RESIZE_MAX):
-        raise NiceError(E_ARG, f"{who}: size must be within 1..{RESIZE_MAX} on both axes")
-    windows, m, slot_first, n = _set_windows(who, iset, images, windows)
-    packed = iset.packed
-    tables = _host_tables(torch, who, iset, n)
-    scale, bias = [_f32(v) for v in scale], [_f32(v) for v in bias]
-    if len(scale) != 3 or len(bias) != 3:
-        raise NiceError(E_ARG, f"{who}: scale and bias have three entries each")
-    flips = [0] * m if flip is None else [1 if f else 0 for f in flip]
-    if len(flips) != m:
-        raise NiceError(E_ARG, f"{who}: flip must have one entry per window")
-    dev = packed.device
-    shape_msg = f"{who}: out must be [M, 3, oh, ow] or a list of M tensors [3, oh, ow]"
-    if out is None:   # one batch tensor, in the memory format asked for
-        out = (torch.empty((m, oh, ow, 3), dtype=dtype, device=dev).permute(0, 3, 1, 2) if channels_last else
-               torch.empty((m, 3, oh, ow), dtype=dtype, device=dev))
-    outs, result = _set_outputs(out, windows, None, shape_msg)
-    for o in outs:
-        if not hasattr(o, "dim") or o.dim() != 3 or tuple(o.shape) != (3, oh, ow):
-            raise NiceError(E_ARG, shape_msg)
-        if o.dtype != dtype or not o.is_cuda or o.device != dev:
-            raise NiceError(E_ARG, f"{who}: out must have the dtype asked for, on the set's device")
-    # one layout per call: the first that every output's strides fit
-    for layout in (TENSOR_PLANAR, TENSOR_INTERLEAVED):
-        pitches = [_tensor_pitches(o, layout) for o in outs]
-        if all(v is not None for v in pitches):
-            break
-    else:
-        raise NiceError(E_ARG, f"{who}: the outputs' strides must all be planar (innermost 1) or all interleaved "
-                               "(channel stride 1, innermost 3)")
-    status = torch.full((slot_first[m],), 99, dtype=torch.int32, device=dev)
-    name = "nice_decode_set_resized_aa_dev" if antialias else "nice_decode_set_resized_dev"
-    rc = getattr(lib(), name)(
-        *_launch(torch, dev, stream, ctx), _p(packed), int(tables[0][n]), *map(_p, tables),
-        *_set_geom(iset.widths, iset.heights, iset.tile_w, iset.tile_h), _win_array(windows),
-        (ctypes.c_uint8 * m)(*flips), ow, oh, *_images(outs, [v[0] for v in pitches]),
-        (ctypes.c_uint64 * m)(*[v[1] for v in pitches]), m, dt, layout, (ctypes.c_float * 3)(*scale),
-        (ctypes.c_float * 3)(*bias), flags, _p(status))
-    _check(rc, name)
-    return _decode_tail(stream, [(name, status)], result, alpha_field=False)
+    entry = "nice_decode_set_resized_aa_dev" if antialias else "nice_decode_set_resized_dev"
+    return _decode_set_tensor("decode_set_resized", entry, True, iset, images=images, windows=windows, size=size,
+                              out=out, dtype=dtype, scale=scale, bias=bias, flip=flip, channels_last=channels_last,
+                              flags=flags, stream=stream, ctx=ctx)
 
 
 # Host-side container of an image set: one file, little-endian throughout

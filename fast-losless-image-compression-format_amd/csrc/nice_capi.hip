@@ -1422,6 +1422,58 @@ int nice_set_split_dev(nice_ctx* ctx, void* stream, const uint8_t* const* h_img,
                                 d_tiles, tile_stride);
 }
 
+extern "C++" {
+namespace {
+// What nice_set_merge_dev and nice_set_merge_tensor_dev share, the merge kernel
+// alone (ctx, the channels and the call's own arguments checked by the caller);
+// Win is the window descriptor of the kernel: the set and the windows
+// (table(tab)), the slots, the upload, then launch(d_wins).
+template <class Win, class Table, class Launch>
+int set_merge_alone(nice_ctx* ctx, void* stream, const uint8_t* d_tiles, uint64_t tile_stride, const uint64_t* d_src_off,
+                    const uint32_t* d_slot_win, const uint32_t* d_slot_tile, uint32_t n_slots, uint8_t tile_channels,
+                    const uint32_t* h_w, const uint32_t* h_h, uint32_t K, uint32_t tile_w, uint32_t tile_h,
+                    const uint32_t* h_win, uint32_t M, Table table, Launch launch) {
+  std::vector<uint32_t> slot_first((size_t)M + 1);
+  int rc = nice_set_select(h_w, h_h, K, tile_w, tile_h, h_win, M, slot_first.data());
+  if (rc) return rc;
+  std::vector<Win> tab;
+  if ((rc = table(tab))) return rc;
+  if (n_slots == 0) return NICE_OK;
+  if (!d_tiles || !d_slot_win || !d_slot_tile) return NICE_E_ARG;
+  if (!d_src_off && tile_stride < (uint64_t)tile_w * tile_h * tile_channels) return NICE_E_ARG;
+  NICE_HIP(hipSetDevice(ctx->device));
+  if ((rc = ctx->tile_tab.grow(M * sizeof(Win)))) return rc;
+  NICE_HIP(hipMemcpyAsync(ctx->tile_tab.ptr, tab.data(), M * sizeof(Win), hipMemcpyHostToDevice, (hipStream_t)stream));
+  return launch((const Win*)ctx->tile_tab.ptr);
+}
+
+// The slots of one merge launch, as set_merge_launch and set_merge_tensor_launch take them.
+struct MergeSlots {
+  const uint8_t* tiles;
+  uint64_t stride;
+  const uint64_t* src_off;
+  const uint32_t *win, *idx;
+  const int32_t* status;
+  uint32_t n;
+  uint8_t channels;
+};
+// The tail of nice_decode_set_dev and nice_decode_set_tensor_dev: merge(slots)
+// once for the coded slots (decoded, dec_channels bytes per pixel, with their
+// statuses) and once for the raw ones (at their offsets in the packed buffer, 3
+// bytes per pixel); a kind without slots is not launched.
+template <class Merge>
+int set_merge_both(const DevSlots& d, const uint8_t* d_packed, uint8_t dec_channels, Merge merge) {
+  const MergeSlots both[2] = {{d.dec, d.stride, nullptr, d.c_win, d.c_idx, d.c_st, d.nc, dec_channels},
+                              {d_packed, 0, d.s_src, d.s_win, d.s_idx, nullptr, d.ns, 3}};
+  for (const MergeSlots& g : both) {
+    if (!g.n) continue;
+    if (int rc = merge(g)) return rc;
+  }
+  return NICE_OK;
+}
+}  // namespace
+}  // extern "C++"
+
 int nice_set_merge_dev(nice_ctx* ctx, void* stream, const uint8_t* d_tiles, uint64_t tile_stride,
                        const uint64_t* d_src_off, const uint32_t* d_slot_win, const uint32_t* d_slot_tile,
                        const int32_t* d_slot_status, uint32_t n_slots, uint8_t tile_channels, const uint32_t* h_w,
@@ -1431,21 +1483,16 @@ int nice_set_merge_dev(nice_ctx* ctx, void* stream, const uint8_t* d_tiles, uint
   if (!ctx) return NICE_E_ARG;
   if ((tile_channels != 3 && tile_channels != 4) || (out_channels != 3 && out_channels != 4)) return NICE_E_ARG;
   if (d_src_off && tile_channels != 3) return NICE_E_ARG;   // (raw tiles in a packed buffer hold 3 bytes per pixel)
-  std::vector<uint32_t> slot_first((size_t)M + 1);
-  int rc = nice_set_select(h_w, h_h, K, tile_w, tile_h, h_win, M, slot_first.data());
-  if (rc) return rc;
-  std::vector<SetWindow> tab;
-  if ((rc = set_window_table(h_w, h_h, K, tile_w, tile_h, h_win, h_out, h_out_pitch, M, out_channels, tab))) return rc;
-  if (n_slots == 0) return NICE_OK;
-  if (!d_tiles || !d_slot_win || !d_slot_tile) return NICE_E_ARG;
-  if (!d_src_off && tile_stride < (uint64_t)tile_w * tile_h * tile_channels) return NICE_E_ARG;
-  NICE_HIP(hipSetDevice(ctx->device));
-  if ((rc = ctx->tile_tab.grow(M * sizeof(SetWindow)))) return rc;
-  NICE_HIP(hipMemcpyAsync(ctx->tile_tab.ptr, tab.data(), M * sizeof(SetWindow), hipMemcpyHostToDevice,
-                          (hipStream_t)stream));
-  return nice::set_merge_launch(stream, d_tiles, tile_stride, d_src_off, d_slot_win, d_slot_tile, d_slot_status,
-                                n_slots, (const SetWindow*)ctx->tile_tab.ptr, M, tile_w, tile_h, tile_channels,
-                                out_channels, alpha);
+  return set_merge_alone<SetWindow>(
+      ctx, stream, d_tiles, tile_stride, d_src_off, d_slot_win, d_slot_tile, n_slots, tile_channels, h_w, h_h, K, tile_w,
+      tile_h, h_win, M,
+      [&](std::vector<SetWindow>& tab) {
+        return set_window_table(h_w, h_h, K, tile_w, tile_h, h_win, h_out, h_out_pitch, M, out_channels, tab);
+      },
+      [&](const SetWindow* d_wins) {
+        return nice::set_merge_launch(stream, d_tiles, tile_stride, d_src_off, d_slot_win, d_slot_tile, d_slot_status,
+                                      n_slots, d_wins, M, tile_w, tile_h, tile_channels, out_channels, alpha);
+      });
 }
 
 int nice_encode_set_dev(nice_ctx* ctx, void* stream, const uint8_t* const* h_img, const uint64_t* h_pitch,
@@ -1511,42 +1558,44 @@ int nice_decode_set_dev(nice_ctx* ctx, void* stream, const uint8_t* d_packed, ui
   if ((rc = set_decode_colour(ctx, stream, d_packed, packed_bytes, h_off, h_len, h_kind, tile_w, tile_h, first.data(),
                               nx.data(), h_win, M, wins.data(), M * sizeof(SetWindow), out_channels, flags, d_status, d)))
     return rc;
-  const SetWindow* d_wins = (const SetWindow*)d.head;
-  if (d.nc) {
-    if ((rc = nice::set_merge_launch(stream, d.dec, d.stride, nullptr, d.c_win, d.c_idx, d.c_st, d.nc, d_wins, M, tile_w,
-                                     tile_h, out_channels, out_channels, 0)))
-      return rc;
-  }
-  if (d.ns) {
-    const uint32_t fill = (flags & NICE_DEC_ALPHA_FILL_FF) ? 255u : 0u;
-    if ((rc = nice::set_merge_launch(stream, d_packed, 0, d.s_src, d.s_win, d.s_idx, nullptr, d.ns, d_wins, M, tile_w,
-                                     tile_h, 3, out_channels, fill)))
-      return rc;
-  }
-  return NICE_OK;
+  const uint32_t fill = (flags & NICE_DEC_ALPHA_FILL_FF) ? 255u : 0u;   // byte +3 of a raw slot's pixels
+  return set_merge_both(d, d_packed, out_channels, [&](const MergeSlots& g) {
+    return nice::set_merge_launch(stream, g.tiles, g.stride, g.src_off, g.win, g.idx, g.status, g.n,
+                                  (const SetWindow*)d.head, M, tile_w, tile_h, g.channels, out_channels,
+                                  g.src_off ? fill : 0u);
+  });
 }
 
 namespace {
-// The tensor windows of M windows (checked as set_window_table checks its own;
-// NICE_E_ARG also for a base not aligned to the element or a row pitch below the window).
+// The output of tensor window j, `width` elements per row and channel
+// (h_plane_pitch non-null where planar: the caller's check): NICE_E_ARG for a
+// null base, one not aligned to the element, or a row pitch below the row;
+// plane_pitch: the window's, 0 where interleaved.
+int tensor_out_check(const void* out, uint64_t row_pitch, const uint64_t* h_plane_pitch, uint32_t j, uint32_t width,
+                     uint32_t dtype, uint32_t layout, uint64_t& plane_pitch) {
+  const bool planar = layout == NICE_TENSOR_PLANAR;
+  if (!out || ((uintptr_t)out & (nice::set_tensor_elem_bytes(dtype) - 1))) return NICE_E_ARG;
+  if (row_pitch < (uint64_t)width * (planar ? 1u : 3u)) return NICE_E_ARG;
+  plane_pitch = planar ? h_plane_pitch[j] : 0;
+  return NICE_OK;
+}
+
+// The tensor windows of M windows (checked as set_window_table checks its own, and by tensor_out_check).
 int set_tensor_window_table(const uint32_t* h_w, const uint32_t* h_h, uint32_t tile_w, uint32_t tile_h,
                             const uint32_t* h_win, const uint8_t* h_flip, void* const* h_out,
                             const uint64_t* h_row_pitch, const uint64_t* h_plane_pitch, uint32_t M, uint32_t dtype,
                             uint32_t layout, std::vector<SetTensorWindow>& tab) {
-  const uint32_t es = nice::set_tensor_elem_bytes(dtype);
-  const bool planar = layout == NICE_TENSOR_PLANAR;
-  if (!h_out || !h_row_pitch || (planar && !h_plane_pitch)) return NICE_E_ARG;
+  if (!h_out || !h_row_pitch || (layout == NICE_TENSOR_PLANAR && !h_plane_pitch)) return NICE_E_ARG;
   tab.resize(M);
   for (uint32_t j = 0; j < M; ++j) {
     const uint32_t* q = h_win + 5ull * j;
     const uint32_t w = h_w[q[0]], h = h_h[q[0]];
-    if (!h_out[j] || ((uintptr_t)h_out[j] & (es - 1))) return NICE_E_ARG;
-    if (h_row_pitch[j] < (uint64_t)q[3] * (planar ? 1u : 3u)) return NICE_E_ARG;
+    uint64_t pp;
+    if (int rc = tensor_out_check(h_out[j], h_row_pitch[j], h_plane_pitch, j, q[3], dtype, layout, pp)) return rc;
     const uint32_t nx = (w + tile_w - 1) / tile_w, ny = (h + tile_h - 1) / tile_h;
-    const uint64_t pp = planar ? h_plane_pitch[j] : 0;
     const bool flip = h_flip && h_flip[j];
     tab[j] = SetTensorWindow{h_out[j], h_row_pitch[j], pp, q[1], q[2], q[3], q[4], w, h, nx, nx * ny,
-                             nice::set_tensor_window_mode(h_out[j], h_row_pitch[j], pp, q[1], q[3], flip, dtype, layout),
+                             nice::set_tensor_window_mode(h_out[j], h_row_pitch[j], pp, q[1], q[3], flip, dtype),
                              flip ? 1u : 0u};
   }
   return NICE_OK;
@@ -1573,24 +1622,19 @@ int nice_set_merge_tensor_dev(nice_ctx* ctx, void* stream, const uint8_t* d_tile
   if (!ctx) return NICE_E_ARG;
   if (tile_channels != 3 && tile_channels != 4) return NICE_E_ARG;
   if (d_src_off && tile_channels != 3) return NICE_E_ARG;   // (raw tiles in a packed buffer hold 3 bytes per pixel)
-  int rc = set_tensor_check(dtype, layout, scale, bias);
-  if (rc) return rc;
-  std::vector<uint32_t> slot_first((size_t)M + 1);
-  if ((rc = nice_set_select(h_w, h_h, K, tile_w, tile_h, h_win, M, slot_first.data()))) return rc;
-  std::vector<SetTensorWindow> tab;
-  if ((rc = set_tensor_window_table(h_w, h_h, tile_w, tile_h, h_win, h_flip, h_out, h_row_pitch, h_plane_pitch, M, dtype,
-                                    layout, tab)))
-    return rc;
-  if (n_slots == 0) return NICE_OK;
-  if (!d_tiles || !d_slot_win || !d_slot_tile) return NICE_E_ARG;
-  if (!d_src_off && tile_stride < (uint64_t)tile_w * tile_h * tile_channels) return NICE_E_ARG;
-  NICE_HIP(hipSetDevice(ctx->device));
-  if ((rc = ctx->tile_tab.grow(M * sizeof(SetTensorWindow)))) return rc;
-  NICE_HIP(hipMemcpyAsync(ctx->tile_tab.ptr, tab.data(), M * sizeof(SetTensorWindow), hipMemcpyHostToDevice,
-                          (hipStream_t)stream));
-  return nice::set_merge_tensor_launch(stream, d_tiles, tile_stride, d_src_off, d_slot_win, d_slot_tile, d_slot_status,
-                                       n_slots, (const SetTensorWindow*)ctx->tile_tab.ptr, M, tile_w, tile_h,
-                                       tile_channels, dtype, layout, scale, bias);
+  if (int rc = set_tensor_check(dtype, layout, scale, bias)) return rc;
+  return set_merge_alone<SetTensorWindow>(
+      ctx, stream, d_tiles, tile_stride, d_src_off, d_slot_win, d_slot_tile, n_slots, tile_channels, h_w, h_h, K, tile_w,
+      tile_h, h_win, M,
+      [&](std::vector<SetTensorWindow>& tab) {
+        return set_tensor_window_table(h_w, h_h, tile_w, tile_h, h_win, h_flip, h_out, h_row_pitch, h_plane_pitch, M,
+                                       dtype, layout, tab);
+      },
+      [&](const SetTensorWindow* d_wins) {
+        return nice::set_merge_tensor_launch(stream, d_tiles, tile_stride, d_src_off, d_slot_win, d_slot_tile,
+                                             d_slot_status, n_slots, d_wins, M, tile_w, tile_h, tile_channels, dtype,
+                                             layout, scale, bias);
+      });
 }
 
 int nice_decode_set_tensor_dev(nice_ctx* ctx, void* stream, const uint8_t* d_packed, uint64_t packed_bytes,
@@ -1616,19 +1660,12 @@ int nice_decode_set_tensor_dev(nice_ctx* ctx, void* stream, const uint8_t* d_pac
   if ((rc = set_decode_colour(ctx, stream, d_packed, packed_bytes, h_off, h_len, h_kind, tile_w, tile_h, first.data(),
                               nx.data(), h_win, M, wins.data(), M * sizeof(SetTensorWindow), 4, flags, d_status, d)))
     return rc;
-  const SetTensorWindow* d_wins = (const SetTensorWindow*)d.head;
   ctx->last_set_merges = (d.nc ? 1u : 0u) + (d.ns ? 1u : 0u);
-  if (d.nc) {
-    if ((rc = nice::set_merge_tensor_launch(stream, d.dec, d.stride, nullptr, d.c_win, d.c_idx, d.c_st, d.nc, d_wins, M,
-                                            tile_w, tile_h, 4, dtype, layout, scale, bias)))
-      return rc;
-  }
-  if (d.ns) {
-    if ((rc = nice::set_merge_tensor_launch(stream, d_packed, 0, d.s_src, d.s_win, d.s_idx, nullptr, d.ns, d_wins, M,
-                                            tile_w, tile_h, 3, dtype, layout, scale, bias)))
-      return rc;
-  }
-  return NICE_OK;
+  return set_merge_both(d, d_packed, 4, [&](const MergeSlots& g) {
+    return nice::set_merge_tensor_launch(stream, g.tiles, g.stride, g.src_off, g.win, g.idx, g.status, g.n,
+                                         (const SetTensorWindow*)d.head, M, tile_w, tile_h, g.channels, dtype, layout,
+                                         scale, bias);
+  });
 }
 
 // ---- image sets: resized tensor output ------------------------------------------
@@ -1641,19 +1678,16 @@ int set_resize_window_table(const uint32_t* h_w, const uint32_t* h_h, uint32_t t
                             uint32_t out_h, void* const* h_out, const uint64_t* h_row_pitch,
                             const uint64_t* h_plane_pitch, uint32_t M, uint32_t dtype, uint32_t layout,
                             std::vector<SetResizeWindow>& tab) {
-  const uint32_t es = nice::set_tensor_elem_bytes(dtype);
-  const bool planar = layout == NICE_TENSOR_PLANAR;
   if (out_w == 0 || out_h == 0 || out_w > nice::RESIZE_MAX_OUT || out_h > nice::RESIZE_MAX_OUT) return NICE_E_ARG;
-  if (!h_out || !h_row_pitch || (planar && !h_plane_pitch)) return NICE_E_ARG;
+  if (!h_out || !h_row_pitch || (layout == NICE_TENSOR_PLANAR && !h_plane_pitch)) return NICE_E_ARG;
   tab.resize(M);
   for (uint32_t j = 0; j < M; ++j) {
     const uint32_t* q = h_win + 5ull * j;
-    if (!h_out[j] || ((uintptr_t)h_out[j] & (es - 1))) return NICE_E_ARG;
-    if (h_row_pitch[j] < (uint64_t)out_w * (planar ? 1u : 3u)) return NICE_E_ARG;
+    uint64_t pp;
+    if (int rc = tensor_out_check(h_out[j], h_row_pitch[j], h_plane_pitch, j, out_w, dtype, layout, pp)) return rc;
     const TileRange r = nice::window_tiles(tile_w, tile_h, q[1], q[2], q[3], q[4]);
-    const uint64_t pp = planar ? h_plane_pitch[j] : 0;
     tab[j] = SetResizeWindow{h_out[j], h_row_pitch[j], pp, q[1], q[2], q[3], q[4], r.tx0, r.ty0, r.tx1 - r.tx0,
-                             slot_first[j], nice::set_resize_window_mode(h_out[j], h_row_pitch[j], pp, dtype, layout),
+                             slot_first[j], nice::set_resize_window_mode(h_out[j], h_row_pitch[j], pp, dtype),
                              (h_flip && h_flip[j]) ? 1u : 0u};
   }
   return NICE_OK;

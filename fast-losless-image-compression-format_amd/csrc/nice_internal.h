@@ -131,7 +131,7 @@ struct SetTensorWindow {
 };
 uint32_t set_tensor_elem_bytes(uint32_t dtype);   // 0: unknown dtype
 uint32_t set_tensor_window_mode(const void* d_out, uint64_t row_pitch, uint64_t plane_pitch, uint32_t x0, uint32_t rw,
-                                bool flip, uint32_t dtype, uint32_t layout);
+                                bool flip, uint32_t dtype);   // plane_pitch 0: interleaved
 // set_merge_launch's slots and skips; every window element takes
 // fmaf(byte, scale[c], bias[c]) of its pixel's bytes +0..+2, converted to dtype.
 int set_merge_tensor_launch(void* stream, const uint8_t* d_tiles, uint64_t tile_stride, const uint64_t* d_src_off,
@@ -154,8 +154,7 @@ struct SetResizeWindow {
   uint32_t slot_first;
   uint32_t mode, flip;
 };
-uint32_t set_resize_window_mode(const void* d_out, uint64_t row_pitch, uint64_t plane_pitch, uint32_t dtype,
-                                uint32_t layout);
+uint32_t set_resize_window_mode(const void* d_out, uint64_t row_pitch, uint64_t plane_pitch, uint32_t dtype);
 // Every element of the n_wins windows from the slots its taps fall in (d_src[p]
 // as slot_position_sources gives it: dense slots at d_tiles + value *
 // tile_stride, dwords; raw slots at d_packed + value).  An element with a tap

@@ -13,6 +13,7 @@
 
 #include "../../include/nice.h"
 #include "nice_internal.h"
+#include "nice_tile_geom.hpp"
 #include "nice_tiles.hpp"
 
 namespace nice {
@@ -129,12 +130,12 @@ struct SetMergeArgs {
   uint32_t mode_cap;                   // the best mode the slots allow
 };
 
-// Pixels [xa, xa + nxp) of rows [ya, yb) of the tile at st (origin tx0, ty0)
-// -> window d.
+// The cut c of the tile at st -> window d.
 template <int MODE>
-__device__ __forceinline__ void set_merge_rows(const SetMergeArgs& a, const SetWindow& d, const uint8_t* st, uint32_t tx0,
-                                               uint32_t ty0, uint32_t xa, uint32_t nxp, uint32_t ya, uint32_t yb) {
+__device__ __forceinline__ void set_merge_rows(const SetMergeArgs& a, const SetWindow& d, const uint8_t* st,
+                                               const TileCut& c) {
   const uint32_t lane = threadIdx.x & 63u, wave = tl_wave();
+  const uint32_t tx0 = c.tx0, ty0 = c.ty0, xa = c.xa, nxp = c.nxp, ya = c.ya, yb = c.yb;
   for (uint32_t y = ya + wave; y < yb; y += TL_WAVES) {
     const uint8_t* srow = st + ((uint64_t)(y - ty0) * a.tw + (xa - tx0)) * a.tc;
     uint8_t* drow = d.out + (uint64_t)(y - d.y0) * d.pitch + (uint64_t)(xa - d.x0) * a.oc;
@@ -196,21 +197,14 @@ __global__ __launch_bounds__(TL_THREADS) void set_merge(SetMergeArgs a) {
   const SetWindow d = a.wins[wi];
   const uint32_t t = a.slot_tile[slot];
   if (t >= d.n_tiles) return;
-  const uint32_t ty = t / d.nx, tx = t % d.nx;
-  // the tile's pixels inside the rectangle and the image: [xa, xb) x [ya, yb)
-  const uint64_t tx0 = (uint64_t)tx * a.tw, ty0 = (uint64_t)ty * a.th;
-  const uint64_t xa64 = max(tx0, (uint64_t)d.x0);
-  const uint64_t xb64 = min(min(tx0 + a.tw, (uint64_t)d.x0 + d.rw), (uint64_t)d.w);
-  const uint64_t ya64 = max(ty0 + (uint64_t)band * a.rows_pb, (uint64_t)d.y0);
-  const uint64_t yb64 = min(min(ty0 + min((uint64_t)(band + 1) * a.rows_pb, (uint64_t)a.th), (uint64_t)d.y0 + d.rh),
-                            (uint64_t)d.h);
-  if (xa64 >= xb64 || ya64 >= yb64) return;
-  const uint32_t xa = (uint32_t)xa64, nxp = (uint32_t)(xb64 - xa64), ya = (uint32_t)ya64, yb = (uint32_t)yb64;
+  // the tile's pixels inside the rectangle and the image
+  const TileCut c = tile_cut(t, d.nx, a.tw, a.th, band, a.rows_pb, d.x0, d.y0, d.rw, d.rh, d.w, d.h);
+  if (c.empty) return;
   const uint8_t* st = a.tiles + (a.src_off ? (uint64_t)a.src_off[slot] : (uint64_t)slot * a.tile_stride);
   const uint32_t mode = min(d.mode, a.mode_cap);
-  if (mode == TL_QUAD) set_merge_rows<TL_QUAD>(a, d, st, (uint32_t)tx0, (uint32_t)ty0, xa, nxp, ya, yb);
-  else if (mode == TL_DWORD) set_merge_rows<TL_DWORD>(a, d, st, (uint32_t)tx0, (uint32_t)ty0, xa, nxp, ya, yb);
-  else set_merge_rows<TL_BYTES>(a, d, st, (uint32_t)tx0, (uint32_t)ty0, xa, nxp, ya, yb);
+  if (mode == TL_QUAD) set_merge_rows<TL_QUAD>(a, d, st, c);
+  else if (mode == TL_DWORD) set_merge_rows<TL_DWORD>(a, d, st, c);
+  else set_merge_rows<TL_BYTES>(a, d, st, c);
 }
 
 // ---- alpha (include/nice.h, "image sets: alpha") -------------------------------
@@ -296,13 +290,12 @@ struct SetAlphaMergeArgs {
 
 template <int MODE>
 __device__ __forceinline__ void set_alpha_merge_rows(const SetWindow& d, const uint8_t* st, uint32_t sp, bool cst,
-                                                     uint32_t cval, uint32_t tx0, uint32_t ty0, uint32_t xa, uint32_t nxp,
-                                                     uint32_t ya, uint32_t yb) {
+                                                     uint32_t cval, const TileCut& c) {
   const uint32_t lane = threadIdx.x & 63u, wave = tl_wave();
-  for (uint32_t y = ya + wave; y < yb; y += TL_WAVES) {
-    const uint8_t* srow = st + (uint64_t)(y - ty0) * sp + (xa - tx0);
-    uint8_t* drow = d.out + (uint64_t)(y - d.y0) * d.pitch + 4ull * (xa - d.x0);
-    alpha_merge_row<MODE>(srow, drow, nxp, cst, cval, lane);
+  for (uint32_t y = c.ya + wave; y < c.yb; y += TL_WAVES) {
+    const uint8_t* srow = st + (uint64_t)(y - c.ty0) * sp + (c.xa - c.tx0);
+    uint8_t* drow = d.out + (uint64_t)(y - d.y0) * d.pitch + 4ull * (c.xa - d.x0);
+    alpha_merge_row<MODE>(srow, drow, c.nxp, cst, cval, lane);
   }
 }
 
@@ -322,38 +315,29 @@ __global__ __launch_bounds__(TL_THREADS) void set_alpha_merge(SetAlphaMergeArgs 
   const SetWindow d = a.wins[wi];
   const uint32_t t = a.slot_tile[slot];
   if (t >= d.n_tiles) return;
-  const uint32_t ty = t / d.nx, tx = t % d.nx;
-  const uint64_t tx0 = (uint64_t)tx * a.tw, ty0 = (uint64_t)ty * a.th;
-  const uint64_t xa64 = max(tx0, (uint64_t)d.x0);
-  const uint64_t xb64 = min(min(tx0 + a.tw, (uint64_t)d.x0 + d.rw), (uint64_t)d.w);
-  const uint64_t ya64 = max(ty0 + (uint64_t)band * a.rows_pb, (uint64_t)d.y0);
-  const uint64_t yb64 = min(min(ty0 + min((uint64_t)(band + 1) * a.rows_pb, (uint64_t)a.th), (uint64_t)d.y0 + d.rh),
-                            (uint64_t)d.h);
-  if (xa64 >= xb64 || ya64 >= yb64) return;
-  const uint32_t xa = (uint32_t)xa64, nxp = (uint32_t)(xb64 - xa64), ya = (uint32_t)ya64, yb = (uint32_t)yb64;
+  const TileCut c = tile_cut(t, d.nx, a.tw, a.th, band, a.rows_pb, d.x0, d.y0, d.rw, d.rh, d.w, d.h);
+  if (c.empty) return;
   const bool cst = kind == 2;
   const uint32_t cval = (uint32_t)src & 255u;
   // the tile's plane: row pitch and first byte (unused for a constant)
   const uint32_t sp = kind == 0 ? a.aw3 : a.tw;
   const uint8_t* st = cst ? d.out : kind == 0 ? a.dec + src * a.dec_stride : a.packed + src;
   if (min(d.mode, a.mode_cap) == TL_QUAD)
-    set_alpha_merge_rows<TL_QUAD>(d, st, sp, cst, cval, (uint32_t)tx0, (uint32_t)ty0, xa, nxp, ya, yb);
+    set_alpha_merge_rows<TL_QUAD>(d, st, sp, cst, cval, c);
   else
-    set_alpha_merge_rows<TL_BYTES>(d, st, sp, cst, cval, (uint32_t)tx0, (uint32_t)ty0, xa, nxp, ya, yb);
+    set_alpha_merge_rows<TL_BYTES>(d, st, sp, cst, cval, c);
 }
 
 namespace {
+static_assert(TL_BYTES == 0 && TL_DWORD == 1 && TL_QUAD == 2, "byte_mode's values");
 // the best mode a base and its pitch (or stride) allow on their own
-uint32_t mode_of(const void* p, uint64_t s) {
-  return tl_aligned(p, s, 16) ? TL_QUAD : tl_aligned(p, s, 4) ? TL_DWORD : TL_BYTES;
-}
+uint32_t mode_of(const void* p, uint64_t s) { return byte_mode((uintptr_t)p, s, 0); }
 }  // namespace
 
 uint32_t set_image_mode(const uint8_t* d_img, uint64_t row_pitch) { return mode_of(d_img, row_pitch); }
 
 uint32_t set_window_mode(const uint8_t* d_out, uint64_t out_pitch, uint32_t x0) {
-  const uint32_t m = mode_of(d_out, out_pitch);
-  return (m == TL_QUAD && (x0 & 3u) != 0) ? (uint32_t)TL_DWORD : m;
+  return byte_mode((uintptr_t)d_out, out_pitch, x0);
 }
 
 int set_split_launch(void* stream, const SetImage* d_imgs, uint32_t K, uint32_t n, uint32_t channels, uint32_t tile_w,

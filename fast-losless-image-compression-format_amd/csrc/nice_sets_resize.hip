@@ -21,6 +21,7 @@
 #include "nice_resize.hpp"
 #include "nice_sets_tensor.hpp"
 #include "nice_slot_plan.hpp"
+#include "nice_tile_geom.hpp"
 #include "nice_tiles.hpp"
 
 namespace nice {
@@ -41,36 +42,6 @@ struct SetResizeArgs {
   float scale[3], bias[3];
 };
 
-// Where the pixels of a position are: pixel i of the slot at base + i * bpp;
-// bpp 0: nothing to read there (a failed or refused slot).
-struct ResizeSlot {
-  const uint8_t* base;
-  uint32_t bpp;
-};
-__device__ __forceinline__ ResizeSlot resize_slot(const SetResizeArgs& a, uint32_t p) {
-  const uint64_t s = a.src[p];
-  const uint32_t kind = (uint32_t)(s >> 62);
-  const uint64_t v = s & SLOT_SRC_VALUE;
-  const bool bad = kind > 1u || (a.slot_status && a.slot_status[p] != 0);
-  const uint8_t* base = kind == 0u ? a.tiles + v * a.tile_stride : a.packed + v;
-  return ResizeSlot{base, bad ? 0u : kind == 0u ? 4u : 3u};
-}
-// bytes +0..+2 of pixel i: one dword of a dense slot, three bytes of a raw one
-__device__ __forceinline__ uint32_t resize_ld(const ResizeSlot& s, uint32_t i) {
-  const uint8_t* p = s.base + (uint64_t)i * s.bpp;
-  return s.bpp == 4u ? ld32(p) : ld_px_bytes(p, 3u, 0u);
-}
-
-// x, held in a vector register: the constants of the conversion are the same in
-// every lane, and the scalar registers are short (the window, the arguments and
-// the loops' masks fill them)
-template <class T>
-__device__ __forceinline__ T in_vgpr(T x) {
-  static_assert(sizeof(T) == 4, "one register");
-  asm("" : "+v"(x));
-  return x;
-}
-
 // a column's taps, packed: bits 0-13 the column of i0 inside its tile, 14-21
 // the weight of i1, 22 whether i1 is the next pixel
 constexpr uint32_t RS_CX = 0x3FFFu, RS_F_SHIFT = 14, RS_STEP_SHIFT = 22;
@@ -82,20 +53,17 @@ constexpr uint32_t RS_CX = 0x3FFFu, RS_F_SHIFT = 14, RS_STEP_SHIFT = 22;
 template <int DT, int LAYOUT, int LP>
 __device__ __forceinline__ void set_resize_rows(const SetResizeArgs& a, const SetResizeWindow& d, uint32_t ya,
                                                 uint32_t yb) {
-  using E = TensorElem<DT>;
-  using B = typename E::bits;
+  using B = typename TensorElem<DT>::bits;
   constexpr uint32_t P = 1u << LP;
   const uint32_t lane = threadIdx.x & 63u, wave = tl_wave();
   const uint32_t G = (a.ow + P - 1u) >> LP;   // the groups of a row
-  // lanes per row: the power of two that holds the groups, up to the wave; the other lanes take the rows below
-  uint32_t ls = 0;
-  while (ls < 6u && (1u << ls) < G) ++ls;
-  const uint32_t lpr = 1u << ls, rpw = 64u >> ls;
-  const uint32_t lx = lane & (lpr - 1u), ly = lane >> ls;
+  const RowShare rs = row_share(G);   // the lanes a row does not need take the rows below
+  const uint32_t lpr = rs.lpr, rpw = rs.rpw, lx = lane & (lpr - 1u), ly = lane >> rs.ls;
   B* const out = reinterpret_cast<B*>(d.out);
   const float scale[3] = {in_vgpr(a.scale[0]), in_vgpr(a.scale[1]), in_vgpr(a.scale[2])};
   const float bias[3] = {in_vgpr(a.bias[0]), in_vgpr(a.bias[1]), in_vgpr(a.bias[2])};
-  const uint64_t plane_pitch = ((uint64_t)in_vgpr((uint32_t)(d.plane_pitch >> 32)) << 32) | in_vgpr((uint32_t)d.plane_pitch);
+  const uint64_t plane_pitch = in_vgpr64(d.plane_pitch);
+  const auto slot = [&](uint32_t p) { return slot_source(a.src, a.slot_status, a.tiles, a.tile_stride, a.packed, p); };
   for (uint32_t g = lx; g < G; g += lpr) {
     const uint32_t x = g << LP;
     // the columns' positions, once per block: the slot column of i0, and the rest packed
@@ -133,8 +101,7 @@ __device__ __forceinline__ void set_resize_rows(const SetResizeArgs& a, const Se
         const uint32_t wrap = cx1 == a.tw ? 1u : 0u;   // i1 is the first column of the tile to the right
         cx1 = wrap ? 0u : cx1;
         const uint32_t sc1 = sc[k] + wrap;
-        const ResizeSlot s00 = resize_slot(a, p0 + sc[k]), s01 = resize_slot(a, p0 + sc1);
-        const ResizeSlot s10 = resize_slot(a, p1 + sc[k]), s11 = resize_slot(a, p1 + sc1);
+        const SlotSource s00 = slot(p0 + sc[k]), s01 = slot(p0 + sc1), s10 = slot(p1 + sc[k]), s11 = slot(p1 + sc1);
         if ((s00.bpp & s01.bpp & s10.bpp & s11.bpp) == 4u) {   // all dense: four dwords
           v[k][0] = ld32(s00.base + 4ull * (o0 + cx0));
           v[k][1] = ld32(s01.base + 4ull * (o0 + cx1));
@@ -142,10 +109,10 @@ __device__ __forceinline__ void set_resize_rows(const SetResizeArgs& a, const Se
           v[k][3] = ld32(s11.base + 4ull * (o1 + cx1));
           okm |= (x + k < a.ow ? 1u : 0u) << k;
         } else if (min(min(s00.bpp, s01.bpp), min(s10.bpp, s11.bpp)) != 0u) {
-          v[k][0] = resize_ld(s00, o0 + cx0);
-          v[k][1] = resize_ld(s01, o0 + cx1);
-          v[k][2] = resize_ld(s10, o1 + cx0);
-          v[k][3] = resize_ld(s11, o1 + cx1);
+          v[k][0] = ld_tap(s00, o0 + cx0);
+          v[k][1] = ld_tap(s01, o0 + cx1);
+          v[k][2] = ld_tap(s10, o1 + cx0);
+          v[k][3] = ld_tap(s11, o1 + cx1);
           okm |= (x + k < a.ow ? 1u : 0u) << k;
         }
       }
@@ -155,43 +122,17 @@ __device__ __forceinline__ void set_resize_rows(const SetResizeArgs& a, const Se
         const uint32_t sh = 8u * c, fx = (cw[k] >> RS_F_SHIFT) & 255u;
         const uint32_t acc = resize_acc((v[k][0] >> sh) & 255u, (v[k][1] >> sh) & 255u, (v[k][2] >> sh) & 255u,
                                         (v[k][3] >> sh) & 255u, fx, r.f);
-        return E::cvt(__fmaf_rn(resize_unit(acc), scale[c], bias[c]));
+        return tensor_value<DT>(resize_unit(acc), scale[c], bias[c]);
       };
       bool whole = false;
       if constexpr (P > 1) {
         whole = okm == (1u << P) - 1u;   // (no bit is set past the row's end)
-        if (whole) {
-          if (LAYOUT == (int)NICE_TENSOR_PLANAR) {
-#pragma unroll
-            for (uint32_t c = 0; c < 3; ++c) {
-              B e[P];
-#pragma unroll
-              for (uint32_t k = 0; k < P; ++k) e[k] = elem(k, c);
-              st_elems<B, P>(orow + c * plane_pitch + x, e);
-            }
-          } else {
-            B e[3 * P];
-#pragma unroll
-            for (uint32_t k = 0; k < P; ++k) {
-#pragma unroll
-              for (uint32_t c = 0; c < 3; ++c) e[3 * k + c] = elem(k, c);
-            }
-#pragma unroll
-            for (uint32_t c = 0; c < 3; ++c) st_elems<B, P>(orow + 3ull * x + c * P, e + c * P);
-          }
-        }
+        if (whole) st_group<B, P, LAYOUT>(orow, plane_pitch, x, elem);
       }
       if (!whole) {
 #pragma unroll
         for (uint32_t k = 0; k < P; ++k) {
-          if ((okm >> k) & 1u) {
-#pragma unroll
-            for (uint32_t c = 0; c < 3; ++c) {
-              const B e = elem(k, c);
-              if (LAYOUT == (int)NICE_TENSOR_PLANAR) orow[c * plane_pitch + x + k] = e;
-              else orow[3ull * (x + k) + c] = e;
-            }
-          }
+          if ((okm >> k) & 1u) st_one<B, LAYOUT>(orow, plane_pitch, x + k, [&](uint32_t c) { return elem(k, c); });
         }
       }
     }
@@ -213,17 +154,9 @@ __global__ __launch_bounds__(TL_THREADS) void set_resize_tensor(SetResizeArgs a)
   }
 }
 
-uint32_t set_resize_window_mode(const void* d_out, uint64_t row_pitch, uint64_t plane_pitch, uint32_t dtype,
-                                uint32_t layout) {
-  const uint64_t es = set_tensor_elem_bytes(dtype);
-  uint32_t mode = 0;
-  for (uint32_t lp = 1; lp <= RS_MAX_MODE; ++lp) {
-    const uint64_t p = 1ull << lp;
-    if (((uintptr_t)d_out & (p * es - 1)) || (row_pitch & (p - 1))) break;
-    if (layout == NICE_TENSOR_PLANAR && (plane_pitch & (p - 1))) break;
-    mode = lp;
-  }
-  return mode;
+// (plane_pitch: 0 for an interleaved window; every group counts from output column 0)
+uint32_t set_resize_window_mode(const void* d_out, uint64_t row_pitch, uint64_t plane_pitch, uint32_t dtype) {
+  return vector_mode((uintptr_t)d_out, set_tensor_elem_bytes(dtype), row_pitch, plane_pitch, 0, RS_MAX_MODE);
 }
 
 int set_resize_tensor_launch(void* stream, const uint8_t* d_tiles, uint64_t tile_stride, const uint8_t* d_packed,
@@ -237,20 +170,10 @@ int set_resize_tensor_launch(void* stream, const uint8_t* d_tiles, uint64_t tile
   if ((uint64_t)n_wins * a.bands > 0x7FFFFFFFull) return NICE_E_ARG;
   hipStream_t st = (hipStream_t)stream;
   const dim3 grid(n_wins * a.bands), block(TL_THREADS);
-  const bool planar = layout == NICE_TENSOR_PLANAR;
-  if (dtype == NICE_TENSOR_F32) {
-    if (planar) hipLaunchKernelGGL((set_resize_tensor<(int)NICE_TENSOR_F32, (int)NICE_TENSOR_PLANAR>), grid, block, 0, st, a);
-    else hipLaunchKernelGGL((set_resize_tensor<(int)NICE_TENSOR_F32, (int)NICE_TENSOR_INTERLEAVED>), grid, block, 0, st, a);
-  } else if (dtype == NICE_TENSOR_F16) {
-    if (planar) hipLaunchKernelGGL((set_resize_tensor<(int)NICE_TENSOR_F16, (int)NICE_TENSOR_PLANAR>), grid, block, 0, st, a);
-    else hipLaunchKernelGGL((set_resize_tensor<(int)NICE_TENSOR_F16, (int)NICE_TENSOR_INTERLEAVED>), grid, block, 0, st, a);
-  } else if (dtype == NICE_TENSOR_BF16) {
-    if (planar) hipLaunchKernelGGL((set_resize_tensor<(int)NICE_TENSOR_BF16, (int)NICE_TENSOR_PLANAR>), grid, block, 0, st, a);
-    else hipLaunchKernelGGL((set_resize_tensor<(int)NICE_TENSOR_BF16, (int)NICE_TENSOR_INTERLEAVED>), grid, block, 0, st, a);
-  } else {
-    return NICE_E_ARG;
-  }
-  return hipGetLastError() == hipSuccess ? NICE_OK : NICE_E_HIP;
+  const int rc = tensor_dispatch(dtype, layout, [&](auto dt, auto lay) {
+    hipLaunchKernelGGL((set_resize_tensor<decltype(dt)::value, decltype(lay)::value>), grid, block, 0, st, a);
+  });
+  return rc ? rc : hipGetLastError() == hipSuccess ? NICE_OK : NICE_E_HIP;
 }
 
 }  // namespace nice

@@ -76,13 +76,6 @@ __global__ __launch_bounds__(TL_THREADS) void set_resize_aa_weights(const SetRes
 }
 
 // ---- 2. the filter -------------------------------------------------------------------
-// x, held in a vector register: the scalar registers are short (the window, the
-// arguments and the loops' bounds fill them)
-__device__ __forceinline__ uint32_t aa_in_vgpr(uint32_t x) {
-  asm("" : "+v"(x));
-  return x;
-}
-
 // The taps lo..hi of output index x of an axis, and f of resize_pos where the axis does not reduce.
 struct AaTaps {
   uint32_t lo, hi, f;
@@ -111,20 +104,15 @@ __device__ __forceinline__ uint32_t aa_fetch(const SetResizeAaArgs& a, const Set
                                              uint32_t cy, uint32_t i) {
   const uint32_t xs = d.x0 + i, tx = xs / a.tw, cx = xs - tx * a.tw;
   const uint32_t p = slot_row + (tx - d.tx0);
-  const uint64_t s = a.src[p];
-  const uint32_t kind = (uint32_t)(s >> 62);
-  const uint64_t v = s & SLOT_SRC_VALUE;
-  if (kind > 1u || (a.slot_status && a.slot_status[p] != 0)) return 0u;
-  const uint64_t px = (uint64_t)cy * a.tw + cx;
-  const uint32_t b = kind == 0u ? ld32(a.tiles + v * a.tile_stride + 4ull * px) : ld_px_bytes(a.packed + v + 3ull * px, 3u, 0u);
-  return (b & 0xFFFFFFu) | (1u << 24);
+  const SlotSource s = slot_source(a.src, a.slot_status, a.tiles, a.tile_stride, a.packed, p);
+  if (s.bpp == 0u) return 0u;
+  return (ld_tap(s, cy * a.tw + cx) & 0xFFFFFFu) | (1u << 24);   // (a tile has at most 2^26 pixels)
 }
 
 // Block b: chunk b % chunks of band b / chunks % bands of window b / chunks / bands.
 template <int DT, int LAYOUT>
 __global__ __launch_bounds__(TL_THREADS) void set_resize_aa_tensor(SetResizeAaArgs a) {
-  using E = TensorElem<DT>;
-  using B = typename E::bits;
+  using B = typename TensorElem<DT>::bits;
   __shared__ uint32_t px[AA_LDS_PX];
   __shared__ uint32_t vw[TL_THREADS];   // [staged row][band row]: the weight, AA_IN_RANGE where the row is under its taps
   const uint32_t chunk = blockIdx.x % a.chunks, band = blockIdx.x / a.chunks % a.bands, wi = blockIdx.x / a.chunks / a.bands;
@@ -134,8 +122,8 @@ __global__ __launch_bounds__(TL_THREADS) void set_resize_aa_tensor(SetResizeAaAr
   const uint32_t xa = chunk * AA_COLS, xb = min(xa + AA_COLS, a.ow);
   const bool red_x = a.ow < d.rw, red_y = a.oh < d.rh;
   // (addresses the lanes add to: kept out of the scalar registers)
-  const uint16_t* const wcol = a.weights + aa_in_vgpr(d.wcol);
-  const uint16_t* const wrow = a.weights + aa_in_vgpr(d.wrow);
+  const uint16_t* const wcol = a.weights + in_vgpr(d.wcol);
+  const uint16_t* const wrow = a.weights + in_vgpr(d.wrow);
   // the block's source rows and columns (everything here is the same in every lane)
   const uint32_t jlo = aa_taps(ya, d.rh, a.oh).lo, jhi = aa_taps(yb - 1u, d.rh, a.oh).hi;
   const AaTaps ca = aa_taps(d.flip ? a.ow - 1u - xa : xa, d.rw, a.ow);
@@ -207,30 +195,20 @@ __global__ __launch_bounds__(TL_THREADS) void set_resize_aa_tensor(SetResizeAaAr
   }
   if (!active) return;
   B* const out = reinterpret_cast<B*>(d.out);
-  const uint64_t row_pitch = ((uint64_t)aa_in_vgpr((uint32_t)(d.row_pitch >> 32)) << 32) | aa_in_vgpr((uint32_t)d.row_pitch);
-  const uint64_t plane_pitch = ((uint64_t)aa_in_vgpr((uint32_t)(d.plane_pitch >> 32)) << 32) | aa_in_vgpr((uint32_t)d.plane_pitch);
+  const uint64_t row_pitch = in_vgpr64(d.row_pitch), plane_pitch = in_vgpr64(d.plane_pitch);
 #pragma unroll
   for (uint32_t y = 0; y < AA_ROWS; ++y) {
     if (ya + y < yb && !((bad >> y) & 1u)) {
       B* const orow = out + (uint64_t)(ya + y) * row_pitch;
       B e[3];
 #pragma unroll
-      for (uint32_t c = 0; c < 3; ++c) {
-        // the value is the fmaf rounded to binary32 and then to the type: the empty asm keeps the compiler
-        // from fusing both into v_fma_mixlo_f16, which rounds the exact sum once, to binary16
-        float v = __fmaf_rn(resize_unit(resize_aa_round(acc[y][c])), a.scale[c], a.bias[c]);
-        asm("" : "+v"(v));
-        e[c] = E::cvt(v);
-      }
+      for (uint32_t c = 0; c < 3; ++c)
+        e[c] = tensor_value<DT>(resize_unit(resize_aa_round(acc[y][c])), a.scale[c], a.bias[c]);
       if constexpr (LAYOUT == (int)NICE_TENSOR_INTERLEAVED && sizeof(B) == 4) {
         // a pixel's three float32 are 12 bytes at 4-byte alignment: one store
         *reinterpret_cast<AaThree*>(orow + 3ull * x) = AaThree{e[0], e[1], e[2]};
       } else {
-#pragma unroll
-        for (uint32_t c = 0; c < 3; ++c) {
-          if (LAYOUT == (int)NICE_TENSOR_PLANAR) orow[c * plane_pitch + x] = e[c];
-          else orow[3ull * x + c] = e[c];
-        }
+        st_one<B, LAYOUT>(orow, plane_pitch, x, [&](uint32_t c) { return e[c]; });
       }
     }
   }
@@ -244,28 +222,19 @@ int set_resize_aa_tensor_launch(void* stream, const uint8_t* d_tiles, uint64_t t
                                 uint32_t tile_h, uint32_t out_w, uint32_t out_h, uint32_t dtype, uint32_t layout,
                                 const float* scale, const float* bias) {
   if (n_wins == 0) return NICE_OK;
-  if (dtype != NICE_TENSOR_F32 && dtype != NICE_TENSOR_F16 && dtype != NICE_TENSOR_BF16) return NICE_E_ARG;
   SetResizeAaArgs a{d_tiles, tile_stride, d_packed, (const unsigned long long*)d_src, d_slot_status, d_wins, d_weights,
                     tile_w, tile_h, out_w, out_h, (out_h + AA_ROWS - 1u) / AA_ROWS, (out_w + AA_COLS - 1u) / AA_COLS,
                     {scale[0], scale[1], scale[2]}, {bias[0], bias[1], bias[2]}};
   const uint32_t tchunks = max_reducing ? (max_reducing + TL_THREADS - 1u) / TL_THREADS : 1u;
   if (2ull * n_wins * tchunks > 0x7FFFFFFFull || (uint64_t)n_wins * a.bands * a.chunks > 0x7FFFFFFFull) return NICE_E_ARG;
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(set_resize_aa_weights, dim3(2u * n_wins * tchunks), dim3(TL_THREADS), 0, st, d_wins, d_weights, out_w,
-                     out_h, tchunks);
   const dim3 grid(n_wins * a.bands * a.chunks), block(TL_THREADS);
-  const bool planar = layout == NICE_TENSOR_PLANAR;
-  if (dtype == NICE_TENSOR_F32) {
-    if (planar) hipLaunchKernelGGL((set_resize_aa_tensor<(int)NICE_TENSOR_F32, (int)NICE_TENSOR_PLANAR>), grid, block, 0, st, a);
-    else hipLaunchKernelGGL((set_resize_aa_tensor<(int)NICE_TENSOR_F32, (int)NICE_TENSOR_INTERLEAVED>), grid, block, 0, st, a);
-  } else if (dtype == NICE_TENSOR_F16) {
-    if (planar) hipLaunchKernelGGL((set_resize_aa_tensor<(int)NICE_TENSOR_F16, (int)NICE_TENSOR_PLANAR>), grid, block, 0, st, a);
-    else hipLaunchKernelGGL((set_resize_aa_tensor<(int)NICE_TENSOR_F16, (int)NICE_TENSOR_INTERLEAVED>), grid, block, 0, st, a);
-  } else {
-    if (planar) hipLaunchKernelGGL((set_resize_aa_tensor<(int)NICE_TENSOR_BF16, (int)NICE_TENSOR_PLANAR>), grid, block, 0, st, a);
-    else hipLaunchKernelGGL((set_resize_aa_tensor<(int)NICE_TENSOR_BF16, (int)NICE_TENSOR_INTERLEAVED>), grid, block, 0, st, a);
-  }
-  return hipGetLastError() == hipSuccess ? NICE_OK : NICE_E_HIP;
+  const int rc = tensor_dispatch(dtype, layout, [&](auto dt, auto lay) {   // (an unknown dtype launches neither)
+    hipLaunchKernelGGL(set_resize_aa_weights, dim3(2u * n_wins * tchunks), block, 0, st, d_wins, d_weights, out_w, out_h,
+                       tchunks);
+    hipLaunchKernelGGL((set_resize_aa_tensor<decltype(dt)::value, decltype(lay)::value>), grid, block, 0, st, a);
+  });
+  return rc ? rc : hipGetLastError() == hipSuccess ? NICE_OK : NICE_E_HIP;
 }
 
 }  // namespace nice

@@ -1,10 +1,10 @@
 // nice_sets_tensor.hip -- image sets, tensor output (include/nice.h, "image
 // sets: tensor output"): set_merge (nice_sets.hip) that converts as it stores.
 // The slot tables, the bands, the per-block window descriptor and the cut of a
-// tile to its window and image are set_merge's.  New: every output element is
-// fmaf(byte, scale[c], bias[c]) in binary32, stored as float32 or rounded to
-// nearest even to float16 / bfloat16; the window is planar or interleaved and
-// may be mirrored.  A lane takes P = 1, 2, 4 or 8 consecutive pixels: it loads
+// tile to its window and image (tile_cut) are set_merge's.  New: every output
+// element is fmaf(byte, scale[c], bias[c]) in binary32, stored as float32 or
+// rounded to nearest even to float16 / bfloat16 (tensor_value); the window is
+// planar or interleaved and may be mirrored.  A lane takes P = 1, 2, 4 or 8 consecutive pixels: it loads
 // them as P dwords (dense 4-byte slots) or 3 P bytes (raw slots) and stores P
 // elements per plane as one store of 4, 8 or 16 bytes; P is a field of the
 // window descriptor, so one launch serves windows of different alignment (a
@@ -16,6 +16,7 @@
 #include "../../include/nice.h"
 #include "nice_internal.h"
 #include "nice_sets_tensor.hpp"
+#include "nice_tile_geom.hpp"
 #include "nice_tiles.hpp"
 
 namespace nice {
@@ -36,31 +37,29 @@ struct SetTensorArgs {
   float scale[3], bias[3];
 };
 
-// Pixels [xa, xa + nxp) of rows [ya, yb) of the tile at st (origin tx0, ty0)
-// -> window d.  A lane takes the group of P = 1 << LP pixels at image column
-// P * g; a group that the tile, the window or the image cuts goes pixel by
-// pixel.  LP > 0: P divides x0 (flipped: x0 + rw), the pitches and, with
+// The cut c of the tile at st -> window d.  A lane takes the group of
+// P = 1 << LP pixels at image column P * g; a group that the tile, the window
+// or the image cuts goes pixel by pixel.  LP > 0: P divides x0 (flipped: x0 + rw), the pitches and, with
 // src_dwords, the tile width, and base and slots are aligned to match
 // (set_tensor_window_mode, set_merge_tensor_launch).
 template <int DT, int LAYOUT, int LP>
 __device__ __forceinline__ void set_tensor_rows(const SetTensorArgs& a, const SetTensorWindow& d, const uint8_t* st,
-                                                uint32_t tx0, uint32_t ty0, uint32_t xa, uint32_t nxp, uint32_t ya,
-                                                uint32_t yb) {
-  using E = TensorElem<DT>;
-  using B = typename E::bits;
+                                                const TileCut& c) {
+  using B = typename TensorElem<DT>::bits;
   constexpr uint32_t P = 1u << LP;
   constexpr uint32_t U = P == 8 ? TL_UNROLL / 2 : TL_UNROLL;   // at most 4 x 1 KiB of loads in flight per wave
   const uint32_t lane = threadIdx.x & 63u, wave = tl_wave();
-  const uint32_t xe = xa + nxp;
+  const uint32_t tx0 = c.tx0, ty0 = c.ty0, xa = c.xa, ya = c.ya, yb = c.yb, xe = xa + c.nxp;
   const uint32_t gb = xa >> LP, ge = (xe + P - 1u) >> LP;   // the groups of the image row that hold [xa, xe)
-  // lanes per row: the power of two that holds the groups, up to the wave; the other lanes take the rows below
-  uint32_t ls = 0;
-  while (ls < 6u && (1u << ls) < ge - gb) ++ls;
-  const uint32_t lpr = 1u << ls, rpw = 64u >> ls;
-  const uint32_t lx = lane & (lpr - 1u), ly = lane >> ls;
+  const RowShare rs = row_share(ge - gb);   // the lanes a row does not need take the rows below
+  const uint32_t lpr = rs.lpr, rpw = rs.rpw, lx = lane & (lpr - 1u), ly = lane >> rs.ls;
   const bool flip = d.flip != 0;
   const uint32_t xlast = d.x0 + d.rw - 1u;   // the window's last image column
   B* const out = reinterpret_cast<B*>(d.out);
+  // channel ch of the pixel px
+  const auto elem = [&](uint32_t px, uint32_t ch) {
+    return tensor_value<DT>((float)((px >> (8u * ch)) & 255u), a.scale[ch], a.bias[ch]);
+  };
   // (the unrolled steps go along the row; taking them down the rows where a row
   // is one step measured 8 % slower on the crop batch, at 12 VGPRs more)
   for (uint32_t y = ya + wave * rpw + ly; y < yb; y += TL_WAVES * rpw) {
@@ -113,38 +112,14 @@ __device__ __forceinline__ void set_tensor_rows(const SetTensorArgs& a, const Se
             uint32_t q[P];
 #pragma unroll
             for (uint32_t k = 0; k < P; ++k) q[k] = flip ? v[u][P - 1u - k] : v[u][k];
-            if (LAYOUT == (int)NICE_TENSOR_PLANAR) {
-#pragma unroll
-              for (uint32_t c = 0; c < 3; ++c) {
-                B e[P];
-#pragma unroll
-                for (uint32_t k = 0; k < P; ++k)
-                  e[k] = E::cvt(__fmaf_rn((float)((q[k] >> (8u * c)) & 255u), a.scale[c], a.bias[c]));
-                st_elems<B, P>(orow + c * d.plane_pitch + xo, e);
-              }
-            } else {
-              B e[3 * P];
-#pragma unroll
-              for (uint32_t k = 0; k < P; ++k) {
-#pragma unroll
-                for (uint32_t c = 0; c < 3; ++c)
-                  e[3 * k + c] = E::cvt(__fmaf_rn((float)((q[k] >> (8u * c)) & 255u), a.scale[c], a.bias[c]));
-              }
-#pragma unroll
-              for (uint32_t c = 0; c < 3; ++c) st_elems<B, P>(orow + 3ull * xo + c * P, e + c * P);
-            }
+            st_group<B, P, LAYOUT>(orow, d.plane_pitch, xo, [&](uint32_t k, uint32_t ch) { return elem(q[k], ch); });
           }
           if (!whole) {
 #pragma unroll
             for (uint32_t k = 0; k < P; ++k) {
               if (x + k >= xa && x + k < xe) {
                 const uint32_t xo = flip ? xlast - (x + k) : x + k - d.x0;
-#pragma unroll
-                for (uint32_t c = 0; c < 3; ++c) {
-                  const B e = E::cvt(__fmaf_rn((float)((v[u][k] >> (8u * c)) & 255u), a.scale[c], a.bias[c]));
-                  if (LAYOUT == (int)NICE_TENSOR_PLANAR) orow[c * d.plane_pitch + xo] = e;
-                  else orow[3ull * xo + c] = e;
-                }
+                st_one<B, LAYOUT>(orow, d.plane_pitch, xo, [&](uint32_t ch) { return elem(v[u][k], ch); });
               }
             }
           }
@@ -166,27 +141,20 @@ __global__ __launch_bounds__(TL_THREADS) void set_merge_tensor(SetTensorArgs a) 
   const SetTensorWindow d = a.wins[wi];
   const uint32_t t = a.slot_tile[slot];
   if (t >= d.n_tiles) return;
-  const uint32_t ty = t / d.nx, tx = t % d.nx;
-  // the tile's pixels inside the rectangle and the image: [xa, xb) x [ya, yb)
-  const uint64_t tx0 = (uint64_t)tx * a.tw, ty0 = (uint64_t)ty * a.th;
-  const uint64_t xa64 = max(tx0, (uint64_t)d.x0);
-  const uint64_t xb64 = min(min(tx0 + a.tw, (uint64_t)d.x0 + d.rw), (uint64_t)d.w);
-  const uint64_t ya64 = max(ty0 + (uint64_t)band * a.rows_pb, (uint64_t)d.y0);
-  const uint64_t yb64 = min(min(ty0 + min((uint64_t)(band + 1) * a.rows_pb, (uint64_t)a.th), (uint64_t)d.y0 + d.rh),
-                            (uint64_t)d.h);
-  if (xa64 >= xb64 || ya64 >= yb64) return;
-  const uint32_t xa = (uint32_t)xa64, nxp = (uint32_t)(xb64 - xa64), ya = (uint32_t)ya64, yb = (uint32_t)yb64;
+  // the tile's pixels inside the rectangle and the image
+  const TileCut c = tile_cut(t, d.nx, a.tw, a.th, band, a.rows_pb, d.x0, d.y0, d.rw, d.rh, d.w, d.h);
+  if (c.empty) return;
   const uint8_t* st = a.tiles + (a.src_off ? (uint64_t)a.src_off[slot] : (uint64_t)slot * a.tile_stride);
   const uint32_t mode = min(d.mode, a.mode_cap);
   if (mode == 3u) {   // (float32: the launch caps the mode at 2, 16 bytes per store)
     if constexpr (DT != (int)NICE_TENSOR_F32)
-      set_tensor_rows<DT, LAYOUT, 3>(a, d, st, (uint32_t)tx0, (uint32_t)ty0, xa, nxp, ya, yb);
+      set_tensor_rows<DT, LAYOUT, 3>(a, d, st, c);
   } else if (mode == 2u) {
-    set_tensor_rows<DT, LAYOUT, 2>(a, d, st, (uint32_t)tx0, (uint32_t)ty0, xa, nxp, ya, yb);
+    set_tensor_rows<DT, LAYOUT, 2>(a, d, st, c);
   } else if (mode == 1u) {
-    set_tensor_rows<DT, LAYOUT, 1>(a, d, st, (uint32_t)tx0, (uint32_t)ty0, xa, nxp, ya, yb);
+    set_tensor_rows<DT, LAYOUT, 1>(a, d, st, c);
   } else {
-    set_tensor_rows<DT, LAYOUT, 0>(a, d, st, (uint32_t)tx0, (uint32_t)ty0, xa, nxp, ya, yb);
+    set_tensor_rows<DT, LAYOUT, 0>(a, d, st, c);
   }
 }
 
@@ -199,18 +167,11 @@ namespace {
 uint32_t max_mode(uint32_t dtype) { return dtype == NICE_TENSOR_F32 ? 2u : 3u; }
 }  // namespace
 
+// (plane_pitch: 0 for an interleaved window; the groups count from x0, mirrored from x0 + rw)
 uint32_t set_tensor_window_mode(const void* d_out, uint64_t row_pitch, uint64_t plane_pitch, uint32_t x0, uint32_t rw,
-                                bool flip, uint32_t dtype, uint32_t layout) {
-  const uint64_t es = set_tensor_elem_bytes(dtype);
-  const uint64_t edge = flip ? (uint64_t)x0 + rw : x0;
-  uint32_t mode = 0;
-  for (uint32_t lp = 1; lp <= max_mode(dtype); ++lp) {
-    const uint64_t p = 1ull << lp;
-    if (((uintptr_t)d_out & (p * es - 1)) || (row_pitch & (p - 1)) || (edge & (p - 1))) break;
-    if (layout == NICE_TENSOR_PLANAR && (plane_pitch & (p - 1))) break;
-    mode = lp;
-  }
-  return mode;
+                                bool flip, uint32_t dtype) {
+  return vector_mode((uintptr_t)d_out, set_tensor_elem_bytes(dtype), row_pitch, plane_pitch, flip ? (uint64_t)x0 + rw : x0,
+                     max_mode(dtype));
 }
 
 int set_merge_tensor_launch(void* stream, const uint8_t* d_tiles, uint64_t tile_stride, const uint64_t* d_src_off,
@@ -234,20 +195,10 @@ int set_merge_tensor_launch(void* stream, const uint8_t* d_tiles, uint64_t tile_
   }
   hipStream_t st = (hipStream_t)stream;
   const dim3 grid(n_slots * a.bands), block(TL_THREADS);
-  const bool planar = layout == NICE_TENSOR_PLANAR;
-  if (dtype == NICE_TENSOR_F32) {
-    if (planar) hipLaunchKernelGGL((set_merge_tensor<(int)NICE_TENSOR_F32, (int)NICE_TENSOR_PLANAR>), grid, block, 0, st, a);
-    else hipLaunchKernelGGL((set_merge_tensor<(int)NICE_TENSOR_F32, (int)NICE_TENSOR_INTERLEAVED>), grid, block, 0, st, a);
-  } else if (dtype == NICE_TENSOR_F16) {
-    if (planar) hipLaunchKernelGGL((set_merge_tensor<(int)NICE_TENSOR_F16, (int)NICE_TENSOR_PLANAR>), grid, block, 0, st, a);
-    else hipLaunchKernelGGL((set_merge_tensor<(int)NICE_TENSOR_F16, (int)NICE_TENSOR_INTERLEAVED>), grid, block, 0, st, a);
-  } else if (dtype == NICE_TENSOR_BF16) {
-    if (planar) hipLaunchKernelGGL((set_merge_tensor<(int)NICE_TENSOR_BF16, (int)NICE_TENSOR_PLANAR>), grid, block, 0, st, a);
-    else hipLaunchKernelGGL((set_merge_tensor<(int)NICE_TENSOR_BF16, (int)NICE_TENSOR_INTERLEAVED>), grid, block, 0, st, a);
-  } else {
-    return NICE_E_ARG;
-  }
-  return hipGetLastError() == hipSuccess ? NICE_OK : NICE_E_HIP;
+  const int rc = tensor_dispatch(dtype, layout, [&](auto dt, auto lay) {
+    hipLaunchKernelGGL((set_merge_tensor<decltype(dt)::value, decltype(lay)::value>), grid, block, 0, st, a);
+  });
+  return rc ? rc : hipGetLastError() == hipSuccess ? NICE_OK : NICE_E_HIP;
 }
 
 }  // namespace nice

@@ -14,6 +14,7 @@
 
 #include "../../include/nice.h"
 #include "nice_internal.h"
+#include "nice_tile_geom.hpp"
 #include "nice_tiles.hpp"
 
 namespace nice {
@@ -110,21 +111,14 @@ __global__ __launch_bounds__(TL_THREADS) void tiles_merge(MergeArgs a, TileGrid 
   if (a.slot_status && a.slot_status[slot] != 0) return;
   const uint32_t t = a.tile_idx[slot];
   if (t >= a.n_tiles) return;
-  const uint32_t ty = t / q.nx, tx = t % q.nx;
   const uint32_t lane = threadIdx.x & 63u, wave = tl_wave();
-  // the tile's pixels inside the rectangle and the image: [xa, xb) x [ya, yb)
-  const uint64_t tx0 = (uint64_t)tx * q.tw, ty0 = (uint64_t)ty * q.th;
-  const uint64_t xa64 = max(tx0, (uint64_t)a.x0);
-  const uint64_t xb64 = min(min(tx0 + q.tw, (uint64_t)a.x0 + a.rw), (uint64_t)q.w);
-  const uint64_t ya64 = max(ty0 + (uint64_t)band * q.rows_pb, (uint64_t)a.y0);
-  const uint64_t yb64 = min(min(ty0 + min((uint64_t)(band + 1) * q.rows_pb, (uint64_t)q.th), (uint64_t)a.y0 + a.rh),
-                            (uint64_t)q.h);
-  if (xa64 >= xb64 || ya64 >= yb64) return;
-  const uint32_t xa = (uint32_t)xa64, xb = (uint32_t)xb64, ya = (uint32_t)ya64, yb = (uint32_t)yb64;
+  // the tile's pixels inside the rectangle and the image
+  const TileCut c = tile_cut(t, q.nx, q.tw, q.th, band, q.rows_pb, a.x0, a.y0, a.rw, a.rh, q.w, q.h);
+  if (c.empty) return;
+  const uint32_t xa = c.xa, nxp = c.nxp, ya = c.ya, yb = c.yb;
   const uint8_t* st = a.tiles + (a.src_off ? (uint64_t)a.src_off[slot] : (uint64_t)slot * a.tile_stride);
-  const uint32_t nxp = xb - xa;
   for (uint32_t y = ya + wave; y < yb; y += TL_WAVES) {
-    const uint8_t* srow = st + ((uint64_t)(y - (uint32_t)ty0) * q.tw + (xa - (uint32_t)tx0)) * a.tc;
+    const uint8_t* srow = st + ((uint64_t)(y - c.ty0) * q.tw + (xa - c.tx0)) * a.tc;
     uint8_t* drow = a.out + (uint64_t)(y - a.y0) * a.out_pitch + (uint64_t)(xa - a.x0) * a.oc;
     if (MODE == TL_QUAD) {   // xa, x0 and the tile's x origin are multiples of 4: both rows are 16-byte aligned
       const uint32_t G = (nxp + 3u) >> 2;
@@ -390,24 +384,17 @@ __global__ __launch_bounds__(TL_THREADS) void alpha_merge(AlphaMergeArgs a, Tile
   const unsigned long long src = a.src[slot];
   if (kind == 0 && a.dec_status[src] != 0) return;
   const uint32_t t = a.tile_idx[slot];
-  const uint32_t ty = t / q.nx, tx = t % q.nx;
   const uint32_t lane = threadIdx.x & 63u, wave = tl_wave();
-  const uint64_t tx0 = (uint64_t)tx * q.tw, ty0 = (uint64_t)ty * q.th;
-  const uint64_t xa64 = max(tx0, (uint64_t)a.x0);
-  const uint64_t xb64 = min(min(tx0 + q.tw, (uint64_t)a.x0 + a.rw), (uint64_t)q.w);
-  const uint64_t ya64 = max(ty0 + (uint64_t)band * q.rows_pb, (uint64_t)a.y0);
-  const uint64_t yb64 = min(min(ty0 + min((uint64_t)(band + 1) * q.rows_pb, (uint64_t)q.th), (uint64_t)a.y0 + a.rh),
-                            (uint64_t)q.h);
-  if (xa64 >= xb64 || ya64 >= yb64) return;
-  const uint32_t xa = (uint32_t)xa64, xb = (uint32_t)xb64, ya = (uint32_t)ya64, yb = (uint32_t)yb64;
+  const TileCut c = tile_cut(t, q.nx, q.tw, q.th, band, q.rows_pb, a.x0, a.y0, a.rw, a.rh, q.w, q.h);
+  if (c.empty) return;
+  const uint32_t xa = c.xa, nxp = c.nxp, ya = c.ya, yb = c.yb;
   const bool cst = kind == 2;
   const uint32_t cval = (uint32_t)src & 255u;
   // the tile's plane: row pitch and first byte (unused for a constant)
   const uint32_t sp = kind == 0 ? a.aw3 : q.tw;
   const uint8_t* st = cst ? a.out : kind == 0 ? a.dec + src * a.dec_stride : a.packed + src;
-  const uint32_t nxp = xb - xa;
   for (uint32_t y = ya + wave; y < yb; y += TL_WAVES) {
-    const uint8_t* srow = st + (uint64_t)(y - (uint32_t)ty0) * sp + (xa - (uint32_t)tx0);
+    const uint8_t* srow = st + (uint64_t)(y - c.ty0) * sp + (xa - c.tx0);
     uint8_t* drow = a.out + (uint64_t)(y - a.y0) * a.out_pitch + 4ull * (xa - a.x0);
     alpha_merge_row<MODE>(srow, drow, nxp, cst, cval, lane);
   }

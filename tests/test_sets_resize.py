@@ -17,7 +17,7 @@ import pytest
 from test_sets import (CROPS, K, PH_DEC_TABLES, _cuda, _random_image, _slot_counts, _timing, _touched, encoded, last_set,
                        ref)
 from test_sets_tensor import (BF16, CROP_FLIPS, DTYPES, F16, F32, INTERLEAVED, PLANAR, POISON, POISON_BITS, _merge_tensor,
-                              _tdtype, bits_of)
+                              _tdtype, bits_of, expect_bits, holds_halfway, lut_bits, plant_halfway)
 from test_sets_tensor_cpu import const_sets
 from test_sets_resize_cpu import model_bits, positions
 
@@ -260,6 +260,29 @@ def test_identity_size_equals_the_tensor_merge(nice, ctx, dt, layout):
     want, _ = _merge_tensor(nice, ctx, imgs, 8, 6, windows, dt, layout, leads, flips, "odd")
     for wdw, a, b in zip(windows, got, want):
         assert np.array_equal(a, b), wdw
+
+
+def check_float16_rounds_twice(nice, ctx, run, layout):
+    """float16 on the constants whose elements differ between one rounding and
+    two (tests/test_sets_tensor_cpu.py), through `run` (_resize, or the
+    antialiased harness): three windows of the output's size, so acc = b << 16
+    and an element is the table's; each holds the 14 entries, planted; stores of
+    4, 1 and 2 elements, one window mirrored."""
+    imgs = _images()
+    windows = [(0, 3, 2, 10, 7), (0, 30, 23, 10, 7), (1, 27, 0, 10, 7)]
+    leads, flips = [0, 1, 2], [0, 1, 0]
+    for i, x0, y0, rw, rh in windows:
+        plant_halfway(imgs[i], x0, y0, rw, rh)
+        assert holds_halfway(imgs[i][y0:y0 + rh, x0:x0 + rw])
+    table = lut_bits(nice, "halfway", "float16")
+    got, _ = run(nice, ctx, imgs, 8, 6, windows, (7, 10), F16, layout, leads, flips, const_sets(nice)["halfway"])
+    for (i, x0, y0, rw, rh), flip, a in zip(windows, flips, got):
+        assert np.array_equal(a, expect_bits(table, imgs[i][y0:y0 + rh, x0:x0 + rw], flip)), (i, x0, y0)
+
+
+@pytest.mark.parametrize("layout", [PLANAR, INTERLEAVED])
+def test_identity_size_float16_rounds_twice(nice, ctx, layout):
+    check_float16_rounds_twice(nice, ctx, _resize, layout)
 
 
 # ---- 2. end to end on the reference set -------------------------------------------------------------

@@ -23,7 +23,7 @@ from test_sets_tensor import (BF16, CROP_FLIPS, DTYPES, F16, F32, INTERLEAVED, P
                               _tdtype, bits_of)
 from test_sets_tensor_cpu import const_sets
 from test_sets_resize import (FLIPS, KIND_DENSE, KIND_NONE, KIND_RAW, LEADS, ODD, RCROPS, RFLIPS, RSIZE, SHAPES, SIZES,
-                              WINDOWS, _images, _merges, _resize, garbage_tiles)
+                              WINDOWS, _images, _merges, _resize, check_float16_rounds_twice, garbage_tiles)
 from test_sets_resize_cpu import model_bits
 from test_sets_resize_aa_cpu import aa_taps, model_bits_aa, tap_ranges
 
@@ -283,6 +283,12 @@ def test_identity_size_equals_the_tensor_merge(nice, ctx, dt, layout):
     want, _ = _merge_tensor(nice, ctx, imgs, 8, 6, windows, dt, layout, leads, flips, "odd")
     for wdw, a, b in zip(windows, got, want):
         assert np.array_equal(a, b), wdw
+
+
+@pytest.mark.parametrize("layout", [PLANAR, INTERLEAVED])
+def test_identity_size_float16_rounds_twice(nice, ctx, layout):
+    """The filter's elements too are the float32 fmaf rounded again (tests/test_sets_resize.py)."""
+    check_float16_rounds_twice(nice, ctx, _resize_aa, layout)
 
 
 # ---- 2. end to end on the reference set -------------------------------------------------------------

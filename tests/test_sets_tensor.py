@@ -16,7 +16,7 @@ import pytest
 from test_tiled import np_tiles
 from test_sets import (CROPS, K, MERGE_SHAPES, MERGE_WINDOWS, PH_DEC_TABLES, PH_ENC_CLASSIFY, _cuda, _random_image,
                        _slot_counts, _timing, _touched, encoded, last_set, ref)
-from test_sets_tensor_cpu import const_sets, lut32
+from test_sets_tensor_cpu import HALFWAY, const_sets, lut32
 
 pytestmark = pytest.mark.gpu
 
@@ -177,6 +177,42 @@ def test_merge_tensor_matches_table(nice, ctx, tw, th, c, dt, layout):
     outs, poison = _merge_tensor(nice, ctx, imgs, tw, th, MERGE_WINDOWS, dt, layout, TENSOR_LEADS, TENSOR_FLIPS, "odd")
     for wdw, flip, got in zip(MERGE_WINDOWS, TENSOR_FLIPS, outs):
         assert np.array_equal(got, _expect_window(table, imgs[wdw[0]], wdw, flip, tw, th, poison)), wdw
+
+
+def plant_halfway(img, x0, y0, rw, rh):
+    """The 14 (byte, channel) pairs of HALFWAY into the first pixels of the
+    window, row by row: seven pixels hold them all, a smaller window what fits."""
+    for i in range(min(7, rw * rh)):
+        y, x = divmod(i, rw)
+        img[y0 + y, x0 + x, :3] = [HALFWAY[c][i % len(HALFWAY[c])] for c in range(3)]
+
+
+def holds_halfway(px):
+    """Whether the pixels [rh, rw, >= 3] hold one of the (byte, channel) pairs of HALFWAY."""
+    return any(np.isin(px[:, :, c], HALFWAY[c]).any() for c in range(3))
+
+
+@pytest.mark.parametrize("layout", [PLANAR, INTERLEAVED])
+@pytest.mark.parametrize("raw_lead", [None, 1])
+def test_merge_tensor_float16_rounds_twice(nice, ctx, raw_lead, layout):
+    """float16 on the constants whose elements differ between one rounding and
+    two (tests/test_sets_tensor_cpu.py): the element is the float32 fmaf rounded
+    again, in every store width (the leads give 1, 2 and 8 pixels per lane), for
+    dense 4-byte slots and raw ones.  Every window holds such an element: the
+    large ones among their random bytes, the small ones planted."""
+    c = 4 if raw_lead is None else 3
+    imgs = [_random_image(w, h, c, i) for i, (w, h) in enumerate(MERGE_SHAPES)]
+    for i, x0, y0, rw, rh in MERGE_WINDOWS:
+        if rw * rh < 100:                                  # 9 x 11, 3 x 7, 1 x 1
+            plant_halfway(imgs[i], x0, y0, rw, rh)
+    for i, x0, y0, rw, rh in MERGE_WINDOWS:
+        assert rw * rh < 64 or holds_halfway(imgs[i][y0:y0 + rh, x0:x0 + rw]), (i, x0, y0)
+    assert sum(rw * rh < 100 for _, _, _, rw, rh in MERGE_WINDOWS) == 3
+    table = lut_bits(nice, "halfway", "float16")
+    outs, poison = _merge_tensor(nice, ctx, imgs, 64, 64, MERGE_WINDOWS, F16, layout, TENSOR_LEADS, TENSOR_FLIPS, "halfway",
+                                 raw_lead=raw_lead)
+    for wdw, flip, got in zip(MERGE_WINDOWS, TENSOR_FLIPS, outs):
+        assert np.array_equal(got, _expect_window(table, imgs[wdw[0]], wdw, flip, 64, 64, poison)), wdw
 
 
 @pytest.mark.parametrize("flip", [0, 1])

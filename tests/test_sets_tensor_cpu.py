@@ -2,10 +2,15 @@
 parts that need no GPU: normalize_affine, the exactness on which the table
 reference of tests/test_sets_tensor.py rests, and the header.
 
-The reference of an element is fmaf(b, scale, bias) in float32.  For the three
+The reference of an element is fmaf(b, scale, bias) in float32.  For the four
 constant sets below b * scale + bias is exact in double (asserted here with
 rationals), so rounding that double once to float32 gives the fused result: a
-256 x 3 table per constant set, which the GPU tests look pixels up in."""
+256 x 3 table per constant set, which the GPU tests look pixels up in.
+
+A float16 element is that float32 rounded again.  `halfway` holds the entries
+for which rounding the exact sum once, to float16, gives other bits (HALFWAY):
+a kernel that fuses the multiply-add with the conversion fails on them, and on
+no entry of the other three sets."""
 import os
 import re
 import struct
@@ -28,7 +33,14 @@ def const_sets(nice):
     """name -> (scale, bias), float32 values as Python floats."""
     return {"unit": ((f32(1 / 255),) * 3, (0.0,) * 3),
             "imagenet": nice.normalize_affine(IMAGENET_MEAN, IMAGENET_STD),
-            "odd": (tuple(f32(v) for v in (-0.0123, 3.5, 1 / 3)), tuple(f32(v) for v in (7.25, -100, 1e-3)))}
+            "odd": (tuple(f32(v) for v in (-0.0123, 3.5, 1 / 3)), tuple(f32(v) for v in (7.25, -100, 1e-3))),
+            "halfway": (tuple(float.fromhex(v) for v in ("0x1.4234f8p-8", "0x1.3745d4p-6", "0x1.ea8960p-7")),
+                        tuple(float.fromhex(v) for v in ("0x1.eabffep-1", "0x1.31fffcp+1", "0x1.abc95cp-1")))}
+
+
+# channel -> the bytes of `halfway` whose float16 differs between rounding the exact sum once and rounding it to
+# float32 first
+HALFWAY = {0: (29, 58, 87, 116, 145, 174, 203), 1: (143, 187, 209, 253), 2: (18, 141, 223)}
 
 
 def lut32(scale, bias):
@@ -57,7 +69,7 @@ def test_normalize_affine_is_the_rounded_double_expression():
 
 
 def test_table_reference_is_exact_in_double():
-    """For every byte and channel of the three constant sets the double
+    """For every byte and channel of the four constant sets the double
     b * scale + bias equals the rational one: its one rounding to float32 is
     the fused multiply-add's.  And no entry is subnormal or infinite in float32
     or float16, so no flush-to-zero mode can hide or cause a failure."""
@@ -65,6 +77,7 @@ def test_table_reference_is_exact_in_double():
     for name, (scale, bias) in const_sets(nice).items():
         table = lut32(scale, bias)
         for c in range(3):
+            assert scale[c] == f32(scale[c]) and bias[c] == f32(bias[c]), (name, c)      # float32 holds the constants
             s, t = Fraction(scale[c]), Fraction(bias[c])
             for b in range(256):
                 exact = b * s + t
@@ -75,6 +88,22 @@ def test_table_reference_is_exact_in_double():
         assert np.isfinite(table).all() and (mag < 65504.0).all(), name
         assert ((mag == 0) | (mag >= 2.0 ** -14)).all(), name              # normal in float16, hence in float32 and bfloat16
         assert np.isfinite(table.astype(np.float16)).all(), name
+
+
+def test_float16_rounds_twice_and_only_halfway_shows_it():
+    """The float16 element is the float32 table rounded again.  Rounding the
+    exact sum (the double table) once to float16 instead, as a multiply-add
+    fused with its conversion does, differs at exactly the 14 entries of
+    HALFWAY, and at no entry of the other three sets: they cannot tell the two
+    apart."""
+    nice = nice_pkg()
+    for name, (scale, bias) in const_sets(nice).items():
+        b = np.arange(256, dtype=np.float64)[:, None]
+        exact = b * np.array(scale, np.float64)[None, :] + np.array(bias, np.float64)[None, :]
+        twice, once = lut32(scale, bias).astype(np.float16), exact.astype(np.float16)
+        differ = {c: tuple(int(v) for v in np.nonzero(twice[:, c] != once[:, c])[0]) for c in range(3)}
+        assert differ == (HALFWAY if name == "halfway" else {0: (), 1: (), 2: ()}), name
+    assert sum(len(v) for v in HALFWAY.values()) == 14
 
 
 def test_unfused_form_differs():
